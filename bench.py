@@ -2,7 +2,7 @@
 """Headline benchmark: GStencils/s of the stencil sweep, star2d1r 16384 x 16384 fp64 (BASELINE.json configs[1]),
 on N MI355X GPUs of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one kernel application (one sweep of the whole grid): the reference's time-step loop body
@@ -16,7 +16,13 @@ E launches, hidden behind the next launch's interior (lorastencil_amd/slab.py).
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N ranks (a
 torch.distributed.run child, before this process touches the GPU) and relays rank 0's line.
 
-The single JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line: `value` (GStencils/s), `ms_per_step` (the
+milliseconds of one timed step) and the configuration.  `--dump-outputs DIR` also writes what the last timed step left
+in the result grid, as the caller receives it: its interior as DIR/out.npy (float64; float32 for bf16) when that fits in
+48 MB, otherwise the values at a fixed seeded sample of interior points (4 Mi draws) as DIR/out_sample.npy, the same
+points for the same sizes.  The inputs are seeded: the same arguments give the same inputs in every run.
+
+With `--full` the JSON line also carries
   roofline      for the dominant kernel, against both roofs (`hbm`, `fp64`; `bound` / `frac` name the nearer one).  hbm:
                 COMPULSORY bytes per launch (one read + one write of every interior point, 2 x sizeof(T) x points,
                 however many applications the launch fuses) / its average launch duration (HIP events on the launch
@@ -33,7 +39,8 @@ The single JSON line also carries
                 by default -- one hipGraph replay of the K sweeps, captured before the timed region
                 (`config.graph_replay`); their per-launch durations come from an untimed profiled run of the same K;
   cpu_baseline  the CPU oracle (a port of the reference's test_cpu loop) timed on this box's host cores on a
-                bounded sample of the same workload (rank 0, N = 1 only).
+                bounded sample of the same workload (rank 0, N = 1 only);
+and a `--full` run guards against a throttled timed region (one more launch behind it; `roofline.retimed`).
 """
 from __future__ import annotations
 
@@ -72,7 +79,14 @@ def parse_args():
                          "launch path on a box without a GPU (no kernel runs, nothing is measured)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the copy-bandwidth reference, the throttle guard and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 DEFAULT_SIZES = {"star2d1r": (16384, 16384), "box2d3r": (8192, 8192), "box2d1r": (8192, 8192), "star2d3r": (16384, 16384),
@@ -185,6 +199,44 @@ def planned_launches(ndim, times, spl, fused_ok=True):
     nk = sum(1 for d in depths if d == spl and spl > 1)
     ns = sum(1 for d in depths if d == 1) if spl > 1 else len(depths)
     return nk, len(depths) - nk - ns, ns
+
+
+DUMP_WHOLE_BYTES = 48 << 20  # an interior up to this size is written whole
+DUMP_SAMPLE_POINTS = 4 << 20  # otherwise this many seeded draws (32 MB in fp64 at most)
+DUMP_SEED = 20261016
+
+
+def output_arrays(shape, dims, result):
+    """{name: array} of what a run leaves in its padded result grid `result` (torch, on the device or the host): the
+    interior, whole if it fits in DUMP_WHOLE_BYTES, else at a fixed seeded sample of interior points (sorted, without
+    repeats; the same points for the same sizes).  float64, float32 for bf16 grids (exact)."""
+    import numpy as np
+    import torch
+
+    from lorastencil_amd.ops import halo, padded_shape
+
+    h = halo(shape)
+    assert tuple(result.shape) == padded_shape(shape, dims), (tuple(result.shape), dims)
+    ftype = torch.float32 if result.dtype == torch.bfloat16 else torch.float64
+    n = 1
+    for d in dims:
+        n *= d
+    if n * ftype.itemsize <= DUMP_WHOLE_BYTES:
+        inner = result[tuple(slice(k, k + d) for k, d in zip(h, dims))]
+        return {"out": inner.to(ftype).cpu().numpy()}
+    flat = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE_POINTS, dtype=np.int64))
+    coords = np.unravel_index(flat, dims)
+    idx = np.ravel_multi_index(tuple(c + k for c, k in zip(coords, h)), tuple(result.shape))
+    vals = result.reshape(-1)[torch.from_numpy(idx).to(result.device)]
+    return {"out_sample": vals.to(ftype).cpu().numpy()}
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def main():
@@ -305,7 +357,9 @@ def main():
             drv.load_local(src0)
             drv.refresh_ghosts()  # neighbours' own rows of time level 0 into the ghost zones
 
-    # achievable-bandwidth reference of THIS box, in this run: a device copy of the same grid (read + write once)
+    # achievable-bandwidth reference of THIS box, in this run: a device copy of the same grid (read + write once).  A plain
+    # run makes the copies too and reports only with --full: they are the device's first sustained load, ahead of the
+    # warm-up, and without them the timed sweeps of the headline configuration ran 1.7 % slower (5 alternating runs each)
     copy_gbs = None
     if world == 1:
         dst_c = torch.empty_like(src0)
@@ -354,7 +408,7 @@ def main():
         if graph_replay:
             plan.run(b0, b1, K, stream=side)
             side.synchronize()
-        elif world == 1:
+        elif world == 1 and args.full:
             prof_ = plan.run_profiled(b0, b1, K)  # = plan.run + events around its fused / single-sweep launches; blocks
         else:
             run(K)
@@ -368,7 +422,15 @@ def main():
             el = float(t.item())
         return el, ev0.elapsed_time(ev1), prof_
 
+    def take_outputs():
+        """The result grid of the region just timed, sampled (every rank takes part in a slab run's gather)."""
+        if args.dump_outputs is None:
+            return None
+        result = (b0, b1)[K % 2] if world == 1 else drv.gather_global(0)
+        return output_arrays(shape, dims, result) if rank == 0 else None
+
     elapsed, ev_ms, prof = timed_region()
+    outputs = take_outputs()
     # Throttle guard.  Twice in some fifty runs of this round a whole timed region ran FOUR times slower than every run
     # around it on the same code (83 ms instead of 21 for the 100 sweeps; the copy-bandwidth reference measured a moment
     # earlier in the same process was normal): the box, not the kernels.  The yardstick is this run's own: ONE more fused
@@ -376,7 +438,7 @@ def main():
     # sweep as that launch, the region is timed ONCE more and both figures are reported.
     retimed = None
     probe_ms_per_sweep = None
-    if not graph_replay:
+    if args.full and not graph_replay:
         n_probe = max(1, int(plan.get_option("steps_per_launch")))
         n_probe += n_probe & 1  # (an even count: the buffers' halo state as at the start of a run)
         reset()
@@ -388,7 +450,7 @@ def main():
         barrier()
         probe_ms_per_sweep = p_ev0.elapsed_time(p_ev1) / n_probe
     slow = bool(probe_ms_per_sweep and elapsed * 1e3 / K > 2.0 * probe_ms_per_sweep)
-    if world > 1:
+    if world > 1 and args.full:
         f = torch.tensor([1.0 if slow else 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(f, op=dist.ReduceOp.MAX)
         slow = bool(f.item() > 0)
@@ -396,9 +458,10 @@ def main():
         first_ms = elapsed * 1e3
         reset()
         elapsed, ev_ms, prof = timed_region()
+        outputs = take_outputs()
         retimed = {"first_region_ms": round(first_ms, 3), "probe_ms_per_sweep": round(probe_ms_per_sweep, 4),
                    "reason": "the first timed region ran > 2 x slower per sweep than one more launch right behind it: timed once more"}
-    if graph_replay:
+    if graph_replay and args.full:
         reset()
         torch.cuda.synchronize()
         prof = plan.run_profiled(b0, b1, K)  # untimed: launch counts and durations of the same schedule
@@ -407,6 +470,42 @@ def main():
     for d in dims:
         points *= d
     value = points * K / elapsed / 1e9
+    if rank == 0:
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
+        res = {
+            "metric": "GStencils/s",
+            "value": round(value, 3),
+            "unit": "GStencils/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": round(elapsed * 1e3 / K, 6),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {
+                "workload": f"{shape} {'x'.join(map(str, dims))} {'bf16' if bf16 else 'fp64'}, {K} sweeps (lorastencil_{len(dims)}d {shape} "
+                            f"{' '.join(map(str, dims))} {K})",
+                "parallelism": (f"row-slabs x{world}, ghost {drv.layout.ghost} rows refreshed every "
+                                f"{drv.exchange_every} launches ({drv.exchange_mode}, "
+                                f"{'boundary strips first' if drv.overlap else 'whole slab per launch'}, deferred wait)")
+                               if world > 1 else "single GPU",
+                "kernel": kernel,
+                "variant": {1: "direct", 2: "mfma"}.get(plan.get_option("variant"), "?"),
+                "normalised_taps": bool(normalised),
+                "graph_replay": graph_replay,
+            },
+            "value_reference_convention": round(value * L.ops.gstencil_factor(shape), 3),
+        }
+        if not args.full:
+            print(json.dumps(res), flush=True)
+    if not args.full:
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # The dominant kernel and its average launch duration over the timed region.  One launch applies `spl` sweeps
     # (temporal fusion) but moves the grid through HBM once: compulsory bytes per launch = 2 x sizeof(T) x points.
     if world == 1:
@@ -501,33 +600,8 @@ def main():
     else:
         bound_hbm = hbm_frac >= arith_frac
     if rank == 0:
-        res = {
-            "metric": "GStencils/s",
-            "value": round(value, 3),
-            "unit": "GStencils/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": round(elapsed * 1e3 / K, 6),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {
-                "workload": f"{shape} {'x'.join(map(str, dims))} {'bf16' if bf16 else 'fp64'}, {K} sweeps (lorastencil_{len(dims)}d {shape} "
-                            f"{' '.join(map(str, dims))} {K})",
-                "parallelism": (f"row-slabs x{world}, ghost {drv.layout.ghost} rows refreshed every "
-                                f"{drv.exchange_every} launches ({drv.exchange_mode}, "
-                                f"{'boundary strips first' if drv.overlap else 'whole slab per launch'}, deferred wait)")
-                               if world > 1 else "single GPU",
-                "kernel": kernel,
-                "variant": {1: "direct", 2: "mfma"}.get(plan.get_option("variant"), "?"),
-                "normalised_taps": bool(normalised),
-                "steps_per_launch": spl,
-                "graph_replay": graph_replay,
-            },
-            "value_reference_convention": round(value * L.ops.gstencil_factor(shape), 3),
+        res["config"].update(kernel=kernel, steps_per_launch=spl)
+        res.update({
             "roofline": {
                 # `bound`: the resource this kernel uses the larger share of -- the HBM stream (measured bytes per launch
                 # against a plain copy on this box) or the vector pipe (SQ_ACTIVE_INST_VALU busy share) -- from the kernel's
@@ -584,7 +658,7 @@ def main():
                 "tail_fused_launches": (prof.two_launches if prof else 0),
                 "single_sweep_launches": (prof.single_launches if prof else None),
             },
-        }
+        })
         if world == 1 and not args.no_cpu_baseline and not bf16:
             res["cpu_baseline"] = cpu_baseline(shape, dims, args.cpu_seconds)
         print(json.dumps(res), flush=True)

@@ -9,6 +9,12 @@ So step 1 is exactly what the reference's CHECK_ERROR block compares against; st
 driver semantics read from the reference host code.
 
 Each fixture holds data only: `input`, `params`, `dims`, and `out_t<k>` = whole padded buffer [k % 2] after k steps.
+
+`--ref-pins` writes the three fixtures that pin the oracle to test_cpu without oracle/_ref (tests/test_oracle.py):
+  ref_random_params.npz   one sweep of test_cpu on gaussian input and taps: `<shape>_input`, `<shape>_params`, `<shape>_out`
+  ref_chain.npz           `<shape>_t5`, `<shape>_t6`: the chain on the fixtures' inputs above, buffer [t % 2]
+  ref_1d1r_config0.npz    BASELINE configs[0] (1d1r 2^20, 100 steps): `sha256` of the result's bytes (float64, last
+                          element excluded: the operator leaves it untouched) and every 4096th element as `sample`
 """
 import os
 import sys
@@ -32,6 +38,9 @@ CASES = {
     "box3d1r": (8, 16, 128),
 }
 STEPS = (1, 2, 3, 4)
+RANDOM_PARAMS_CASES = [("1d1r", (96,)), ("star2d1r", (16, 32)), ("box2d3r", (8, 24)), ("star2d3r", (12, 20)),
+                       ("star3d1r", (5, 6, 18)), ("box3d1r", (4, 9, 10))]
+CHAIN_STEPS = (5, 6)
 
 
 def main():
@@ -49,5 +58,37 @@ def main():
         print(f"{shape:10s} dims={dims} -> {os.path.getsize(path)} bytes")
 
 
+def ref_pins():
+    if not ref.available():
+        sys.exit("oracle/_ref is missing: run oracle/build_ref.sh (needs the reference's sources)")
+    import hashlib
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    data = {}
+    rng = np.random.default_rng(42)
+    for shape, dims in RANDOM_PARAMS_CASES:
+        a = rng.standard_normal(o.padded_shape(shape, dims))
+        p = rng.standard_normal(o.NTAPS[len(dims)])
+        data.update({f"{shape}_input": a, f"{shape}_params": p, f"{shape}_out": ref.test_cpu(a, p)})
+    np.savez_compressed(os.path.join(here, "ref_random_params.npz"), **data)
+    data = {}
+    for shape, dims in CASES.items():
+        a = o.reference_input(shape, dims)
+        for t in CHAIN_STEPS:
+            data[f"{shape}_t{t}"] = ref.run_chain(a, o.default_params(shape), t)
+    np.savez_compressed(os.path.join(here, "ref_chain.npz"), **data)
+    a = o.reference_input("1d1r", (1 << 20,))
+    exp = ref.run_chain(a, o.default_params("1d1r"), 100)
+    assert np.isfinite(exp).all()
+    body = np.ascontiguousarray(exp[:-1], dtype="<f8")
+    np.savez_compressed(os.path.join(here, "ref_1d1r_config0.npz"), sha256=np.array(hashlib.sha256(body.tobytes()).hexdigest()),
+                        sample=body[::4096].copy())
+    for f in ("ref_random_params.npz", "ref_chain.npz", "ref_1d1r_config0.npz"):
+        print(f"{f:24s} {os.path.getsize(os.path.join(here, f))} bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if "--ref-pins" in sys.argv[1:]:
+        ref_pins()
+    else:
+        main()

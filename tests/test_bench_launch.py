@@ -52,10 +52,73 @@ def test_planned_launches_follow_the_driver_rule():
     assert bench.planned_launches(2, 20, 1) == (0, 0, 20)
 
 
+def test_dumped_outputs_are_the_interior_or_a_fixed_sample(monkeypatch):
+    """--dump-outputs: the result grid's interior, whole (float64; bf16 as float32) or, past the size limit, at the same
+    seeded interior points every time -- within the 64 MB the option may write."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from lorastencil_amd.ops import halo, padded_shape
+
+    assert bench.DUMP_WHOLE_BYTES <= 64 << 20 and bench.DUMP_SAMPLE_POINTS * 8 <= 64 << 20
+    shape, dims = "star2d1r", (6, 10)
+    ps = padded_shape(shape, dims)
+    g = torch.arange(ps[0] * ps[1], dtype=torch.float64).reshape(ps)
+    out = bench.output_arrays(shape, dims, g)
+    assert list(out) == ["out"] and out["out"].dtype == np.float64 and np.array_equal(out["out"], g[4:10, 4:14].numpy())
+    out = bench.output_arrays(shape, dims, g.to(torch.bfloat16))
+    assert out["out"].dtype == np.float32 and np.array_equal(out["out"], g[4:10, 4:14].to(torch.bfloat16).float().numpy())
+    monkeypatch.setattr(bench, "DUMP_WHOLE_BYTES", 0)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_POINTS", 40)
+    for shape, dims in (("star2d1r", (6, 10)), ("box3d1r", (3, 4, 5)), ("1d2r", (50,))):
+        ps = padded_shape(shape, dims)
+        g = torch.arange(int(np.prod(ps)), dtype=torch.float64).reshape(ps)
+        s1, s2 = bench.output_arrays(shape, dims, g), bench.output_arrays(shape, dims, g.clone())
+        assert list(s1) == ["out_sample"] and np.array_equal(s1["out_sample"], s2["out_sample"])
+        v = s1["out_sample"]
+        assert 0 < v.size <= 40 and v.dtype == np.float64 and np.all(np.diff(v) > 0)  # sorted, no repeats
+        interior = np.zeros(ps, bool)
+        interior[tuple(slice(k, k + d) for k, d in zip(halo(shape), dims))] = True
+        assert interior.ravel()[v.astype(np.int64)].all()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline fields only (no roofline, no CPU baseline); --dump-outputs writes what the K timed
+    steps computed, the same in two runs, and it is the oracle's result on the same seeded input."""
+    import numpy as np
+    import torch
+
+    from oracle import oracle as O
+
+    shape, dims, K, W = "star2d1r", (256, 384), 6, 1
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r, lines = _bench("--steps", str(K), "--warmup", str(W), "--size", *map(str, dims), "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line
+        assert "roofline" not in line and "cpu_baseline" not in line
+        assert line["steps"] == K and line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+        assert sorted(p.name for p in d.iterdir()) == ["out.npy"]
+        outs.append(np.load(d / "out.npy"))
+    assert outs[0].dtype == np.float64 and outs[0].shape == dims and np.array_equal(outs[0], outs[1])
+    # bench.py's input: small integers from a device generator seeded 1234 (rank 0)
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    a = torch.randint(0, 100, O.padded_shape(shape, dims), generator=gen, device="cuda").to(torch.float64).cpu().numpy()
+    exp = O.interior(shape, O.run(shape, a, K))
+    assert np.abs(outs[0] - exp).max() <= 1e-12 * np.abs(exp).max()
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_over_gloo_on_one_gpu():
     r, lines = _bench("--gpus", "2", "--steps", "4", "--warmup", "0", "--size", "256", "256", "--no-cpu-baseline",
-                      env={"LORA_DIST_BACKEND": "gloo"})
+                      "--full", env={"LORA_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -64,7 +127,7 @@ def test_bench_two_ranks_over_gloo_on_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_line_roofline_is_a_fraction():
-    r, lines = _bench("--steps", "8", "--warmup", "2", "--size", "2048", "2048", "--cpu-seconds", "1")
+    r, lines = _bench("--steps", "8", "--warmup", "2", "--size", "2048", "2048", "--cpu-seconds", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[-1])
     rf = d["roofline"]

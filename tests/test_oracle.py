@@ -1,5 +1,5 @@
-"""CPU tests of the oracle itself: pinned to libc rand(), to the golden fixtures generated from the reference's
-own test_cpu, and (when oracle/_ref is present) to that test_cpu directly."""
+"""CPU tests of the oracle itself: pinned to libc rand() and to the golden fixtures generated from the reference's
+own test_cpu (tests/golden/make_golden.py)."""
 import ctypes
 
 import numpy as np
@@ -7,7 +7,6 @@ import pytest
 from conftest import ALL_SHAPES, load_golden
 
 from oracle import oracle as o
-from oracle import ref
 
 
 def test_rng_matches_libc_rand():
@@ -43,22 +42,22 @@ def test_oracle_matches_golden_bit_exact(shape, t):
         assert np.array_equal(out, exp)
 
 
-@pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("shape,dims", [("1d1r", (96,)), ("star2d1r", (16, 32)), ("box2d3r", (8, 24)),
                                         ("star2d3r", (12, 20)), ("star3d1r", (5, 6, 18)), ("box3d1r", (4, 9, 10))])
 def test_oracle_step_equals_reference_test_cpu_random_params(shape, dims):
-    rng = np.random.default_rng(42)
-    a = rng.standard_normal(o.padded_shape(shape, dims))
-    p = rng.standard_normal(o.NTAPS[len(dims)])
-    assert np.array_equal(o.interior(shape, ref.test_cpu(a, p)), o.interior(shape, o.step(shape, a, p)))
+    # gaussian input and taps; `<shape>_out` is one sweep of the reference's test_cpu (make_golden.py --ref-pins)
+    z = load_golden("ref_random_params")
+    a, p = z[f"{shape}_input"], z[f"{shape}_params"]
+    assert a.shape == o.padded_shape(shape, dims) and p.shape == (o.NTAPS[len(dims)],)
+    assert np.array_equal(o.interior(shape, z[f"{shape}_out"]), o.interior(shape, o.step(shape, a, p)))
 
 
-@pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("shape", ALL_SHAPES)
 def test_oracle_driver_equals_reference_chain(shape):
     g = load_golden(shape)
+    chain = load_golden("ref_chain")  # test_cpu chained with the reference driver's ping-pong (make_golden.py --ref-pins)
     for t in (0, 5, 6):
-        exp = ref.run_chain(g["input"], g["params"], t)
+        exp = g["input"] if t == 0 else chain[f"{shape}_t{t}"]
         out = o.run(shape, g["input"], t)
         n = -1 if out.ndim == 1 else None
         assert np.array_equal(out.ravel()[:n], exp.ravel()[:n])
@@ -165,17 +164,21 @@ def test_boundary_options_of_the_oracle_have_the_properties_they_claim():
             assert np.array_equal(out[0, 2:-2, 4:-4], core[-1]) and np.array_equal(out[1:-1, 2:-2, :4], core[:, :, -4:])
 
 
-@pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
 def test_baseline_config0_1d1r_2pow20_100_steps_cpu_path():
     """BASELINE.json configs[0]: `lorastencil_1d 1d1r 1048576 100`, the CPU-runnable plumbing case: the oracle's
     driver against 100 chained sweeps of the reference's own test_cpu, bit for bit (values leave the exact-integer
-    range after ~13 steps, so this also pins the rounding of every later step)."""
+    range after ~13 steps, so this also pins the rounding of every later step).  The fixture holds the SHA-256 of that
+    result's bytes and every 4096th value (make_golden.py --ref-pins)."""
+    import hashlib
+
     n, t = 1 << 20, 100
     a = o.reference_input("1d1r", (n,))
-    p = o.default_params("1d1r")
-    exp = ref.run_chain(a, p, t)
     got = o.run("1d1r", a, t, threads=o.max_threads())
-    assert np.isfinite(exp).all() and np.array_equal(got[:-1], exp[:-1])
+    body = np.ascontiguousarray(got[:-1], dtype="<f8")
+    pin = load_golden("ref_1d1r_config0")
+    assert np.isfinite(got).all()
+    assert np.array_equal(body[::4096], pin["sample"])
+    assert hashlib.sha256(body.tobytes()).hexdigest() == str(pin["sha256"])
 
 
 def test_bf16_matrix_pipe_contract_is_the_correctly_rounded_sum():

@@ -4,5 +4,5 @@
 args=${1:---shape box3d1r --dtype bf16}; vals=${2:-0 2}; n=${3:-3}
 for i in $(seq 1 $n); do
 for o in $vals; do
-timeout -k 10 300 python bench.py --steps 50 --no-cpu-baseline $args --option spans3=$o 2>/dev/null | grep "^{" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$args', 'spans3=$o', d['value'], d['roofline']['launch_us'])"
+timeout -k 10 300 python bench.py --steps 50 --full --no-cpu-baseline $args --option spans3=$o 2>/dev/null | grep "^{" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$args', 'spans3=$o', d['value'], d['roofline']['launch_us'])"
 done; done
