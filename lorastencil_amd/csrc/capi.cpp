@@ -16,6 +16,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "engine.h"
 #include "spans.h"
@@ -42,8 +43,6 @@ void set_last_run_info(const lora_run_info &info) { g_last_info = info; }
             return LORA_EHIP;                   \
         }                                       \
     } while (0)
-
-static int outer_extent(const Plan &p) { return p.dims[0]; }
 
 int region_granularity(const Plan &p) {
     switch (p.ndim) {
@@ -421,7 +420,7 @@ void plan_refresh(Plan &p) {
     }
 }
 
-int check_buffers(const void *a, const void *b) {
+static int check_buffers(const void *a, const void *b) {
     if (!a || !b) return LORA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(a) & 15) || (reinterpret_cast<uintptr_t>(b) & 15)) {
         g_last_error = "device buffers must be 16-byte aligned";
@@ -430,47 +429,67 @@ int check_buffers(const void *a, const void *b) {
     return LORA_OK;
 }
 
-static int step_region(Plan &p, const void *d_in, void *d_out, int begin, int end, hipStream_t s) {
-    if (int rc = check_buffers(d_in, d_out)) return rc;
-    if (d_in == d_out) return LORA_EINVAL;
-    const int ext = outer_extent(p);
-    if (begin < 0 || end > ext || begin > end) return LORA_EINVAL;
-    const int g = region_granularity(p);
-    if (begin % g != 0) return LORA_EINVAL;
-    const double *in = static_cast<const double *>(d_in);
-    double *out = static_cast<double *>(d_out);
-    hipError_t e;
-    if (p.dtype == LORA_BF16)
-        e = launch_3d_bf16(p, d_in, d_out, begin, end, s);
-    else if (p.generic)
-        e = (p.ndim == 2) ? launch_2d_generic(p, in, out, begin, end, s) : launch_3d_generic(p, in, out, begin, end, s);
-    else if (p.ndim == 1)
-        e = launch_1d(p, in, out, begin, end, s);
-    else if (p.ndim == 2)
-        e = (p.variant == LORA_VARIANT_MFMA) ? launch_2d_mfma(p, in, out, begin, end, s)
-                                             : launch_2d_direct(p, in, out, begin, end, s);
-    else
-        e = launch_3d(p, in, out, begin, end, s);
-    if (e != hipSuccess) {
-        set_last_error("kernel launch", e);
-        return LORA_EHIP;
-    }
-    return LORA_OK;
+// Which launches a plan has.  One application: every plan.  lora_plan_step2's two: 2D direct-variant plans whose fused
+// kernels apply (odd innermost extents: the row-streaming kernel) and 3D plans with a fused kernel, whatever their depth.
+// Otherwise the plan's own kernel family at any depth up to `depth` that it has: 1D the powers of two, 2D the even ones
+// (row-streaming kernel 4 / 2, workgroup-row kernel 6 / 4 / 2), 3D the plan's own and 2.
+static bool has_apps(const Plan &p, int napps, int depth, bool step2) {
+    if (step2)
+        return (p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT && (!p.generic || (p.stream2 && p.boundary == LORA_BC_REFERENCE))) ||
+               (p.ndim == 3 && (!p.generic || p.lanes3_active));
+    if (napps == 1) return true;
+    if (napps < 2 || napps > depth) return false;
+    if (p.ndim == 1) return (napps & (napps - 1)) == 0;
+    if (p.ndim == 2) return napps % 2 == 0;
+    return napps == 2 || napps == depth;
 }
 
-// Three applications (3D fp64, plane-streaming kernel) starting at a global step of the given parity; `d_halo` is a
-// buffer that carries the caller's halo (what even global levels see outside the interior).
-static int step3_natural(Plan &p, const void *d_in, void *d_out, const void *d_halo, int parity, int begin, int end,
-                         void *stream) {
-    if (!(p.ndim == 3 && p.dtype != LORA_BF16 && !p.generic && p.stream3_active && p.steps_per_launch == 3))
-        return LORA_EUNSUPPORTED;
+bool has_depth(const Plan &p, int napps) { return has_apps(p, napps, p.steps_per_launch, false); }
+
+int launch_apps(const Plan &p, const Apps &a, const void *d_in, void *d_out, hipStream_t s) {
+    const int n = a.napps, b = a.begin, e = a.end;
+    if (!has_apps(p, n, a.depth ? a.depth : p.steps_per_launch, a.step2)) return LORA_EUNSUPPORTED;
     if (int rc = check_buffers(d_in, d_out)) return rc;
-    if (d_in == d_out || !d_halo || begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
-    const hipError_t e = launch_3d_stream(p, 3, static_cast<const double *>(d_in), static_cast<double *>(d_out),
-                                          static_cast<const double *>(d_halo), parity, begin, end,
-                                          static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-        set_last_error("fused 3-step kernel launch", e);
+    const int g = region_granularity(p);
+    auto bad = [&](int begin, int end) { return begin < 0 || end > p.dims[0] || begin > end || begin % g != 0; };
+    if (d_in == d_out || bad(b, e) || bad(a.begin2, a.end2)) return LORA_EINVAL;
+    const double *in = static_cast<const double *>(d_in);
+    double *out = static_cast<double *>(d_out);
+    const bool bf16 = p.dtype == LORA_BF16;
+    hipError_t err;
+    if (n == 1 && bf16)
+        err = launch_3d_bf16(p, d_in, d_out, b, e, s);
+    else if (n == 1 && p.generic)
+        err = p.ndim == 2 ? launch_2d_generic(p, in, out, b, e, s) : launch_3d_generic(p, in, out, b, e, s);
+    else if (n == 1)
+        err = p.ndim == 1   ? launch_1d(p, in, out, b, e, s)
+              : p.ndim == 3 ? launch_3d(p, in, out, b, e, s)
+              : p.variant == LORA_VARIANT_MFMA ? launch_2d_mfma(p, in, out, b, e, s)
+                                               : launch_2d_direct(p, in, out, b, e, s);
+    else if (p.ndim == 1)
+        err = launch_1d_fused(p, n, in, out, b, e, s);
+    else if (p.ndim == 2)
+        err = (p.wg_active && !a.step2) ? launch_2d_wg(p, n, in, out, b, e, s)
+              : p.stream2               ? launch_2d_stream(p, n, in, out, b, e, s)
+                                        : launch_2d_fused2(p, in, out, b, e, s);
+    else if (n == 3)  // an even global step by default: level 1 has the zero halo, level 2 the source's
+        err = launch_3d_stream(p, 3, in, out, static_cast<const double *>(a.halo ? a.halo : d_in), a.parity, b, e, s);
+    else if (p.lanes3_active && n == 2 && a.begin2 == a.end2 && !bf16 && !p.generic && p.stream3 != 0 && e - b >= 128)
+        // Two sweeps move the same bytes as four, and at that the plane-streaming kernel is the faster of the two (star3d1r
+        // 512^3: 475 against 551 us; box3d1r 768^3: 1651 against 1893; tools/tail_time.py) -- same taps in the same order,
+        // same bits.  Deep regions of even-extent fp64 grids take it; the rest (thin regions, odd extents, bf16, two ranges)
+        // stays with the register-resident kernels.
+        err = launch_3d_stream(p, 2, in, out, in, 0, b, e, s);
+    else if (p.lanes3_active)
+        err = bf16 ? launch_3d_bf16_lanes(p, n, d_in, d_out, b, e, s, a.begin2, a.end2)
+                   : launch_3d_lanes(p, n, in, out, b, e, s, a.begin2, a.end2);
+    else if (bf16)
+        err = p.variant == LORA_VARIANT_MFMA ? launch_3d_bf16_mfma2(p, d_in, d_out, b, e, s)
+                                             : launch_3d_bf16_fused2(p, d_in, d_out, b, e, s);
+    else
+        err = p.stream3_active ? launch_3d_stream(p, 2, in, out, in, 0, b, e, s) : launch_3d_fused2(p, in, out, b, e, s);
+    if (err != hipSuccess) {
+        set_last_error(n == 1 ? "kernel launch" : "fused kernel launch", err);
         return LORA_EHIP;
     }
     return LORA_OK;
@@ -898,75 +917,22 @@ const char *lora_plan_kernel_signature(const lora_plan *plan) {
 
 int lora_plan_region_granularity(const lora_plan *plan) { return plan ? lora::region_granularity(plan->p) : 0; }
 
+// The public launch entries: each one launch of the dispatcher (lora::launch_apps) at its depth.
 int lora_plan_step_region(lora_plan *plan, const void *d_in, void *d_out, int begin, int end, void *stream) {
     if (!plan) return LORA_EINVAL;
-    return lora::step_region(plan->p, d_in, d_out, begin, end, static_cast<hipStream_t>(stream));
+    return lora::launch_apps(plan->p, {1, begin, end}, d_in, d_out, static_cast<hipStream_t>(stream));
 }
 
 int lora_plan_step(lora_plan *plan, const void *d_in, void *d_out, void *stream) {
     if (!plan) return LORA_EINVAL;
-    return lora::step_region(plan->p, d_in, d_out, 0, plan->p.dims[0], static_cast<hipStream_t>(stream));
+    return lora_plan_step_region(plan, d_in, d_out, 0, plan->p.dims[0], stream);
 }
 
 int lora_plan_step2_region(lora_plan *plan, const void *d_in, void *d_out, int begin, int end, void *stream) {
     if (!plan) return LORA_EINVAL;
-    Plan &p = plan->p;
-    const bool ok2 = p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT &&
-                     (!p.generic || (p.stream2 && p.boundary == LORA_BC_REFERENCE));
-    const bool ok3 = p.ndim == 3 && !p.generic;
-    if (p.ndim == 3 && p.lanes3_active) {  // the two-application tail of a four-application plan (also: odd innermost extents)
-        if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-        if (d_in == d_out || begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
-        // Two sweeps move the same bytes as four, and at that the plane-streaming kernel is the faster of the two (star3d1r
-        // 512^3: 475 against 551 us; box3d1r 768^3: 1651 against 1893; tools/tail_time.py) -- same taps in the same order,
-        // same bits.  Deep regions of even-extent fp64 grids take it; the rest (thin regions, odd extents, bf16) stays here.
-        if (p.dtype != LORA_BF16 && !p.generic && p.stream3 != 0 && end - begin >= 128) {
-            Plan q = p;
-            q.lanes3_active = 0;
-            q.stream3_active = 1;
-            q.steps_per_launch = 2;
-            const hipError_t e = lora::launch_3d_stream(q, 2, static_cast<const double *>(d_in), static_cast<double *>(d_out),
-                                                        static_cast<const double *>(d_in), 0, begin, end, static_cast<hipStream_t>(stream));
-            if (e != hipSuccess) {
-                lora::set_last_error("fused plane-streaming kernel launch (two-application tail)", e);
-                return LORA_EHIP;
-            }
-            return LORA_OK;
-        }
-        const hipError_t e = p.dtype == LORA_BF16
-                                 ? lora::launch_3d_bf16_lanes(p, 2, d_in, d_out, begin, end, static_cast<hipStream_t>(stream))
-                                 : lora::launch_3d_lanes(p, 2, static_cast<const double *>(d_in), static_cast<double *>(d_out), begin,
-                                                         end, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) {
-            lora::set_last_error("fused register-resident 3D kernel launch", e);
-            return LORA_EHIP;
-        }
-        return LORA_OK;
-    }
-    if (!ok2 && !ok3) return LORA_EUNSUPPORTED;
-    if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-    if (d_in == d_out || begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
-    const hipError_t e = ok2 ? (p.stream2 ? lora::launch_2d_stream(p, 2, static_cast<const double *>(d_in),
-                                                                   static_cast<double *>(d_out), begin, end,
-                                                                   static_cast<hipStream_t>(stream))
-                                          : lora::launch_2d_fused2(p, static_cast<const double *>(d_in),
-                                                                   static_cast<double *>(d_out), begin, end,
-                                                                   static_cast<hipStream_t>(stream)))
-                         : p.dtype == LORA_BF16
-                             ? (p.variant == LORA_VARIANT_MFMA
-                                    ? lora::launch_3d_bf16_mfma2(p, d_in, d_out, begin, end, static_cast<hipStream_t>(stream))
-                                    : lora::launch_3d_bf16_fused2(p, d_in, d_out, begin, end, static_cast<hipStream_t>(stream)))
-                         : p.stream3_active
-                             ? lora::launch_3d_stream(p, 2, static_cast<const double *>(d_in), static_cast<double *>(d_out),
-                                                      static_cast<const double *>(d_in), 0, begin, end,
-                                                      static_cast<hipStream_t>(stream))
-                             : lora::launch_3d_fused2(p, static_cast<const double *>(d_in), static_cast<double *>(d_out),
-                                                      begin, end, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-        lora::set_last_error("fused kernel launch", e);
-        return LORA_EHIP;
-    }
-    return LORA_OK;
+    lora::Apps a{2, begin, end};
+    a.step2 = true;
+    return lora::launch_apps(plan->p, a, d_in, d_out, static_cast<hipStream_t>(stream));
 }
 
 int lora_copy_block_f64(void *d_dst, long dst_ld, const void *d_src, long src_ld, long rows, long cols, void *stream) {
@@ -1007,55 +973,7 @@ int lora_plan_step2(lora_plan *plan, const void *d_in, void *d_out, void *stream
 
 int lora_plan_stepk_region(lora_plan *plan, const void *d_in, void *d_out, int begin, int end, void *stream) {
     if (!plan) return LORA_EINVAL;
-    Plan &p = plan->p;
-    if (p.steps_per_launch <= 1) return lora_plan_step_region(plan, d_in, d_out, begin, end, stream);
-    if (p.ndim == 2 && (p.steps_per_launch == 6 || (p.wg_active && (p.steps_per_launch == 4 || p.steps_per_launch == 2)))) {
-        if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-        if (d_in == d_out || begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
-        const hipError_t e = lora::launch_2d_wg(p, p.steps_per_launch, static_cast<const double *>(d_in),
-                                                static_cast<double *>(d_out), begin, end, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) {
-            lora::set_last_error("fused workgroup-row kernel launch", e);
-            return LORA_EHIP;
-        }
-        return LORA_OK;
-    }
-    if (p.ndim == 2 && p.steps_per_launch == 4) {
-        if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-        if (d_in == d_out || begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
-        const hipError_t e = lora::launch_2d_stream(p, 4, static_cast<const double *>(d_in), static_cast<double *>(d_out),
-                                                    begin, end, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) {
-            lora::set_last_error("fused 4-step kernel launch", e);
-            return LORA_EHIP;
-        }
-        return LORA_OK;
-    }
-    if (p.ndim == 3 && p.lanes3_active && (p.steps_per_launch == 4 || p.steps_per_launch == 2)) {
-        if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-        if (d_in == d_out || begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
-        const hipError_t e = p.dtype == LORA_BF16
-                                 ? lora::launch_3d_bf16_lanes(p, p.steps_per_launch, d_in, d_out, begin, end, static_cast<hipStream_t>(stream))
-                                 : lora::launch_3d_lanes(p, p.steps_per_launch, static_cast<const double *>(d_in),
-                                                         static_cast<double *>(d_out), begin, end, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) {
-            lora::set_last_error("fused register-resident 3D kernel launch", e);
-            return LORA_EHIP;
-        }
-        return LORA_OK;
-    }
-    if (p.ndim == 3 && p.steps_per_launch == 3)  // an even global step: level 1 has the zero halo, level 2 the source's
-        return lora::step3_natural(p, d_in, d_out, d_in, 0, begin, end, stream);
-    if (p.ndim != 1) return lora_plan_step2_region(plan, d_in, d_out, begin, end, stream);
-    if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-    if (d_in == d_out || begin < 0 || end > p.dims[0] || begin > end || (begin & 1)) return LORA_EINVAL;
-    const hipError_t e = lora::launch_1d_fused(p, static_cast<const double *>(d_in), static_cast<double *>(d_out), begin,
-                                               end, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-        lora::set_last_error("fused 1D kernel launch", e);
-        return LORA_EHIP;
-    }
-    return LORA_OK;
+    return lora_plan_stepn_region(plan, plan->p.steps_per_launch, d_in, d_out, begin, end, stream);
 }
 
 int lora_plan_stepk(lora_plan *plan, const void *d_in, void *d_out, void *stream) {
@@ -1063,36 +981,10 @@ int lora_plan_stepk(lora_plan *plan, const void *d_in, void *d_out, void *stream
     return lora_plan_stepk_region(plan, d_in, d_out, 0, plan->p.dims[0], stream);
 }
 
-// `napps` applications in one launch where the plan's kernel family has that depth: 1, the plan's own depth, or one of
-// the shallower depths its runs use for their tails (2D workgroup-row kernel: 4 and 2 under a six-application plan; 1D:
-// the powers of two below the plan's depth; otherwise 2).  What the slab / block drivers issue for the tail of a run.
 int lora_plan_stepn_region(lora_plan *plan, int napps, const void *d_in, void *d_out, int begin, int end, void *stream) {
     if (!plan || napps < 1) return LORA_EINVAL;
-    Plan &p = plan->p;
-    if (napps == 1) return lora_plan_step_region(plan, d_in, d_out, begin, end, stream);
-    if (napps == p.steps_per_launch) return lora_plan_stepk_region(plan, d_in, d_out, begin, end, stream);
-    if (napps > p.steps_per_launch) return LORA_EUNSUPPORTED;
-    const bool wg_tail = p.ndim == 2 && p.wg_active && (napps == 4 || napps == 2);
-    const bool d1_tail = p.ndim == 1 && (napps & (napps - 1)) == 0;
-    if (wg_tail || d1_tail) {
-        const int depth = p.steps_per_launch;
-        p.steps_per_launch = napps;
-        const int rc = lora_plan_stepk_region(plan, d_in, d_out, begin, end, stream);
-        p.steps_per_launch = depth;
-        return rc;
-    }
-    if (napps == 2) return lora_plan_step2_region(plan, d_in, d_out, begin, end, stream);
-    return LORA_EUNSUPPORTED;
+    return lora::launch_apps(plan->p, {napps, begin, end}, d_in, d_out, static_cast<hipStream_t>(stream));
 }
-
-// The launches of one run, in order, on `stream` (also what gets captured into a hipGraph).
-// How a run of `times` steps is cut into launches: nk launches of the plan's K applications, n2 shallower fused launches
-// (1D and 2D; their depths in `tail`), the rest single sweeps.  The fused launches must leave the data in buffer 0.
-struct FusedSchedule {
-    int nk = 0, n2 = 0;
-    bool scratch = false;  // odd number of fused launches: the last two hops go through the plan's scratch grid
-    int tail[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // depths of the n2 launches after the nk full-depth ones
-};
 
 static void drop_graph(lora_plan *plan);
 
@@ -1123,107 +1015,95 @@ static bool ensure_scratch(lora_plan *plan) {
     return true;
 }
 
-static FusedSchedule fused_schedule(lora_plan *plan, int times, bool can_fuse, bool allocate = true) {
-    const Plan &p = plan->p;
-    FusedSchedule fs;
-    const int K = p.steps_per_launch;
-    if (!can_fuse || K < 2) return fs;
-    fs.nk = times / K;
-    fs.n2 = 0;
-    if (p.ndim == 2 || (p.ndim == 3 && K == 4)) {
-        // 2D (and 3D with four applications per launch): what the full-depth launches leave is covered by one launch of four and / or one of two applications (the
-        // row-streaming kernel), so that at most one single sweep remains: 100 sweeps at depth 6 = 16 x 6 + 4
-        int r = times - K * fs.nk;
-        if (K == 6 && r >= 2 && r < 4 && fs.nk >= 1) {
-            // 6 + 2 as 4 + 4: a two-application launch moves the whole grid for two sweeps (star2d1r 16384^2, us per
-            // launch of the workgroup-row kernel at 6 / 4 / 2 applications: 1194 / 944 / 885)
-            fs.nk -= 1;
-            fs.tail[fs.n2++] = 4;
-            fs.tail[fs.n2++] = 4;
-            r -= 2;
-        }
-        for (int d = 4; d >= 2; d -= 2)
-            if (d < K && r >= d) {
-                fs.tail[fs.n2++] = d;
-                r -= d;
-            }
-        const int n = fs.nk + fs.n2;
-        if (n % 2 == 0) return fs;
-        if (n >= 3 && p.use_scratch != 0 && (allocate ? ensure_scratch(plan) : scratch_ready(plan))) {
-            fs.scratch = true;
-            return fs;
-        }
-        // no scratch grid: an even number of launches -- one full-depth launch becomes two shallower ones (6 = 4 + 2,
-        // 4 = 2 + 2), or the last launch becomes single sweeps
-        if (fs.nk >= 1 && K >= 4) {
-            fs.nk -= 1;
-            for (int q = fs.n2 - 1; q >= 0; --q) fs.tail[q + 2] = fs.tail[q];
-            fs.tail[0] = K == 6 ? 4 : 2;
-            fs.tail[1] = 2;
-            fs.n2 += 2;
-        } else if (fs.n2 > 0 && fs.tail[fs.n2 - 1] >= 4) {
-            fs.tail[fs.n2 - 1] = 2;  // a four-application launch as two of two
-            fs.tail[fs.n2++] = 2;
-        } else if (fs.n2 > 0) {
-            fs.n2 -= 1;
-        } else {
-            fs.nk -= 1;
-        }
-        return fs;
-    }
-    if (p.ndim == 1) {
-        // 1D: what the full-depth launches leave is covered by shallower launches (K / 2, K / 4, ... 2 applications), so
-        // that at most one single sweep remains: 100 sweeps at depth 32 = 32 + 32 + 32 + 4
-        int r = times - K * fs.nk;
-        for (int d = K / 2; d >= 2; d /= 2)
-            if (r >= d) {
-                fs.tail[fs.n2++] = d;
-                r -= d;
-            }
-        const int n1 = fs.nk + fs.n2;
-        if (n1 % 2 == 0) return fs;
-        if (n1 >= 3 && p.use_scratch != 0 && (allocate ? ensure_scratch(plan) : scratch_ready(plan))) {
-            fs.scratch = true;
-            return fs;
-        }
-        // no scratch grid: an even number of launches -- the last launch becomes two of half its depth, or two single sweeps
-        if (fs.n2 > 0) {
-            const int d = fs.tail[fs.n2 - 1];
-            if (d >= 4) {
-                fs.tail[fs.n2 - 1] = d / 2;
-                fs.tail[fs.n2++] = d / 2;
-            } else {
-                fs.n2 -= 1;
-            }
-        } else if (K >= 4) {
-            fs.nk -= 1;
-            fs.tail[fs.n2++] = K / 2;
-            fs.tail[fs.n2++] = K / 2;
-        } else {
-            fs.nk -= 1;
-        }
-        return fs;
-    }
-    const int n = fs.nk + fs.n2;
-    if (n % 2 == 0) return fs;
-    if (n >= 3 && p.use_scratch != 0 && (allocate ? ensure_scratch(plan) : scratch_ready(plan))) {
-        fs.scratch = true;
-        return fs;
-    }
-    fs.nk -= 1;  // no scratch grid: an even number of launches instead
-    return fs;
+// 1D runs with the automatic launch depth fuse more applications per launch the longer the run is: 8 is the plan's
+// own depth (what lora_plan_stepk and the slab drivers use), 16 / 32 pay from 32 / 64 sweeps on (2^20 points: 840 ->
+// 999 -> 1066 GStencils/s per launch, 2^28: 1600 -> 1915 -> 1987; tools/k1d.sh) while short runs keep enough fused
+// launches.  Every other plan runs at its own depth.
+static int run_depth(const Plan &p, int times) {
+    if (p.ndim == 1 && p.steps_per_launch_req == 0 && p.steps_per_launch == 8 && p.boundary != LORA_BC_PERIODIC)
+        return times >= 64 ? 32 : (times >= 32 ? 16 : 8);
+    return p.steps_per_launch;
 }
 
-// Does lora_plan_run cut this plan's runs into fused launches at all, and is it the three-application 3D schedule (which
-// runs on the reference's own buffer state: no scratch grid)?  One place, used by run_launches and by the pre-capture
-// allocation in lora_plan_run.
-static bool run_can_fuse(const Plan &p) {
-    const int K = p.steps_per_launch;
-    return p.boundary != LORA_BC_PERIODIC && K >= 2 &&
-           (!p.generic || (p.ndim == 2 && p.stream2 && p.boundary == LORA_BC_REFERENCE) || (p.ndim == 3 && p.lanes3_active)) &&
-           ((p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT) || p.ndim == 3 || p.ndim == 1);
+// How lora_plan_run cuts a run of `times` sweeps at depth K into launches: the depths of its fused launches in order (the
+// full-depth ones first, then the shallower ones), the rest of the run single sweeps.
+struct Schedule {
+    std::vector<int> depths;
+    bool natural = false;  // three-application 3D form: launch k reads buffer k mod 2 (see run_launches)
+    bool scratch = false;  // an odd number of launches: the last two hops go through the plan's scratch grid
+};
+
+static Schedule run_schedule(const Plan &p, int times, int K, bool scratch_ok) {
+    Schedule sc;
+    std::vector<int> &d = sc.depths;
+    const bool can_fuse = p.boundary != LORA_BC_PERIODIC && K >= 2 &&
+                          (!p.generic || (p.ndim == 2 && p.stream2 && p.boundary == LORA_BC_REFERENCE) || (p.ndim == 3 && p.lanes3_active)) &&
+                          ((p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT) || p.ndim == 3 || p.ndim == 1);
+    if (!can_fuse) return sc;
+    if (p.ndim == 3 && K == 3) {
+        // What three-application launches leave (1 or 2 sweeps) would be single sweeps at a third of the rate.  When the
+        // launches before them end at an even step in buffer 0, two of them are traded for TWO-application launches of
+        // the same kernel instead: 3 a + 1 = 3 (a - 1) + 2 + 2, 3 a + 2 = 3 (a - 2) + 4 x 2 (50 sweeps = 14 x 3 + 4 x 2).
+        sc.natural = true;
+        int nk = times / 3, n2 = 0;
+        if (times % 3 == 1 && nk >= 1 && (nk - 1) % 2 == 0) {
+            nk -= 1;
+            n2 = 2;
+        } else if (times % 3 == 2 && nk >= 2 && (nk - 2) % 2 == 0) {
+            nk -= 2;
+            n2 = 4;
+        }
+        d.assign(nk, 3);
+        d.insert(d.end(), n2, 2);
+        return sc;
+    }
+    // What the full-depth launches leave is covered by shallower ones, so that at most one single sweep remains: 1D K / 2,
+    // K / 4, ... 2 applications (100 sweeps at depth 32 = 32 + 32 + 32 + 4); 2D and 3D four and / or two (100 sweeps at
+    // depth 6 = 16 x 6 + 4)
+    const int nk = times / K;
+    int r = times % K;
+    d.assign(nk, K);
+    if (K == 6 && r >= 2 && r < 4 && nk >= 1) {
+        // 6 + 2 as 4 + 4: a two-application launch moves the whole grid for two sweeps (star2d1r 16384^2, us per
+        // launch of the workgroup-row kernel at 6 / 4 / 2 applications: 1194 / 944 / 885)
+        d.back() = 4;
+        d.push_back(4);
+        r -= 2;
+    }
+    for (int t = p.ndim == 1 ? K / 2 : 4; t >= 2; t = p.ndim == 1 ? t / 2 : t - 2)
+        if (t < K && r >= t) {
+            d.push_back(t);
+            r -= t;
+        }
+    const int n = (int) d.size();
+    if (n % 2 == 0) return sc;
+    if (n >= 3 && scratch_ok && p.use_scratch != 0) {
+        sc.scratch = true;
+        return sc;
+    }
+    // no scratch grid: an even number of launches -- 2D / 3D: one full-depth launch becomes two shallower ones (6 = 4 + 2,
+    // 4 = 2 + 2); else the last launch becomes two of half its depth, or (two applications) single sweeps
+    int full = 0;  // the full-depth launches
+    while (full < n && d[full] == K) ++full;
+    if (p.ndim != 1 && full >= 1 && K >= 4) {
+        d[full - 1] = K == 6 ? 4 : 2;
+        d.insert(d.begin() + full, 2);
+    } else if (d.back() >= 4) {
+        d.back() /= 2;
+        d.push_back(d.back());
+    } else {
+        d.pop_back();
+    }
+    return sc;
 }
-static bool run_is_natural3(const Plan &p) { return run_can_fuse(p) && p.ndim == 3 && p.steps_per_launch == 3; }
+
+// The run's schedule, its scratch grid allocated now if it asks for one (`allocate`), else taken only if it is there.
+static Schedule plan_schedule(lora_plan *plan, int times, bool allocate) {
+    const int K = run_depth(plan->p, times);
+    Schedule sc = run_schedule(plan->p, times, K, true);
+    if (sc.scratch && !(allocate ? ensure_scratch(plan) : scratch_ready(plan))) sc = run_schedule(plan->p, times, K, false);
+    return sc;
+}
 
 struct RunMarks {  // lora_plan_run_profiled: events around the fused and the single-sweep segment
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | K-launches | 2-launches | singles
@@ -1324,27 +1204,12 @@ int lora_debug_span_cover(int tiles_x, int tiles_y, int depth, int S, int slots,
 int lora_plan_stepn_region2(lora_plan *plan, int napps, const void *d_in, void *d_out, int begin0, int end0, int begin1, int end1,
                             void *stream) {
     if (!plan || napps < 1) return LORA_EINVAL;
-    Plan &p = plan->p;
-    if (end0 <= begin0) return end1 <= begin1 ? LORA_OK : lora_plan_stepn_region(plan, napps, d_in, d_out, begin1, end1, stream);
-    if (end1 <= begin1) return lora_plan_stepn_region(plan, napps, d_in, d_out, begin0, end0, stream);
-    const bool lanes = p.ndim == 3 && p.lanes3_active && (napps == 4 || napps == 2) && napps <= p.steps_per_launch;
     const bool apart = end0 <= begin1 || end1 <= begin0;
-    if (lanes && apart) {
-        if (int rc = lora::check_buffers(d_in, d_out)) return rc;
-        if (d_in == d_out || begin0 < 0 || end0 > p.dims[0] || begin1 < 0 || end1 > p.dims[0]) return LORA_EINVAL;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const hipError_t e = p.dtype == LORA_BF16
-                                 ? lora::launch_3d_bf16_lanes(p, napps, d_in, d_out, begin0, end0, s, begin1, end1)
-                                 : lora::launch_3d_lanes(p, napps, static_cast<const double *>(d_in), static_cast<double *>(d_out), begin0,
-                                                         end0, s, begin1, end1);
-        if (e != hipSuccess) {
-            lora::set_last_error("fused register-resident 3D kernel launch (two ranges)", e);
-            return LORA_EHIP;
-        }
-        return LORA_OK;
-    }
-    if (int rc = lora_plan_stepn_region(plan, napps, d_in, d_out, begin0, end0, stream)) return rc;
-    return lora_plan_stepn_region(plan, napps, d_in, d_out, begin1, end1, stream);
+    if (plan->p.lanes3_active && (napps == 4 || napps == 2) && end0 > begin0 && end1 > begin1 && apart)
+        return lora::launch_apps(plan->p, {napps, begin0, end0, begin1, end1}, d_in, d_out, static_cast<hipStream_t>(stream));
+    if (end0 > begin0)
+        if (int rc = lora_plan_stepn_region(plan, napps, d_in, d_out, begin0, end0, stream)) return rc;
+    return end1 > begin1 ? lora_plan_stepn_region(plan, napps, d_in, d_out, begin1, end1, stream) : LORA_OK;
 }
 
 // ---- the periodic option in fused launches: the torus by ghost zones ---------------------------------------------
@@ -1446,21 +1311,9 @@ static int run_torus(lora_plan *plan, void *d_buf0, void *d_buf1, int times, hip
     if (int rc = hip(lora::launch_ring_wrap(p.dtype, nd, p.dims, ring, E[0], s), "torus: wrap")) return rc;
     int cur = 0, left = times;
     while (left > 0) {
-        int d = 1;
-        if (left >= K)
-            d = K;
-        else if (nd == 1)
-            while (2 * d <= left && 2 * d <= K) d *= 2;
-        else if (nd == 2 && K == 6 && left >= 4)
-            d = 4;
-        else if (left >= 2)
-            d = 2;
-        int rc = lora_plan_stepn_region(tp, d, E[cur], E[1 - cur], 0, tp->p.dims[0], s);
-        while (rc == LORA_EUNSUPPORTED && d > 1) {  // (a depth this plan's kernels do not have: the next one down)
-            d = d > 2 ? 2 : 1;
-            rc = lora_plan_stepn_region(tp, d, E[cur], E[1 - cur], 0, tp->p.dims[0], s);
-        }
-        if (rc != LORA_OK) return rc;
+        int d = std::min(left, K);
+        while (!lora::has_depth(tp->p, d)) --d;  // the deepest launch the extended plan's kernels have
+        if (int rc = lora::launch_apps(tp->p, {d, 0, tp->p.dims[0]}, E[cur], E[1 - cur], s)) return rc;
         if (int rc2 = hip(lora::launch_ring_wrap(p.dtype, nd, p.dims, ring, E[1 - cur], s), "torus: wrap")) return rc2;
         if (marks) {
             if (d == K)
@@ -1485,7 +1338,7 @@ static int run_torus(lora_plan *plan, void *d_buf0, void *d_buf1, int times, hip
 }
 
 static int run_launches(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *stream, RunMarks *marks = nullptr) {
-    Plan &p = plan->p;
+    const Plan &p = plan->p;
     void *buf[2] = {d_buf0, d_buf1};
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto mark = [&](int k) {
@@ -1535,102 +1388,60 @@ static int run_launches(lora_plan *plan, void *d_buf0, void *d_buf1, int times, 
         // fixed halo: both buffers carry the caller's halo for the whole run
         if (int rc = halo(buf[1], buf[0], lora::HALO_COPY, "halo copy")) return rc;
     }
-    int done = 0;
-    const int K = p.steps_per_launch;  // applications per fused launch: 2 (2D, 3D) or 2 / 4 / 8 (1D)
-    const bool can_fuse = run_can_fuse(p);
-    FusedSchedule fs;
-    const bool natural3 = run_is_natural3(p);
-    if (natural3) {
-        // Three applications per launch (3D fp64): launch k covers global steps 3 k + 1 .. 3 k + 3, reading buffer
-        // k mod 2 and writing the other one -- exactly where the step-by-step driver has these levels, so the launches
-        // run on the reference's own buffer state (buffer 0: the caller's halo, buffer 1: zeros; both the caller's
-        // under the Dirichlet option): no halo copies, no parity constraint on the number of launches, no scratch grid.
-        // The kernel is told the parity of its first step (which of its inner levels sees which halo).
-        // What three-application launches leave (1 or 2 sweeps) would be single sweeps at a third of the rate.  When the
-        // launches before them end at an even step in buffer 0, two of them are traded for TWO-application launches of
-        // the same kernel instead: 3 a + 1 = 3 (a - 1) + 2 + 2, 3 a + 2 = 3 (a - 2) + 4 x 2 (50 sweeps = 14 x 3 + 4 x 2).
-        // Those run like every other two-application launch: both buffers carry the caller's halo meanwhile.
-        int nk = times / 3, n2 = 0;
-        const int r = times - 3 * nk;
-        if (r == 1 && nk >= 1 && (nk - 1) % 2 == 0) {
-            nk -= 1;
-            n2 = 2;
-        } else if (r == 2 && nk >= 2 && (nk - 2) % 2 == 0) {
-            nk -= 2;
-            n2 = 4;
-        }
-        if (nk + n2 > 0) {
-            if (int rc = lora::check_buffers(d_buf0, d_buf1)) return rc;
-            if (!dirichlet)
-                if (int rc = halo(buf[1], nullptr, lora::HALO_ZERO, "halo reset")) return rc;
-            for (int k = 0; k < nk; ++k)
-                if (int rc = lora::step3_natural(p, buf[k % 2], buf[(k + 1) % 2], buf[0], k & 1, 0, p.dims[0], stream))
-                    return rc;
-            mark(1);
-            if (n2 > 0) {
-                if (!dirichlet)
-                    if (int rc = halo(buf[1], buf[0], lora::HALO_COPY, "halo copy")) return rc;
-                for (int k = 0; k < n2; ++k)
-                    if (int rc = lora_plan_step2(plan, buf[k % 2], buf[(k + 1) % 2], stream)) return rc;
-                if (!dirichlet)
-                    if (int rc = halo(buf[1], nullptr, lora::HALO_ZERO, "halo reset")) return rc;
-            }
-            done = 3 * nk + 2 * n2;
-            if (marks) marks->fused_launches = nk;
-            if (marks) marks->two_launches = n2;
-        } else {
-            mark(1);
-        }
-    } else {
-        fs = fused_schedule(plan, times, can_fuse, /*allocate=*/!plan->capturing);
+    // Temporal fusion.  A fused launch reads a buffer whose halo is the level-0 halo and writes another one, so while
+    // fused launches run every physical buffer carries buffer 0's halo; the data must end in buffer 0, after which
+    // (reference boundary) buffer 1's halo is put back to 0 and the remaining steps are single sweeps -- the result and
+    // its halo end up exactly where the step-by-step driver leaves them.  An EVEN number of launches ping-pongs there by
+    // itself; an odd number (>= 3) makes its last two hops through a scratch grid owned by the plan (.. -> buffer 1 ->
+    // scratch -> buffer 0), which costs memory -- one more grid of 288 GB -- instead of a four-sweep launch replaced by
+    // two two-sweep ones (star2d1r 16384^2, 20 sweeps: 6.2 -> 5.5 ms).  With the Dirichlet boundary all halos simply stay.
+    // Three applications per launch (3D fp64, the natural form): launch k covers global steps 3 k + 1 .. 3 k + 3, reading
+    // buffer k mod 2 and writing the other one -- exactly where the step-by-step driver has these levels, so the launches
+    // run on the reference's own buffer state (buffer 0: the caller's halo, buffer 1: zeros; both the caller's under the
+    // Dirichlet option): no halo copies, no parity constraint on the number of launches, no scratch grid.  The kernel is
+    // told the parity of its first step (which of its inner levels sees which halo).  The two-application launches after
+    // them run like every other fused launch: both buffers carry the caller's halo meanwhile.
+    const int K = run_depth(p, times);
+    const Schedule sc = plan_schedule(plan, times, /*allocate=*/!plan->capturing);
+    const int n = (int) sc.depths.size();
+    int full = 0, done = 0;
+    for (int d : sc.depths) {
+        full += d == K;
+        done += d;
     }
-    if (fs.nk + fs.n2 > 0) {
-        // Temporal fusion.  A fused launch reads a buffer whose halo is the level-0 halo and writes another one, so
-        // while fused launches run every physical buffer carries buffer 0's halo; the data must end in buffer 0, after
-        // which (reference boundary) buffer 1's halo is put back to 0 and the remaining steps are single sweeps -- the
-        // result and its halo end up exactly where the step-by-step driver leaves them.  An EVEN number of launches
-        // ping-pongs there by itself; an odd number (>= 3) makes its last two hops through a scratch grid owned by the
-        // plan (.. -> buffer 1 -> scratch -> buffer 0), which costs memory -- one more grid of 288 GB -- instead of a
-        // four-sweep launch replaced by two two-sweep ones (star2d1r 16384^2, 20 sweeps: 6.2 -> 5.5 ms).  With the
-        // Dirichlet boundary all halos simply stay.
+    void *scratch = sc.scratch ? plan->scratch : nullptr;
+    if (n > 0) {
         if (int rc = lora::check_buffers(d_buf0, d_buf1)) return rc;
-        const int n = fs.nk + fs.n2;
-        void *scratch = fs.scratch ? plan->scratch : nullptr;
         if (!dirichlet)
-            if (int rc = halo(buf[1], buf[0], lora::HALO_COPY, "halo copy")) return rc;
+            if (int rc = sc.natural ? halo(buf[1], nullptr, lora::HALO_ZERO, "halo reset") : halo(buf[1], buf[0], lora::HALO_COPY, "halo copy"))
+                return rc;
         if (scratch)
             if (int rc = halo(scratch, buf[0], lora::HALO_COPY, "halo copy")) return rc;
-        for (int k = 0; k < n; ++k) {
-            void *src = buf[k % 2], *dst = buf[(k + 1) % 2];
-            if (scratch && k == n - 2) dst = scratch;  // k odd: buffer 1 -> scratch
-            if (scratch && k == n - 1) {               // k even: scratch -> buffer 0
-                src = scratch;
-                dst = buf[0];
-            }
-            if (k == fs.nk) mark(1);
-            int rc;
-            if (p.ndim <= 2 && k >= fs.nk) {  // a shallower launch (1D: the same kernel at another depth; 2D: four or two)
-                const int depth = p.steps_per_launch;
-                p.steps_per_launch = fs.tail[k - fs.nk];
-                rc = lora_plan_stepk(plan, src, dst, stream);
-                p.steps_per_launch = depth;
-            } else {
-                rc = k < fs.nk ? lora_plan_stepk(plan, src, dst, stream) : lora_plan_step2(plan, src, dst, stream);
-            }
-            if (rc != LORA_OK) return rc;
+    }
+    for (int k = 0; k < n; ++k) {
+        if (k == full) {
+            mark(1);
+            if (sc.natural && !dirichlet)
+                if (int rc = halo(buf[1], buf[0], lora::HALO_COPY, "halo copy")) return rc;
         }
-        if (fs.n2 == 0) mark(1);
-        if (!dirichlet)
-            if (int rc = halo(buf[1], nullptr, lora::HALO_ZERO, "halo reset")) return rc;
-        done = K * fs.nk + 2 * fs.n2;
-        if (p.ndim <= 2) {
-            done = K * fs.nk;
-            for (int q = 0; q < fs.n2; ++q) done += fs.tail[q];
+        void *src = buf[k % 2], *dst = buf[(k + 1) % 2];
+        if (scratch && k == n - 2) dst = scratch;  // k odd: buffer 1 -> scratch
+        if (scratch && k == n - 1) {               // k even: scratch -> buffer 0
+            src = scratch;
+            dst = buf[0];
         }
-        if (marks) marks->fused_launches = fs.nk;
-        if (marks) marks->two_launches = fs.n2;
-    } else if (!natural3) {
-        mark(1);
+        lora::Apps a{sc.depths[k], 0, p.dims[0]};
+        a.depth = K;
+        a.halo = buf[0];
+        a.parity = k & 1;
+        if (int rc = lora::launch_apps(p, a, src, dst, s)) return rc;
+    }
+    if (full == n) mark(1);
+    if (!dirichlet && n > (sc.natural ? full : 0))
+        if (int rc = halo(buf[1], nullptr, lora::HALO_ZERO, "halo reset")) return rc;
+    if (marks) {
+        marks->fused_launches = full;
+        marks->two_launches = n - full;
     }
     mark(2);
     for (int i = done; i < times; ++i) {  // 2d/gpu.cu:544-546
@@ -1650,40 +1461,23 @@ static void drop_graph(lora_plan *plan) {
     plan->graph_times = -1;
 }
 
-// 1D runs with the automatic launch depth fuse more applications per launch the longer the run is: 8 is the plan's
-// own depth (what lora_plan_stepk and the slab drivers use), 16 / 32 pay from 32 / 64 sweeps on (2^20 points: 840 ->
-// 999 -> 1066 GStencils/s per launch, 2^28: 1600 -> 1915 -> 1987; tools/k1d.sh) while short runs keep enough fused
-// launches.  Scoped to one lora_plan_run / lora_plan_run_profiled call.
-struct RunDepth1D {
-    Plan &p;
-    const int saved;
-    RunDepth1D(Plan &plan, int times) : p(plan), saved(plan.steps_per_launch) {
-        if (p.ndim == 1 && p.steps_per_launch_req == 0 && p.steps_per_launch == 8 && p.boundary != LORA_BC_PERIODIC)
-            p.steps_per_launch = times >= 64 ? 32 : (times >= 32 ? 16 : 8);
-    }
-    ~RunDepth1D() { p.steps_per_launch = saved; }
-};
-
 // Everything lora_plan_run(times) would allocate on first need, now: the scratch grid of a schedule with an odd number of
 // fused launches (a hipMalloc + hipMemset of one more padded grid -- usually a millisecond or two, but on a fresh device
 // it has taken 60 ms, INSIDE whatever region the caller was timing: the "four times slower" runs of DESIGN section 7), the
 // extended grid's plan and buffers of a periodic run.  Idempotent; lora_plan_run works without it.
 int lora_plan_prepare_run(lora_plan *plan, int times) {
     if (!plan || times < 0) return LORA_EINVAL;
-    Plan &p = plan->p;
-    RunDepth1D depth(p, times);
-    if (p.boundary == LORA_BC_PERIODIC) {
+    if (plan->p.boundary == LORA_BC_PERIODIC) {
         if (times >= 2) (void) torus_prepare(plan);
         return LORA_OK;
     }
-    if (run_can_fuse(p) && !run_is_natural3(p)) (void) fused_schedule(plan, times, true);
+    (void) plan_schedule(plan, times, true);
     return LORA_OK;
 }
 
 int lora_plan_run(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *stream) {
     if (!plan || times < 0) return LORA_EINVAL;
-    Plan &p = plan->p;
-    RunDepth1D depth(p, times);
+    const Plan &p = plan->p;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // Launch-bound runs (small grids, many steps: the reference's 1D size sweeps in ~2 us per step) are captured
     // once into a hipGraph and replayed; big grids gain nothing and are launched directly.  Capture needs a real
@@ -1706,7 +1500,7 @@ int lora_plan_run(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *
         if (int rc = lora::check_buffers(d_buf0, d_buf1)) return rc;
         // a scratch grid, if this run's schedule wants one, is allocated BEFORE the capture (hipMalloc and the null-stream
         // memset do not belong inside one); while capturing, run_launches only uses a grid that is already there
-        if (run_can_fuse(p) && !run_is_natural3(p)) (void) fused_schedule(plan, times, true);
+        (void) plan_schedule(plan, times, true);
         if (p.boundary == LORA_BC_PERIODIC && times >= 2) (void) torus_prepare(plan);  // (likewise: the extended grid's buffers)
         hipGraph_t graph = nullptr;
         hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
@@ -1746,7 +1540,6 @@ int lora_plan_run(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *
 int lora_plan_run_profiled(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *stream,
                            lora_run_profile *profile) {
     if (!plan || times < 0 || !profile) return LORA_EINVAL;
-    RunDepth1D depth(plan->p, times);
     RunMarks marks;
     struct Guard {
         RunMarks &m;
@@ -1760,7 +1553,7 @@ int lora_plan_run_profiled(lora_plan *plan, void *d_buf0, void *d_buf1, int time
     if (rc != LORA_OK) return rc;
     LORA_HIP_TRY(hipEventSynchronize(marks.ev[3]));
     profile->fused_launches = marks.fused_launches;
-    profile->apps_per_fused_launch = marks.fused_launches ? plan->p.steps_per_launch : 1;
+    profile->apps_per_fused_launch = marks.fused_launches ? run_depth(plan->p, times) : 1;
     profile->two_launches = marks.two_launches;
     profile->single_launches = marks.single_launches;
     LORA_HIP_TRY(hipEventElapsedTime(&profile->fused_ms, marks.ev[0], marks.ev[1]));

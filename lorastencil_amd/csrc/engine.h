@@ -115,8 +115,8 @@ void plan_refresh(Plan &p);  // re-derive tapset / low-rank factors / kernel nam
 // ---- kernel launchers (kernels_*.hip).  Interior index range [begin, end) of the outermost
 // dimension; all return the launch status. ----------------------------------------------------
 hipError_t launch_1d(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
-// steps_per_launch (2 / 4 / 8) applications per launch, intermediate levels in LDS
-hipError_t launch_1d_fused(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
+// K (2 / 4 / 8 / 16 / 32) applications per launch, intermediate levels in LDS
+hipError_t launch_1d_fused(const Plan &p, int K, const double *in, double *out, int begin, int end, hipStream_t s);
 const char *kernel_name_1d_fused(const Plan &p);
 hipError_t launch_2d_direct(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
 hipError_t launch_2d_mfma(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
@@ -171,6 +171,23 @@ bool prepare_3d_bf16_lanes(const Plan &p);  // false: no workgroup of it fits a 
 // bf16 box, two applications per launch, in-plane passes on v_mfma_f32_16x16x32_bf16 (LORA_VARIANT_MFMA)
 hipError_t launch_3d_bf16_mfma2(const Plan &p, const void *in, void *out, int begin, int end, hipStream_t s);
 const char *kernel_name_3d_bf16_mfma2(const Plan &p);
+
+// ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
+// One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,
+// [begin2, end2) (register-resident 3D kernels only; empty = none).
+struct Apps {
+    int napps = 1;
+    int begin = 0, end = 0, begin2 = 0, end2 = 0;
+    const void *halo = nullptr;  // three applications (3D): the buffer with the caller's halo (nullptr = d_in) ...
+    int parity = 0;              // ... and the parity of the launch's first global step
+    int depth = 0;               // the deepest launch the caller allows: 0 = the plan's own; a 1D run passes its run depth
+    bool step2 = false;          // lora_plan_step2's two-application kernel rather than the plan's family at depth 2
+};
+// Whether the plan's kernels have a launch of `napps` applications (lora_plan_stepn_region's contract).
+bool has_depth(const Plan &p, int napps);
+// Validates buffers and ranges, launches, and turns a launch error into LORA_EHIP; LORA_EUNSUPPORTED (checked first) for a
+// launch the plan's kernels do not have.
+int launch_apps(const Plan &p, const Apps &a, const void *d_in, void *d_out, hipStream_t s);
 
 const char *kernel_name_1d(const Plan &p);
 const char *kernel_name_2d_direct(const Plan &p);

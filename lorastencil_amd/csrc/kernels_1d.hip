@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void stencil1d_fusedk_kernel(const ArgsFused1D
 
 }  // namespace
 
-hipError_t launch_1d_fused(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s) {
+hipError_t launch_1d_fused(const Plan &p, int K, const double *in, double *out, int begin, int end, hipStream_t s) {
     if (end <= begin) return hipSuccess;
     if (begin & 1) return hipErrorInvalidValue;
     ArgsFused1D a;
@@ -156,15 +156,15 @@ hipError_t launch_1d_fused(const Plan &p, const double *in, double *out, int beg
     Taps9 w;
     for (int t = 0; t < 9; ++t) w.w[t] = p.w[t];
     const long blocks = ((long) end - begin + kFusedOut - 1) / kFusedOut;
-    if (p.steps_per_launch == 32)
+    if (K == 32)
         hipLaunchKernelGGL((stencil1d_fusedk_kernel<32>), dim3((unsigned) blocks), dim3(256), 0, s, a, w);
-    else if (p.steps_per_launch == 16)
+    else if (K == 16)
         hipLaunchKernelGGL((stencil1d_fusedk_kernel<16>), dim3((unsigned) blocks), dim3(256), 0, s, a, w);
-    else if (p.steps_per_launch == 8)
+    else if (K == 8)
         hipLaunchKernelGGL((stencil1d_fusedk_kernel<8>), dim3((unsigned) blocks), dim3(256), 0, s, a, w);
-    else if (p.steps_per_launch == 4)
+    else if (K == 4)
         hipLaunchKernelGGL((stencil1d_fusedk_kernel<4>), dim3((unsigned) blocks), dim3(256), 0, s, a, w);
-    else if (p.steps_per_launch == 2)
+    else if (K == 2)
         hipLaunchKernelGGL((stencil1d_fusedk_kernel<2>), dim3((unsigned) blocks), dim3(256), 0, s, a, w);
     else
         return hipErrorInvalidValue;

@@ -1339,6 +1339,80 @@ def test_periodic_runs_in_fused_launches_on_a_ghost_extended_grid(L, O, shape, d
     assert prof.fused_launches == 0 and prof.single_launches == 8
 
 
+# The launch schedule of lora_plan_run, pinned: (shape, dims, dtype, boundary, options, times) -> (fused_launches,
+# apps_per_fused_launch, two_launches, single_launches) as lora_plan_run_profiled reports them.  Recorded on the MI355X;
+# the counts follow from the schedule rules alone (capi.cpp: run_depth, run_schedule, run_torus), not from the data.
+_S2, _S3, _B3 = (4096, 4096), (512, 512, 512), (384, 384, 384)
+RUN_SCHEDULES = [
+    # 1D: the run's own depth (8, 16 from 32 sweeps, 32 from 64), halving tails; an odd count via the scratch grid or not
+    ("1d1r", (1 << 20,), "f64", None, {}, 7, (0, 1, 2, 1)),
+    ("1d1r", (1 << 20,), "f64", None, {}, 24, (3, 8, 0, 0)),
+    ("1d1r", (1 << 20,), "f64", None, {"scratch": 0}, 24, (2, 8, 2, 0)),
+    ("1d1r", (1 << 20,), "f64", None, {}, 31, (3, 8, 2, 1)),
+    ("1d1r", (1 << 20,), "f64", None, {}, 33, (2, 16, 0, 1)),
+    ("1d1r", (1 << 20,), "f64", None, {}, 100, (3, 32, 1, 0)),
+    # 2D workgroup-row plan (six per launch): four / two tails, 6 + 2 as 4 + 4, the scratch grid or an even count
+    *[("star2d1r", _S2, "f64", None, {"scratch": sc}, t, exp)
+      for sc in (-1, 0)
+      for t, exp in ((1, (0, 1, 0, 1)), (2, (0, 1, 0, 2)), (3, (0, 1, 0, 3)), (5, (0, 1, 2, 1)), (8, (0, 1, 2, 0)),
+                     (13, (2, 6, 0, 1)), (20, (2, 6, 2, 0)))],
+    ("star2d1r", _S2, "f64", None, {}, 16, (2, 6, 1, 0)),
+    ("star2d1r", _S2, "f64", None, {"scratch": 0}, 16, (1, 6, 3, 0)),
+    ("star2d1r", _S2, "f64", None, {}, 18, (3, 6, 0, 0)),
+    ("star2d1r", _S2, "f64", None, {"scratch": 0}, 18, (2, 6, 2, 0)),
+    # Dirichlet: the workgroup-row kernel at four
+    ("box2d3r", (1024, 1024), "f64", "dirichlet", {}, 5, (0, 1, 2, 1)),
+    ("box2d3r", (1024, 1024), "f64", "dirichlet", {}, 12, (3, 4, 0, 0)),
+    ("box2d3r", (1024, 1024), "f64", "dirichlet", {"scratch": 0}, 12, (2, 4, 2, 0)),
+    ("box2d3r", (1024, 1024), "f64", "dirichlet", {}, 13, (3, 4, 0, 1)),
+    ("box2d3r", (1024, 1024), "f64", "dirichlet", {}, 20, (5, 4, 0, 0)),
+    # 3D fp64, three per launch on the reference's own buffer state: 50 = 14 x 3 + 4 x 2, 51 = 17 x 3
+    ("star3d1r", (256, 256, 256), "f64", None, {"steps_per_launch": 3}, 50, (14, 3, 4, 0)),
+    ("star3d1r", (256, 256, 256), "f64", None, {"steps_per_launch": 3}, 51, (17, 3, 0, 0)),
+    # 3D register-resident kernels (four per launch) and their two-application tails
+    *[(shape, dims, "f64", None, {}, t, exp)
+      for shape, dims in (("star3d1r", _S3), ("box3d1r", _B3))
+      for t, exp in ((5, (0, 1, 2, 1)), (6, (1, 4, 1, 0)), (7, (1, 4, 1, 1)), (50, (12, 4, 1, 0)))],
+    ("star3d1r", _S3, "f64", None, {}, 12, (3, 4, 0, 0)),
+    ("star3d1r", _S3, "f64", None, {"scratch": 0}, 12, (2, 4, 2, 0)),
+    ("box3d1r", _B3, "bf16", None, {}, 50, (12, 4, 1, 0)),
+    # periodic: fused launches of the extended plan (six per launch); the outer plan's depth is what is reported
+    ("star2d1r", (1024, 1024), "f64", "periodic", {}, 20, (3, 2, 1, 0)),
+    ("star2d1r", (1024, 1024), "f64", "periodic", {}, 13, (2, 2, 0, 1)),
+]
+
+
+def test_run_schedules_are_pinned(L):
+    """lora_plan_run's launch schedule for a fixed table of plans and step counts, exactly (the tests above only bound it);
+    once more through a captured hipGraph on a side stream, where the scratch grid is prepared before the capture."""
+    import torch
+
+    def counts(shape, dims, dtype, boundary, options, times, stream=None, graph=False):
+        plan = L.Plan(shape, dims, dtype=dtype)
+        if boundary:
+            plan.set_boundary(boundary)
+        for k, v in options.items():
+            plan.set_option(k, v)
+        b0 = torch.ones(L.padded_shape(shape, dims), dtype=torch.bfloat16 if dtype == "bf16" else torch.float64,
+                        device="cuda")
+        b1 = torch.zeros_like(b0)
+        torch.cuda.synchronize()
+        if graph:
+            plan.set_option("graph", 1)
+            plan.run(b0, b1, times, stream=stream)
+            stream.synchronize()
+        prof = plan.run_profiled(b0, b1, times, stream=stream)
+        torch.cuda.synchronize()
+        return prof.fused_launches, prof.apps_per_fused_launch, prof.two_launches, prof.single_launches
+
+    for shape, dims, dtype, boundary, options, times, exp in RUN_SCHEDULES:
+        got = counts(shape, dims, dtype, boundary, options, times)
+        assert got == exp, (shape, dims, dtype, boundary, options, times)
+    side = torch.cuda.Stream()
+    for times, exp in ((13, (2, 6, 0, 1)), (16, (2, 6, 1, 0))):
+        assert counts("star2d1r", _S2, "f64", None, {}, times, stream=side, graph=True) == exp, times
+
+
 def test_plan_halo_modes(L, O):
     """lora_plan_halo: copy / zero / wrap of every cell outside the interior, any shape, fp64 and bf16."""
     import torch
