@@ -220,7 +220,9 @@ int lora_set_default_normalize(int on);
  *                     each.  Grids smaller than a ghost zone and plans with steps_per_launch = 1 use the latter anyway
  * ("ablate", the load/store-removing timing experiment of round 1, exists only in -DLORA_DIAGNOSTICS builds of the
  * library; the shipped one answers LORA_EINVAL.)
- * lora_plan_get_option also reads the resolved "tapset", "variant", "fused_eval", "boundary". */
+ * lora_plan_get_option reads every key lora_plan_set_option takes -- the value that was set; for "steps_per_launch" and
+ * "fused_rows" the resolved value the plan runs with -- and the read-only resolved "tapset", "variant", "fused_eval",
+ * "boundary".  ("ablate": only in -DLORA_DIAGNOSTICS builds, like its set.) */
 int lora_plan_set_option(lora_plan *plan, const char *key, int value);
 int lora_plan_get_option(const lora_plan *plan, const char *key, int *value);
 size_t lora_plan_padded_bytes(const lora_plan *plan);

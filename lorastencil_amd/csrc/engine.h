@@ -46,27 +46,47 @@ struct LowRank2D {
 };
 
 // ---- plan -------------------------------------------------------------------------------------
-struct Plan {
+// What a refresh derives from the taps and the requested state below (plan.cpp: resolve_1d / _2d / _3d).  Every refresh
+// starts from these defaults, so nothing here outlives the state it was derived from.
+struct Resolved {
+    int tapset = 0;
+    int fused_rows = 8;       // 2D fused: intermediate rows per wave (tile = 4x this - 6 output rows)
+    int steps_per_launch = 1;
+    int fused_eval = 0;       // 0..2 = direct taps of `tapset`, 3 = low-rank diamond, 4..6 = low-rank pyramid forms, 7 = nested profiles
+    double lowrank_rc = 0.0;  // weight of the diamond form's 8-point correction
+    double nest_g[4] = {0, 0, 0, 0}, nest_a[4] = {0, 0, 0, 0};  // fused_eval 7: nested-profile form (rows_2d.h)
+    bool lowrank_valid = false;
+    LowRank2D lowrank{};
+    int wg_active = 0;        // 2D fused launches go through the workgroup-row kernel
+    int stream3_active = 0;   // 3D fused launches go through the plane-streaming kernel
+    int lanes3_active = 0;    // 3D fused launches go through the register-resident kernels
+    double sep64[9] = {0};    // fp64 factors c(x), b(y), a(z) of exactly separable 3D taps (plane-streaming / register-resident kernels)
+    int sep64_valid = 0;      // the fp64 taps are exactly separable and the option allows that form
+    float sep[9] = {0};       // factors c(x), b(y), a(z) when tapset == TAPS3D_SEP
+    bool mfma3_valid = false; // bf16: the taps are scale * a (x) b (x) c with bf16-exact normalised factors (MFMA variant)
+    float mfma3_scale = 0.0f, mfma3_abc[9] = {0};  // normalised c, b, a
+    std::string kernel_name;
+};
+
+// The requested state: what the caller fixed at creation or set since.  (`variant` is a request a refresh may downgrade
+// when the taps / boundary no longer allow the matrix-pipe kernels.)
+struct Plan : Resolved {
     int shape = 0, ndim = 0, dtype = LORA_F64;
     int dims[3] = {0, 0, 0};  // interior extents, outermost first
     int ntaps = 0;
     double w[49] = {0};  // taps applied per sweep
     int variant = LORA_VARIANT_DIRECT;
-    int tapset = 0;
-    // tuning knobs (lora_plan_set_option)
+    bool generic = false;  // odd innermost extent: rows are only 8-byte aligned, the tiled kernels do not apply
+    int boundary = LORA_BC_REFERENCE;  // what halo cells hold between sweeps (lora_plan_set_boundary)
+    unsigned epoch = 0;   // bumped by every change of taps / options: invalidates a cached graph
+    // tuning knobs (lora_plan_set_option; plan.cpp: kOptions)
     int rows_per_thread = 8;  // 2D direct: output rows per lane (tile height = 4x this)
     int panel_width = 32;     // 2D: tile columns per L2 panel of the block->tile map
     int nt_store = 0;         // 2D: non-temporal output stores
     int fused_rows_req = 0;   // 0 = auto, else 6 / 8 / 10
-    int fused_rows = 8;       // 2D fused: intermediate rows per wave (tile = 4x this - 6 output rows), resolved
     int cols_per_lane = 4;    // 3D bf16: 4 (512-byte row pieces per wave) or 8 (1 KiB)
     int separable = -1;       // 3D bf16: evaluate exactly-separable taps as x/y/z passes: -1 auto (= on), 0 off
-    double sep64[9] = {0};    // fp64 factors c(x), b(y), a(z) of exactly separable 3D taps (plane-streaming kernel)
-    int sep64_valid = 0;      // resolved: the fp64 taps are exactly separable and the option allows that form
-    float sep[9] = {0};       // resolved factors c(x), b(y), a(z) when tapset == TAPS3D_SEP
     int mfma_split = 1;       // bf16 MFMA variant: intermediate as hi + lo bf16 halves (1, the contract) or one bf16 rounding (0)
-    bool mfma3_valid = false; // bf16: the taps are scale * a (x) b (x) c with bf16-exact normalised factors (MFMA variant)
-    float mfma3_scale = 0.0f, mfma3_abc[9] = {0};  // normalised c, b, a
     int ablate = 0;           // diagnostics only (2D fused, 3D bf16): 1 = skip stores, 2 = skip loads; results wrong
     int lds_dma = 0;          // 3D bf16: global_load_lds ring, two planes ahead (hand-counted vmcnt)
     int persistent = 0;       // 2D fused: persistent workgroups with register prefetch of the next tile
@@ -77,40 +97,49 @@ struct Plan {
     int stream_prefetch = 0;  // ... K = 4: fetch the next level's LDS window while the current level computes (measured: no gain)
     int stream_sync = 1;      // ... s_barrier per 7 rows (1) / per row (2) keeps a workgroup's four strips in step
     int wg = -1;              // 2D fused launches through the workgroup-row kernel (kernels_2d_wg.hip): -1 = when the plan fuses six applications per launch (then also its four / two tails), 0 never, 1 always
-    int wg_active = 0;        // resolved
     int wg_rows = 0;          // 2D workgroup-row kernel (kernels_2d_wg.hip): output rows per chunk (0 = auto: one round of resident workgroups)
     int wg_prio = 12;         // ... time-sliced wave priorities that share a CU evenly between its two workgroups: log2 of the slice in 10 ns ticks (0 = off)
     int wg_edge_pct = -1;     // ... how much shorter the chunks of the first / last strip are, in per cent of a step's cost (-1 = default)
     int z_chunk = 16;         // 3D: output planes streamed per workgroup
     int fused_pipeline = 0;   // 3D bf16 fused: 1 = level 2 one plane behind level 1, one barrier per plane (no gain measured)
     int stream3 = -1;         // 3D fp64 fused: plane-streaming kernel (kernels_3d_planes.hip: 2 or 3 applications per launch) always (1), never (0: the tile kernel, 2 applications), or by grid size (-1)
-    int stream3_active = 0;   // resolved: fused launches go through the plane-streaming kernel
     int stream3_waves = 0;    // 3D plane-streaming kernel: waves per workgroup: 0 = automatic, 8 (one workgroup per CU) or 4 (two); output tiles of 8 x waves - 2 (K - 1) rows x 60 columns
     int stream3_pipe = 0;     // 3D plane-streaming kernel: 1 = every level consumes what was published one step earlier (one barrier per step, two buffers per level)
     int stream3_async = 0;    // 3D plane-streaming kernel: 1 = no workgroup barriers (neighbour-wave counters in LDS, private input rings)
-    int stream3_slots = 0;    // 3D plane-streaming kernel: input plane slots of the LDS ring (0 = as many as fit)
+    int stream3_slots = 0;    // 3D plane-streaming kernel: input plane slots of the LDS ring (0 or kStream3Slots: the one ring there is)
     int lanes3 = -1;          // 3D fused launches through the register-resident kernels (kernels_3d_lanes.hip, fp64; kernels_3d_bf16_lanes.hip, bf16: four applications per launch): -1 by grid size, 0 never, 1 always (star / separable box taps, reference boundary)
-    int lanes3_active = 0;    // resolved
     int fused_z_chunk = 0;    // 3D fused: output planes per workgroup (0 = auto: 32, shorter on small grids)
     int spans3 = -1;          // 3D register-resident kernels: cut the (tile, plane) line into equal pieces per CU (1), equal chunks per tile (0), by region depth (-1)
     int torus = 1;            // periodic boundary: runs in fused launches on a ghost-extended grid (1), single sweeps behind a wrap each (0)
-    int steps_per_launch_req = 0;  // 0 = auto, 1, 2 (2D / 3D), 4 (2D row-streaming kernel), 2 / 4 / 8 (1D)
-    int steps_per_launch = 1;      // resolved
-    bool generic = false;  // odd innermost extent: rows are only 8-byte aligned, the tiled kernels do not apply
+    int steps_per_launch_req = 0;  // 0 = auto, 1, 2 (2D / 3D), 3 / 4 (3D), 4 / 6 (2D), 2 .. 32 (1D)
     int lowrank_valu = -1;    // 2D fused: low-rank evaluation on the vector pipe: -1 auto, 0 off, 1 on when the factors fit
-    int fused_eval = 0;       // resolved: 0..2 = direct taps of `tapset`, 3 = low-rank diamond, 4..6 = low-rank pyramid forms, 7 = nested profiles
-    double lowrank_rc = 0.0;  // weight of the diamond form's 8-point correction
-    double nest_g[4] = {0, 0, 0, 0}, nest_a[4] = {0, 0, 0, 0};  // fused_eval 7: nested-profile form (rows_2d.h)
-    bool lowrank_valid = false;
-    LowRank2D lowrank{};
-    std::string kernel_name;
-    int boundary = LORA_BC_REFERENCE;  // what halo cells hold between sweeps (lora_plan_set_boundary)
     int use_scratch = -1; // odd numbers of fused launches route through a scratch grid owned by the plan: -1 / 1 yes, 0 no
     int use_graph = -1;   // -1 auto (small grids, many launches, non-default stream), 0 never, 1 whenever possible
-    unsigned epoch = 0;   // bumped by every change of taps / options: invalidates a cached graph
 };
 
-void plan_refresh(Plan &p);  // re-derive tapset / low-rank factors / kernel name from w + options
+// ---- one predicate per fact about a plan ------------------------------------------------------------------------------
+// The deepest launch a plan of `ndim` dimensions can have (1D fused kernel / 2D workgroup-row kernel / 3D register-resident
+// kernels).
+constexpr int max_depth(int ndim) { return ndim == 1 ? 32 : (ndim == 2 ? 6 : 4); }
+// The 3D plane-streaming kernel's LDS ring has two input plane slots (deeper rings -- 7 waves x 3 slots, 6 x 4 -- were
+// built and measured within 3 % of it; they are gone again).
+constexpr int kStream3Slots = 2;
+// Whether the plan has kernels that fuse applications at all: every 1D plan, 2D plans of the direct variant, 3D plans --
+// with an odd innermost extent only where `odd_ok` says one of them takes such rows.
+inline bool has_fused_kernels(const Plan &p, bool odd_ok) {
+    return p.ndim == 1 || ((p.ndim == 3 || p.variant == LORA_VARIANT_DIRECT) && (!p.generic || odd_ok));
+}
+// ... as resolved: odd rows go through the 2D row-streaming family under the reference boundary (the source's own halo),
+// in 3D through the register-resident kernels.
+inline bool has_fused_kernels(const Plan &p) {
+    return has_fused_kernels(p, p.ndim == 2 ? p.stream2 && p.boundary == LORA_BC_REFERENCE : p.lanes3_active != 0);
+}
+// Whether the 3D matrix-pipe variant applies: bf16 box taps with bf16-exact factors, reference boundary, fused launches.
+inline bool mfma3_applies(const Plan &p) {
+    return p.dtype == LORA_BF16 && p.mfma3_valid && p.boundary == LORA_BC_REFERENCE && p.steps_per_launch_req != 1;
+}
+
+void plan_refresh(Plan &p);  // plan.cpp: re-derive everything in Resolved from w + the requested state
 
 // ---- kernel launchers (kernels_*.hip).  Interior index range [begin, end) of the outermost
 // dimension; all return the launch status. ----------------------------------------------------
@@ -154,7 +183,6 @@ const char *kernel_name_3d_stream(const Plan &p);
 hipError_t launch_3d_lanes(const Plan &p, int K, const double *in, double *out, int begin, int end, hipStream_t s, int begin2 = 0, int end2 = 0);
 const char *kernel_name_3d_lanes(const Plan &p);
 bool prepare_3d_lanes(const Plan &p);
-int stream3_slots(int K, int waves, int pipe, int requested);
 int stream3_waves(const Plan &p, int K, int pipe);
 // any size, any taps (odd innermost extents): one thread per point
 hipError_t launch_2d_generic(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
@@ -198,6 +226,7 @@ int region_granularity(const Plan &p);
 void set_last_error(const char *what, hipError_t e);
 void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
+void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus)
 const char *run_label(int shape);                  // the operator's first stdout line (e.g. 2d/gpu.cu:549)
 
 }  // namespace lora

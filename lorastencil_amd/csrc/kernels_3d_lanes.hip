@@ -582,7 +582,7 @@ hipError_t launch_3d_lanes(const Plan &p, int K, const double *in, double *out, 
 }
 
 // one-time host work (kernel resolution, residency query) of the plan's instantiations; no launch.  false: a device is
-// there and says no workgroup of the kernel fits it -- the plan then keeps the tile kernels (capi.cpp: plan_refresh).
+// there and says no workgroup of the kernel fits it -- the plan then keeps the tile kernels (plan.cpp: resolve_3d).
 bool prepare_3d_lanes(const Plan &p) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {

@@ -792,10 +792,7 @@ hipError_t launch_stream3(const Plan &p, const double *in, double *out, const do
 }  // namespace
 
 // workgroup shapes, bounded by 160 KiB of LDS per CU (80 KiB for two 4-wave workgroups per CU): 8 waves (one workgroup
-// per CU) or 4 (two), always two input plane slots; the pipelined three-level form fits with 6 waves only.  (Deeper
-// rings -- 7 waves x 3 slots, 6 x 4 -- were built and measured within 3 % of these; they are gone again.)
-int stream3_slots(int, int, int, int) { return 2; }
-
+// per CU) or 4 (two), always kStream3Slots input plane slots; the pipelined three-level form fits with 6 waves only.
 int stream3_waves(const Plan &p, int K, int pipe) {
     int req = p.stream3_waves;
     if (req == 0) {
@@ -817,7 +814,7 @@ hipError_t launch_3d_stream(const Plan &p, int K, const double *in, double *out,
     // (the three-level form has its second barrier in between) -- found by the full-size tests, invisible on small grids.
     const int pipe = (K == 2 || p.stream3_pipe) ? 1 : 0;
     const int nw = stream3_waves(p, K, pipe);
-    const int ns = stream3_slots(K, nw, pipe, p.stream3_slots);
+    const int ns = kStream3Slots;
 #define LORA_S3(KK, WW, SS, PP)                                                                                       \
     if (K == KK && nw == WW && ns == SS && pipe == PP)                                                                \
         return p.tapset == TAPS3D_STAR                                                                                \

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bf16 box3d1r: GStencils/s per launch of the register-resident kernel (four sweeps) and the tile kernel (two) over grid
-sizes -- where the plan should switch (capi.cpp plan_refresh).   python tools/bf16_crossover.py > gpurun_out/..."""
+sizes -- where the plan should switch (plan.cpp resolve_3d).   python tools/bf16_crossover.py > crossover.jsonl"""
 import json
 import os
 import sys
