@@ -148,6 +148,11 @@ int lora_last_run_info(lora_run_info *info);
  *    A plan fixes shape, interior dims, weights and kernel variant; it owns no grid memory.
  *    Buffers are PADDED device arrays laid out like the host arrays of group A; `stream` is a
  *    hipStream_t passed as void* (NULL = the null stream).  Calls are asynchronous.
+ *    Alignment: every buffer given to a launch or a run must be 16-byte aligned (LORA_EUNSUPPORTED otherwise) and need
+ *    not be more -- a sub-array of a bigger allocation will do.  No kernel reads or writes global memory in pieces wider
+ *    than 16 bytes, and each piece sits at a multiple of its width from the buffer's base (of 8 bytes on the paths that
+ *    take odd innermost extents).  Nothing outside [base, base + lora_plan_padded_bytes) is written, and nothing read
+ *    there reaches a result.
  *    Different plans may be used from different threads at the same time; one plan must not be (it caches the
  *    hipGraph of its last run and its options are plain fields).
  * ====================================================================================== */
@@ -283,7 +288,12 @@ int lora_copy_block_f64(void *d_dst, long dst_ld, const void *d_src, long src_ld
 /* The time-step driver (2d/gpu.cu:544-546): `times` applications ping-ponging between the two
  * buffers starting from d_buf0; the result is in buffer [times % 2] (the other buffer's interior is
  * unspecified).  The caller must have put the padded input in d_buf0 and zeros in d_buf1 to get the
- * reference semantics.  Fused launches move K time levels per buffer flip, so an ODD number of them
+ * reference semantics.
+ * What is read of d_buf1 as the caller left it: under LORA_BC_REFERENCE its HALO cells only (odd sweeps read them: zeros
+ * are the reference's), its interior may hold anything -- every interior cell is written before it is read; under
+ * LORA_BC_DIRICHLET and LORA_BC_PERIODIC nothing -- the run rewrites the halo before the first read --, so the whole
+ * buffer may hold anything.  times == 0 touches neither buffer.
+ * Fused launches move K time levels per buffer flip, so an ODD number of them
  * would leave the data in the wrong buffer: the plan then routes the last two through a scratch grid of
  * its own (one more padded array, allocated on first need, freed with the plan; option "scratch" = 0
  * trades it for a shorter launch schedule instead). */

@@ -710,6 +710,7 @@ int lora_plan_prepare_run(lora_plan *plan, int times) {
 
 int lora_plan_run(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *stream) {
     if (!plan || times < 0) return LORA_EINVAL;
+    if (times == 0) return LORA_OK;  // nothing to launch -- and nothing to capture: an empty graph is not worth a cache entry
     const Plan &p = plan->p;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // Launch-bound runs (small grids, many steps: the reference's 1D size sweeps in ~2 us per step) are captured

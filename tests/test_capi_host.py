@@ -199,6 +199,26 @@ def test_plan_validation(L):
         p.step(0, 0)  # null buffers
 
 
+@pytest.mark.parametrize("shape,dims,dtype", [("1d1r", (4096,), "f64"), ("star2d1r", (64, 128), "f64"), ("box2d3r", (33, 65), "f64"),
+                                              ("star3d1r", (8, 16, 128), "f64"), ("box3d1r", (8, 16, 128), "bf16")])
+def test_device_buffers_must_be_16_byte_aligned(L, shape, dims, dtype):
+    """check_buffers (capi.cpp): the ONE alignment requirement of the launch and run entries, stated in include/lorastencil.h
+    -- 16 bytes, refused with LORA_EUNSUPPORTED before anything is launched (so this needs no device).  That 16 bytes are
+    also enough -- no kernel family assumes more of the base -- is what tests/test_gpu_memory_contract.py runs on the GPU,
+    on buffers that are 16 (mod 32)."""
+    from lorastencil_amd import _lib
+
+    p = L.Plan(shape, dims, dtype=dtype)
+    good = 0x7F0000010  # 16 (mod 32): the least the contract promises
+    for a, b in ((good + 8, good + 0x100000), (good, good + 0x100000 + 8), (good + 4, good + 0x100000), (good + 2, good + 0x100000 + 2)):
+        for launch in (lambda: p.step(a, b), lambda: p.stepk(a, b), lambda: p.step_region(a, b, 0, 2),
+                       lambda: p.stepn_region2(1, a, b, 0, 2, 2, 4), lambda: p.run(a, b, 1), lambda: p.run(a, b, 3)):
+            with pytest.raises(L.LoraError) as e:
+                launch()
+            assert e.value.status == _lib.LORA_EUNSUPPORTED, (shape, hex(a), hex(b))
+    assert "16-byte aligned" in _lib.lib().lora_last_error().decode()
+
+
 def test_block_copy_argument_checks(L):
     """lora_copy_block_f64 (the pack / unpack kernel of the 2-D block decomposition): what it refuses before any launch"""
     from lorastencil_amd import _lib
