@@ -140,6 +140,13 @@ int lora_run_host(int shape, const double *in, double *out, const double *params
  * patterns in uint16_t (LORA_BF16). */
 int lora_run_host_dtype(int shape, int dtype, const void *in, void *out, const double *params, int times,
                         const int *dims, int quiet, lora_run_info *info);
+/* lora_run_host_dtype with the run-until-steady driver of group B (lora_plan_run_until: see there for `u` and `r`) in place
+ * of a fixed number of sweeps: `out` receives level r->times_done; the three lines and lora_run_info are computed from
+ * times_done, the timed region holding the sweeps and their checks. */
+struct lora_until;
+struct lora_until_result;
+int lora_run_host_until(int shape, int dtype, const void *in, void *out, const double *params, const int *dims,
+                        const struct lora_until *u, struct lora_until_result *r, int quiet, lora_run_info *info);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -317,6 +324,60 @@ typedef struct lora_run_profile {
 } lora_run_profile;
 int lora_plan_run_profiled(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *stream,
                            lora_run_profile *profile);
+
+/* ---- reductions over grids on the device (NEW: the reference prints its "Result range" from a host loop over the copied-back
+ * array).  Both read the interior cells of the outermost range [begin, end) as lora_plan_step_region counts it (begin == end
+ * == 0: the whole interior; begin == end otherwise: no cell, the empty record), accumulate in fp64, and return the same bits
+ * for the same call every time (the work is cut by dtype and region shape alone; no atomics).  They keep the buffer
+ * contract above: pieces of at most 16 bytes, nothing read outside [base, base + lora_plan_padded_bytes), and no halo value
+ * reaches a result.  UNLIKE the launches above both BLOCK: they enqueue on `stream` (two small launches and a copy of the
+ * record), then wait until the result is in *out.  LORA_EINVAL for a null pointer or a bad range, LORA_EUNSUPPORTED for a
+ * misaligned buffer or a stream that is capturing, LORA_ENODEVICE without a device. */
+typedef struct lora_grid_stats {
+    double min, max, abs_max, sum, sum_sq; /* over the FINITE cells; none: min = +inf, max = -inf, the rest 0 */
+    long long count, nonfinite;            /* cells of the region; NaN or +-inf cells among them               */
+} lora_grid_stats;
+typedef struct lora_grid_diff {
+    double max_abs, sum_sq, a_abs_max; /* of d = (double) a - (double) b, one rounding, over the cells with finite d;
+                                          a_abs_max = max |a| over the same cells                                    */
+    long long argmax;                  /* LOWEST linear index in the PADDED array of a cell with |d| == max_abs; -1 if none */
+    long long count, nonfinite;        /* cells of the region; cells whose d is not finite                            */
+} lora_grid_diff;
+int lora_plan_stats(lora_plan *plan, const void *d_buf, int begin, int end, lora_grid_stats *out, void *stream);
+int lora_plan_diff(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_diff *out, void *stream);
+/* Host only: *into becomes the record of the union of two DISJOINT regions (the own rows of N slabs: lora_plan_stats takes
+ * lora_slab_plan, lora_slab_buffer(s, 2) and the own-row range of lora_slab_info as they are).  Start from a record of a
+ * region, or from the empty one {+inf, -inf, 0, 0, 0, 0, 0}. */
+void lora_grid_stats_merge(lora_grid_stats *into, const lora_grid_stats *part);
+
+/* Sweep until nothing changes.
+ *   check_every must be even and >= 2, otherwise LORA_EINVAL (also: a negative or NaN tol / rtol, an unknown norm, max_times < 0).
+ *   The loop runs while times_done + check_every <= max_times.  Each round:
+ *     lora_plan_run(plan, d_buf0, d_buf1, check_every, stream) -- an even run leaves the level in d_buf0 and both halos as a
+ *     fresh run expects them;
+ *     a PROBE: one raw lora_plan_step from d_buf0 into d_buf1 (under LORA_BC_PERIODIC after lora_plan_halo(..., LORA_HALO_WRAP)
+ *     on d_buf0);
+ *     diff(a = d_buf1, b = d_buf0) over the whole interior -> `last`; residual = last.max_abs (LORA_NORM_MAX) or
+ *     sqrt(last.sum_sq / last.count) (LORA_NORM_RMS).
+ *   Stop with diverged = 1 when last.nonfinite > 0; else with converged = 1 when residual <= tol + rtol * last.a_abs_max;
+ *   otherwise continue.
+ *   On return d_buf0 holds level times_done, BIT FOR BIT what lora_plan_run(times_done) gives from the same input; d_buf1's
+ *   interior is unspecified, as after any run, and its halo is as a run leaves it.  Not converging is not an error: LORA_OK
+ *   with converged = 0.  `residual` is for level times_done -> times_done + 1 (+inf if no round ran); checks = rounds done.
+ *   Cost per check: ONE single sweep plus ONE diff (about a sweep's bytes, read only) plus ONE synchronise of the host with
+ *   the stream -- choose check_every accordingly (a check costs about eight sweeps of a six-sweep launch: 60 adds 12 % to
+ *   a star2d1r run at 16384^2, 300 under 3 %).  Blocks like the reductions, and answers their status codes. */
+enum lora_norm { LORA_NORM_MAX = 0, LORA_NORM_RMS = 1 }; /* max |d|, sqrt(sum_sq / count) */
+typedef struct lora_until {
+    double tol, rtol;
+    int norm, check_every, max_times;
+} lora_until;
+typedef struct lora_until_result {
+    int times_done, checks, converged, diverged;
+    double residual;
+    lora_grid_diff last;
+} lora_until_result;
+int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_until *u, lora_until_result *r, void *stream);
 void lora_plan_destroy(lora_plan *plan);
 
 /* ========================================================================================

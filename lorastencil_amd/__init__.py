@@ -10,10 +10,14 @@ No CPU fallback exists: importing works anywhere the library is built, computing
 """
 from . import _lib
 from .ops import (  # noqa: F401
+    EMPTY_STATS,
     SHAPES,
     GlibcRand,
+    GridDiff,
+    GridStats,
     LoraError,
     Plan,
+    UntilResult,
     default_params,
     device_count,
     effective_weights,
@@ -30,7 +34,9 @@ from .ops import (  # noqa: F401
     padded_shape,
     reference_input,
     run_host,
+    run_host_until,
     separable_3x3x3,
+    stats_merge,
     svd_7x7,
     to_bf16,
 )

@@ -62,6 +62,30 @@ class RunProfile(ctypes.Structure):
     ]
 
 
+class GridStats(ctypes.Structure):
+    """lora_grid_stats: statistics of the finite interior cells of a region."""
+    _fields_ = [("min", ctypes.c_double), ("max", ctypes.c_double), ("abs_max", ctypes.c_double), ("sum", ctypes.c_double),
+                ("sum_sq", ctypes.c_double), ("count", ctypes.c_longlong), ("nonfinite", ctypes.c_longlong)]
+
+
+class GridDiff(ctypes.Structure):
+    """lora_grid_diff: difference of two grids of one plan over a region."""
+    _fields_ = [("max_abs", ctypes.c_double), ("sum_sq", ctypes.c_double), ("a_abs_max", ctypes.c_double),
+                ("argmax", ctypes.c_longlong), ("count", ctypes.c_longlong), ("nonfinite", ctypes.c_longlong)]
+
+
+class Until(ctypes.Structure):
+    _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int), ("check_every", ctypes.c_int),
+                ("max_times", ctypes.c_int)]
+
+
+class UntilResult(ctypes.Structure):
+    _fields_ = [("times_done", ctypes.c_int), ("checks", ctypes.c_int), ("converged", ctypes.c_int), ("diverged", ctypes.c_int),
+                ("residual", ctypes.c_double), ("last", GridDiff)]
+
+
+NORM_MAX, NORM_RMS = 0, 1
+
 _comm_begin_t = ctypes.CFUNCTYPE(ctypes.c_int, _vp)
 _comm_xfer_t = ctypes.CFUNCTYPE(ctypes.c_int, _vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp)
 
@@ -189,6 +213,12 @@ SIGNATURES = {
     "lora_plan_stepn_region2": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "lora_debug_span_cover": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "lora_plan_run": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp]),
+    "lora_plan_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridStats), _vp]),
+    "lora_plan_diff": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDiff), _vp]),
+    "lora_grid_stats_merge": (None, [ctypes.POINTER(GridStats), ctypes.POINTER(GridStats)]),
+    "lora_plan_run_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Until), ctypes.POINTER(UntilResult), _vp]),
+    "lora_run_host_until": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _dp, _ip, ctypes.POINTER(Until),
+                                           ctypes.POINTER(UntilResult), ctypes.c_int, ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),
     "lora_default_params": (ctypes.c_int, [ctypes.c_int, _dp]),
     "lora_effective_weights": (ctypes.c_int, [ctypes.c_int, _dp, _dp]),

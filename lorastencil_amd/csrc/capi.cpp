@@ -40,7 +40,7 @@ void set_last_run_info(const lora_run_info &info) { g_last_info = info; }
         }                                       \
     } while (0)
 
-static int check_buffers(const void *a, const void *b) {
+int check_buffers(const void *a, const void *b) {
     if (!a || !b) return LORA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(a) & 15) || (reinterpret_cast<uintptr_t>(b) & 15)) {
         g_last_error = "device buffers must be 16-byte aligned";
@@ -969,5 +969,7 @@ void release_run_state(lora_plan *plan) {
     if (plan->scratch) (void) hipFree(plan->scratch);
     plan->scratch = nullptr;
     torus_drop(plan);
+    if (plan->reduce_buf) (void) hipFree(plan->reduce_buf);
+    plan->reduce_buf = nullptr;
 }
 }  // namespace lora

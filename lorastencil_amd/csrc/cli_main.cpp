@@ -15,6 +15,8 @@
 //   --grid=AxB         (2D, 3D) cut the two outer dimensions into A x B blocks instead, one per GPU (csrc/blocks.cpp)
 //                      (lora_run_host_multi; the reference is single-GPU)
 //   --dtype=bf16       (lorastencil_3d only) store the grid in bf16, accumulate in fp32 (BASELINE config 5; new)
+//   --until=TOL        sweep until max |u(T+1) - u(T)| <= TOL, checked on the device every --check-every=N sweeps (N even,
+//                      default 60: a multiple of every launch depth); time_size becomes the cap (lora_run_host_until)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -131,6 +133,8 @@ int main(int argc, char *argv[]) {
     Fill fill = Fill::Random;
     int gpus = 1;
     int grid[2] = {0, 0};
+    bool until = false, gpus_given = false;
+    lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--check")
@@ -153,7 +157,32 @@ int main(int argc, char *argv[]) {
             lora_set_default_normalize(1);  // taps / sum(taps): finite for any number of steps
             normalize = true;
         }
+        else if (a.rfind("--until=", 0) == 0) {
+            const std::string v = a.substr(8);
+            char *rest = nullptr;
+            how.tol = std::strtod(v.c_str(), &rest);
+            if (v.empty() || *rest != '\0' || !(how.tol >= 0.0)) {
+                std::cerr << "Invalid argument: --until=TOL needs a non-negative number.\n";
+                return 1;
+            }
+            until = true;
+        }
+        else if (a.rfind("--check-every=", 0) == 0) {
+            try {
+                size_t used = 0;
+                const std::string v = a.substr(14);
+                how.check_every = std::stoi(v, &used);
+                if (used != v.size()) how.check_every = 0;
+            } catch (const std::exception &) {
+                how.check_every = 0;
+            }
+            if (how.check_every < 2 || how.check_every % 2) {
+                std::cerr << "Invalid argument: --check-every=N needs a positive even integer.\n";
+                return 1;
+            }
+        }
         else if (a.rfind("--gpus=", 0) == 0) {
+            gpus_given = true;
             try {
                 gpus = std::stoi(a.substr(7));
             } catch (const std::exception &) {
@@ -185,6 +214,11 @@ int main(int argc, char *argv[]) {
             std::cerr << "Unknown option: " << a << "\n";
             return 1;
         }
+    }
+
+    if (until && (gpus_given || grid[0] > 0 || check)) {
+        std::cerr << "--until runs on one GPU against its own residual: not with --gpus, --grid or --check\n";
+        return 1;
     }
 
     double params[49];
@@ -225,7 +259,24 @@ int main(int argc, char *argv[]) {
         std::cerr << "--grid=AxB takes the reference boundary\n";
         return 1;
     }
-    if ((gpus > 1 || grid[0] > 0) && !bf16) {
+    lora_until_result reached = {};
+    if (until) {
+        // time_size is the cap; the operator prints the reference's three lines for the sweeps it did
+        how.max_times = times;
+        std::vector<uint16_t> in16, out16;
+        if (bf16) {
+            in16.resize(count);
+            out16.assign(count, 0);
+            lora_f64_to_bf16(matrix.data(), in16.data(), count);
+        }
+        const int rc = bf16 ? lora_run_host_until(shape, LORA_BF16, in16.data(), out16.data(), params, dims, &how, &reached, 0, nullptr)
+                            : lora_run_host_until(shape, LORA_F64, matrix.data(), output.data(), params, dims, &how, &reached, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+        if (bf16) lora_bf16_to_f64(out16.data(), output.data(), count);
+    } else if ((gpus > 1 || grid[0] > 0) && !bf16) {
         // N slabs (or A x B blocks), one per GPU; prints the reference's three lines like the single-GPU operator
         const int rc = grid[0] > 0 ? lora_run_host_blocks(shape, LORA_F64, matrix.data(), output.data(), params, times, dims, grid, 0, nullptr)
                                    : lora_run_host_multi(shape, LORA_F64, matrix.data(), output.data(), params, times, dims, gpus, 0, nullptr);
@@ -277,6 +328,10 @@ int main(int argc, char *argv[]) {
             break;
     }
 
+    if (extra && until)
+        std::printf("Until: times_done = %d, %s, residual = %g (max |u(T+1) - u(T)|, tol %g, checked every %d sweeps)\n", reached.times_done,
+                    reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
+                    how.check_every);
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra) {
         lora_run_info ri;

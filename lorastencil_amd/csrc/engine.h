@@ -200,6 +200,33 @@ bool prepare_3d_bf16_lanes(const Plan &p);  // false: no workgroup of it fits a 
 hipError_t launch_3d_bf16_mfma2(const Plan &p, const void *in, void *out, int begin, int end, hipStream_t s);
 const char *kernel_name_3d_bf16_mfma2(const Plan &p);
 
+// ---- reductions over a box of a padded array (kernels_reduce.hip; host side and geometry: reduce.cpp) ----------------
+// The unit one lane loads: 16 bytes (two fp64 cells, eight bf16 cells) or 8 (fp64 rows of odd length).
+enum ReduceKind { KIND_F64X2 = 0, KIND_F64X1 = 1, KIND_BF16X8 = 2 };
+constexpr int kReduceMaxGroups = 1024;  // workgroups of a launch at most; record [kReduceMaxGroups] is the folded result
+struct ReduceRecord {  // what a workgroup leaves: stats {min, max, sum, sum_sq | nonfinite}, diff {max_abs, sum_sq, a_abs_max | argmax, nonfinite}
+    double f[4];
+    long long i[2];
+};
+struct ReduceArgs {
+    long total, chunk;              // pieces of the box; pieces per workgroup
+    int ppr, e1;                    // pieces per row of the box; rows per outermost index
+    int q0, col_lo, col_hi;         // first piece of a row; padded column range of the box (cells outside are masked)
+    long off0;                      // cell offset of piece q0 of the box's first row
+    long row_stride, plane_stride;  // in cells
+    int dq, d1;                     // one stride of the lanes (reduce_threads() pieces) in digits: pieces, rows ...
+    long step_off, row_carry, plane_carry;  // ... and as cell offsets: the stride, a piece carry, a row carry
+};
+int reduce_threads();
+// The box lo[d] <= x < hi[d] in PADDED coordinates of a (1 x 1 x) ... array, outermost first as in Plan::dims: fills the
+// launch arguments, the piece kind and the number of workgroups -- functions of dtype, extents and box alone.  False for
+// an empty box.
+bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a, int &kind, int &groups);
+// Each: the reduction launch (one record per workgroup into partial[0 .. groups)) and the fold into partial[kReduceMaxGroups].
+hipError_t launch_reduce_stats(const ReduceArgs &a, int kind, int groups, const void *buf, ReduceRecord *partial, hipStream_t s);
+hipError_t launch_reduce_diff(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
+                              hipStream_t s);
+
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,
 // [begin2, end2) (register-resident 3D kernels only; empty = none).
@@ -226,7 +253,8 @@ int region_granularity(const Plan &p);
 void set_last_error(const char *what, hipError_t e);
 void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
-void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus)
+void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus, reduction records)
+int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 const char *run_label(int shape);                  // the operator's first stdout line (e.g. 2d/gpu.cu:549)
 
 }  // namespace lora
@@ -252,4 +280,7 @@ struct lora_plan {
     int torus_ghost[3] = {0, 0, 0};
     unsigned torus_epoch = 0;
     bool torus_tried = false;  // at torus_epoch: the answer was already "no" (grid too small, no fused kernel, no memory)
+    // the reductions' records (reduce.cpp): one per workgroup and the folded one, allocated on first need
+    void *reduce_buf = nullptr;
+    int reduce_device = -1;
 };

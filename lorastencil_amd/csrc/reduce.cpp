@@ -1,0 +1,303 @@
+// reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip) and what is built on them: lora_plan_stats,
+// lora_plan_diff, lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until and its group-A form.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+
+#include "engine.h"
+
+namespace lora {
+
+#define LORA_HIP_TRY(expr)                    \
+    do {                                      \
+        hipError_t e__ = (expr);              \
+        if (e__ != hipSuccess) {              \
+            lora::set_last_error(#expr, e__); \
+            return LORA_EHIP;                 \
+        }                                     \
+    } while (0)
+
+static const int *halo_widths(int ndim) {
+    static const int h1[1] = {4}, h2[2] = {4, 4}, h3[3] = {1, 2, 4};
+    return ndim == 1 ? h1 : (ndim == 2 ? h2 : h3);
+}
+
+// Launch geometry of a box: everything here follows from the dtype, the extents and the box, never from the device or from
+// an earlier call -- which is what makes a reduction return the same bits every time.
+bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a, int &kind, int &groups) {
+    const int *hw = halo_widths(p.ndim);
+    long P[3] = {1, 1, 1};
+    int l[3] = {0, 0, 0}, h[3] = {1, 1, 1};
+    for (int d = 0; d < 3; ++d) {
+        const int sd = d - (3 - p.ndim);
+        if (sd < 0) continue;
+        P[d] = (long) p.dims[sd] + 2 * hw[sd];
+        l[d] = lo[sd];
+        h[d] = hi[sd];
+        if (l[d] < 0 || h[d] > P[d] || h[d] <= l[d]) return false;
+    }
+    // 16-byte pieces wherever rows start on 16 bytes: a 1D array is one row; bf16 rows are a multiple of 8 cells
+    kind = p.dtype == LORA_BF16 ? KIND_BF16X8 : ((p.ndim == 1 || P[2] % 2 == 0) ? KIND_F64X2 : KIND_F64X1);
+    const int C = kind == KIND_BF16X8 ? 8 : (kind == KIND_F64X2 ? 2 : 1);
+    a.q0 = l[2] / C;
+    a.ppr = (h[2] + C - 1) / C - a.q0;  // the last piece ends at most at the row's end: rows are whole pieces (1D: n + 5 <= n + 8)
+    a.e1 = h[1] - l[1];
+    a.total = (long) (h[0] - l[0]) * a.e1 * a.ppr;
+    a.col_lo = l[2];
+    a.col_hi = h[2];
+    a.row_stride = P[2];
+    a.plane_stride = P[1] * P[2];
+    a.off0 = ((long) l[0] * P[1] + l[1]) * P[2] + (long) a.q0 * C;
+    // at least eight strides of the lanes per workgroup, at most kReduceMaxGroups workgroups (four per CU of 256)
+    const long S = reduce_threads();
+    long g = (a.total + 8 * S - 1) / (8 * S);
+    g = g < 1 ? 1 : (g > kReduceMaxGroups ? kReduceMaxGroups : g);
+    a.chunk = ((a.total + g - 1) / g + S - 1) / S * S;
+    groups = (int) ((a.total + a.chunk - 1) / a.chunk);
+    const long rows = S / a.ppr, d0 = rows / a.e1;
+    a.dq = (int) (S % a.ppr);
+    a.d1 = (int) (rows % a.e1);
+    a.step_off = d0 * a.plane_stride + a.d1 * a.row_stride + (long) a.dq * C;
+    a.row_carry = a.row_stride - (long) a.ppr * C;
+    a.plane_carry = a.plane_stride - (long) a.e1 * a.row_stride;
+    return true;
+}
+
+namespace {
+
+// the plan's records on the current device (freed by release_run_state)
+int ensure_records(lora_plan *plan, ReduceRecord **out) {
+    int dev = 0;
+    LORA_HIP_TRY(hipGetDevice(&dev));
+    if (plan->reduce_buf && plan->reduce_device != dev) {
+        (void) hipFree(plan->reduce_buf);
+        plan->reduce_buf = nullptr;
+    }
+    if (!plan->reduce_buf) {
+        if (hipMalloc(&plan->reduce_buf, sizeof(ReduceRecord) * (kReduceMaxGroups + 1)) != hipSuccess) {
+            (void) hipGetLastError();
+            plan->reduce_buf = nullptr;
+            return LORA_ENOMEM;
+        }
+        plan->reduce_device = dev;
+    }
+    *out = static_cast<ReduceRecord *>(plan->reduce_buf);
+    return LORA_OK;
+}
+
+// 1 = whole interior or a proper range, 0 = an empty one, < 0 = a bad one
+int resolve_range(const Plan &p, int &begin, int &end) {
+    if (begin == 0 && end == 0) end = p.dims[0];
+    if (begin < 0 || end > p.dims[0] || begin > end) return LORA_EINVAL;
+    return begin < end;
+}
+
+// what every reduction entry checks before it touches the device
+int admit(const void *a, const void *b, hipStream_t s) {
+    if (int rc = check_buffers(a, b)) return rc;
+    if (lora_device_count() <= 0) {
+        set_last_error_text("no HIP device visible");
+        return LORA_ENODEVICE;
+    }
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+        (void) hipGetLastError();
+        st = hipStreamCaptureStatusActive;  // (the legacy stream while another stream captures globally)
+    }
+    if (st != hipStreamCaptureStatusNone) {
+        set_last_error_text("a reduction returns its result to the host: the stream must not be capturing");
+        return LORA_EUNSUPPORTED;
+    }
+    return LORA_OK;
+}
+
+// launches over the outermost range [begin, end) and the folded record back on the host (blocks)
+int reduce_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, ReduceRecord &rec, long long &count,
+                 hipStream_t s) {
+    const Plan &p = plan->p;
+    const int *hw = halo_widths(p.ndim);
+    int lo[3], hi[3];
+    count = 1;
+    for (int d = 0; d < p.ndim; ++d) {
+        lo[d] = hw[d] + (d == 0 ? begin : 0);
+        hi[d] = hw[d] + (d == 0 ? end : p.dims[d]);
+        count *= hi[d] - lo[d];
+    }
+    ReduceArgs a;
+    int kind = 0, groups = 0;
+    if (!reduce_geometry(p, lo, hi, a, kind, groups)) return LORA_EINVAL;
+    ReduceRecord *records = nullptr;
+    if (int rc = ensure_records(plan, &records)) return rc;
+    const hipError_t e = d_b ? launch_reduce_diff(a, kind, groups, d_a, d_b, records, s) : launch_reduce_stats(a, kind, groups, d_a, records, s);
+    if (e != hipSuccess) {
+        set_last_error("reduction kernel launch", e);
+        return LORA_EHIP;
+    }
+    LORA_HIP_TRY(hipMemcpyAsync(&rec, records + kReduceMaxGroups, sizeof rec, hipMemcpyDeviceToHost, s));
+    LORA_HIP_TRY(hipStreamSynchronize(s));
+    return LORA_OK;
+}
+
+const lora_grid_stats kEmptyStats = {HUGE_VAL, -HUGE_VAL, 0.0, 0.0, 0.0, 0, 0};
+
+int diff_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_diff *out, hipStream_t s) {
+    ReduceRecord rec;
+    long long count = 0;
+    if (int rc = reduce_range(plan, d_a, d_b, begin, end, rec, count, s)) return rc;
+    const bool any = rec.f[0] >= 0.0;  // the kernels' "no finite difference" is max_abs = -1
+    *out = {any ? rec.f[0] : 0.0, rec.f[1], rec.f[2], any ? rec.i[0] : -1, count, rec.i[1]};
+    return LORA_OK;
+}
+
+}  // namespace
+}  // namespace lora
+
+using lora::Plan;
+
+extern "C" {
+
+int lora_plan_stats(lora_plan *plan, const void *d_buf, int begin, int end, lora_grid_stats *out, void *stream) {
+    if (!plan || !d_buf || !out) return LORA_EINVAL;
+    const int some = lora::resolve_range(plan->p, begin, end);
+    if (some < 0) return some;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit(d_buf, d_buf, s)) return rc;
+    *out = lora::kEmptyStats;
+    if (!some) return LORA_OK;
+    lora::ReduceRecord rec;
+    if (int rc = lora::reduce_range(plan, d_buf, nullptr, begin, end, rec, out->count, s)) return rc;
+    out->min = rec.f[0];
+    out->max = rec.f[1];
+    out->sum = rec.f[2];
+    out->sum_sq = rec.f[3];
+    out->nonfinite = rec.i[0];
+    // over one set of finite cells the largest magnitude is at the minimum or at the maximum
+    out->abs_max = out->nonfinite < out->count ? std::fmax(std::fabs(out->min), std::fabs(out->max)) : 0.0;
+    return LORA_OK;
+}
+
+int lora_plan_diff(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_diff *out, void *stream) {
+    if (!plan || !d_a || !d_b || !out) return LORA_EINVAL;
+    const int some = lora::resolve_range(plan->p, begin, end);
+    if (some < 0) return some;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit(d_a, d_b, s)) return rc;
+    *out = {0.0, 0.0, 0.0, -1, 0, 0};
+    if (!some) return LORA_OK;
+    return lora::diff_range(plan, d_a, d_b, begin, end, out, s);
+}
+
+void lora_grid_stats_merge(lora_grid_stats *into, const lora_grid_stats *part) {
+    if (!into || !part) return;
+    into->min = part->min < into->min ? part->min : into->min;
+    into->max = part->max > into->max ? part->max : into->max;
+    into->abs_max = part->abs_max > into->abs_max ? part->abs_max : into->abs_max;
+    into->sum += part->sum;
+    into->sum_sq += part->sum_sq;
+    into->count += part->count;
+    into->nonfinite += part->nonfinite;
+}
+
+int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_until *u, lora_until_result *r, void *stream) {
+    if (!plan || !d_buf0 || !d_buf1 || !u || !r || d_buf0 == d_buf1) return LORA_EINVAL;
+    if (u->check_every < 2 || u->check_every % 2 || u->max_times < 0) return LORA_EINVAL;
+    if (u->norm != LORA_NORM_MAX && u->norm != LORA_NORM_RMS) return LORA_EINVAL;
+    if (!(u->tol >= 0.0) || !(u->rtol >= 0.0)) return LORA_EINVAL;  // (a NaN fails both)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit(d_buf0, d_buf1, s)) return rc;
+    const Plan &p = plan->p;
+    *r = {0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}};
+    while (r->times_done + u->check_every <= u->max_times) {
+        // an even run: the level is back in d_buf0, both halos as a fresh run expects them
+        if (int rc = lora_plan_run(plan, d_buf0, d_buf1, u->check_every, stream)) return rc;
+        r->times_done += u->check_every;
+        // the probe: one raw sweep into the buffer whose interior a run leaves unspecified anyway
+        if (p.boundary == LORA_BC_PERIODIC)
+            if (int rc = lora_plan_halo(plan, d_buf0, nullptr, LORA_HALO_WRAP, stream)) return rc;
+        if (int rc = lora_plan_step(plan, d_buf0, d_buf1, stream)) return rc;
+        if (int rc = lora::diff_range(plan, d_buf1, d_buf0, 0, p.dims[0], &r->last, s)) return rc;
+        r->checks += 1;
+        r->residual = u->norm == LORA_NORM_RMS ? std::sqrt(r->last.sum_sq / (double) r->last.count) : r->last.max_abs;
+        if (r->last.nonfinite > 0) {
+            r->diverged = 1;
+            break;
+        }
+        if (r->residual <= u->tol + u->rtol * r->last.a_abs_max) {
+            r->converged = 1;
+            break;
+        }
+    }
+    return LORA_OK;
+}
+
+int lora_run_host_until(int shape, int dtype, const void *in, void *out, const double *params, const int *dims, const lora_until *u,
+                        lora_until_result *r, int quiet, lora_run_info *info) {
+    if (!in || !out || !dims || !u || !r) return LORA_EINVAL;
+    if (u->check_every < 2 || u->check_every % 2 || u->max_times < 0) return LORA_EINVAL;
+    if (lora_device_count() <= 0) {
+        lora::set_last_error_text("no HIP device visible");
+        return LORA_ENODEVICE;
+    }
+    lora_plan *plan = nullptr;
+    int rc = lora_plan_create(&plan, shape, dtype, dims, params);
+    if (rc != LORA_OK) return rc;
+    struct Guard {
+        lora_plan *p;
+        void *b[2] = {nullptr, nullptr};
+        hipStream_t s = nullptr;
+        ~Guard() {
+            for (void *x : b)
+                if (x) (void) hipFree(x);
+            if (s) (void) hipStreamDestroy(s);
+            lora_plan_destroy(p);
+        }
+    } g{plan};
+
+    using clock = std::chrono::steady_clock;
+    const size_t esize = dtype == LORA_BF16 ? 2 : sizeof(double);
+    const size_t bytes = lora_padded_count(shape, dims) * esize;
+    const auto t_total0 = clock::now();
+    LORA_HIP_TRY(hipMalloc(&g.b[0], bytes));
+    LORA_HIP_TRY(hipMalloc(&g.b[1], bytes));
+    LORA_HIP_TRY(hipMemcpy(g.b[0], in, bytes, hipMemcpyHostToDevice));  // whole padded input, halo included
+    LORA_HIP_TRY(hipMemset(g.b[1], 0, bytes));
+    LORA_HIP_TRY(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
+    (void) lora_plan_prepare_run(plan, u->check_every);
+    LORA_HIP_TRY(hipDeviceSynchronize());
+
+    const auto t0 = clock::now();
+    rc = lora_plan_run_until(plan, g.b[0], g.b[1], u, r, g.s);
+    if (rc != LORA_OK) return rc;
+    LORA_HIP_TRY(hipStreamSynchronize(g.s));
+    const auto t1 = clock::now();
+
+    // 1D copies all but the last element (1d/gpu_1r.cu:134); the level is in buffer 0 (times_done is even)
+    LORA_HIP_TRY(hipMemcpy(out, g.b[0], plan->p.ndim == 1 ? bytes - esize : bytes, hipMemcpyDeviceToHost));
+    const auto t_total1 = clock::now();
+
+    double points = 1.0;
+    for (int d = 0; d < plan->p.ndim; ++d) points *= dims[d];
+    const int times = r->times_done, F = lora_shape_gstencil_factor(shape);
+    lora_run_info ri;
+    ri.sweep_seconds = std::chrono::duration<double>(t1 - t0).count();  // the sweeps and their checks
+    ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
+    ri.gstencils = points * times / ri.sweep_seconds / 1e9;
+    ri.gstencils_refconv = ri.gstencils * F;
+    ri.hbm_gbs = points * times * 2.0 * esize / ri.sweep_seconds / 1e9;
+    ri.variant = plan->p.variant;
+    ri.steps_per_launch = plan->p.steps_per_launch;
+    lora::set_last_run_info(ri);
+    if (info) *info = ri;
+    if (!quiet) {
+        const double secs = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() / 1e6;
+        std::printf("%s\n", lora::run_label(shape));
+        std::printf("Time = %lld[ms]\n", (long long) std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count());
+        std::printf("GStencil/s = %f\n", points * times * F / secs / 1e9);
+        std::fflush(stdout);
+    }
+    return LORA_OK;
+}
+
+}  // extern "C"

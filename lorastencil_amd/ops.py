@@ -11,7 +11,7 @@ Everything computes in the HIP library; there is no Python/CPU implementation he
 from __future__ import annotations
 
 import ctypes
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import numpy as np
 
@@ -196,6 +196,65 @@ def from_bf16(a: np.ndarray) -> np.ndarray:
     return out
 
 
+# ---- reductions on the device: what lora_plan_stats / lora_plan_diff / lora_plan_run_until return -----------------
+class GridStats(NamedTuple):
+    """Statistics of the finite interior cells of a region; ``count`` cells, ``nonfinite`` of them NaN or +-inf."""
+    min: float
+    max: float
+    abs_max: float
+    sum: float
+    sum_sq: float
+    count: int
+    nonfinite: int
+
+
+EMPTY_STATS = GridStats(float("inf"), float("-inf"), 0.0, 0.0, 0.0, 0, 0)
+
+
+class GridDiff(NamedTuple):
+    """Difference d = a - b over a region: ``argmax`` is the lowest PADDED linear index with |d| == max_abs (-1: none)."""
+    max_abs: float
+    sum_sq: float
+    a_abs_max: float
+    argmax: int
+    count: int
+    nonfinite: int
+
+
+class UntilResult(NamedTuple):
+    times_done: int
+    checks: int
+    converged: bool
+    diverged: bool
+    residual: float
+    last: GridDiff
+
+
+NORMS = {"max": _lib.NORM_MAX, "rms": _lib.NORM_RMS}
+
+
+def _tuple_of(cls, c):
+    return cls(*[getattr(c, f) for f in cls._fields])
+
+
+def _until_result(r) -> UntilResult:
+    return UntilResult(r.times_done, r.checks, bool(r.converged), bool(r.diverged), r.residual, _tuple_of(GridDiff, r.last))
+
+
+def _until_arg(tol, rtol, norm, check_every, max_times):
+    n = NORMS[norm] if isinstance(norm, str) else int(norm)
+    return _lib.Until(float(tol), float(rtol), n, int(check_every), int(max_times))
+
+
+def stats_merge(*parts: GridStats) -> GridStats:
+    """The record of the union of disjoint regions (lora_grid_stats_merge), e.g. of the own rows of N slabs."""
+    acc = _lib.GridStats(*EMPTY_STATS)
+    for part in parts:
+        one = _lib.GridStats(*part)
+        _lib.lib().lora_grid_stats_merge(ctypes.byref(acc), ctypes.byref(one))
+    return _tuple_of(GridStats, acc)
+
+
 # ---- group A: the reference's operators on host arrays -------------------------------------------------
 def run_host(shape, in_: np.ndarray, params=None, times: int = 1, quiet: bool = True, out: np.ndarray | None = None):
     """Generic host-buffer operator.  Returns (out, RunInfo).  A uint16 input is taken as bf16 bit patterns."""
@@ -224,6 +283,25 @@ def run_host(shape, in_: np.ndarray, params=None, times: int = 1, quiet: bool = 
     check(_lib.lib().lora_run_host(sid, _p(in_), _p(out), pp, int(times), _dims_arg(dims), int(quiet),
                                    ctypes.byref(info)), f"lora_run_host({SHAPE_NAMES.get(sid, sid)})")
     return out, info
+
+
+def run_host_until(shape, in_: np.ndarray, tol: float, params=None, rtol: float = 0.0, norm="max", check_every: int = 60,
+                   max_times: int = 6000, quiet: bool = True):
+    """run_host with the run-until-steady driver (lora_run_host_until).  Returns (out, UntilResult, RunInfo)."""
+    sid = shape_id(shape)
+    bf16 = in_.dtype == np.uint16
+    in_ = np.ascontiguousarray(in_) if bf16 else np.ascontiguousarray(in_, dtype=np.float64)
+    h = halo(sid)
+    if in_.ndim != len(h):
+        raise ValueError("input rank does not match the shape")
+    dims = [in_.shape[i] - 2 * h[i] for i in range(in_.ndim)]
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    u, r, info = _until_arg(tol, rtol, norm, check_every, max_times), _lib.UntilResult(), RunInfo()
+    check(_lib.lib().lora_run_host_until(sid, _lib.BF16 if bf16 else _lib.F64, in_.ctypes.data, out.ctypes.data, pp, _dims_arg(dims),
+                                         ctypes.byref(u), ctypes.byref(r), int(quiet), ctypes.byref(info)),
+          f"lora_run_host_until({SHAPE_NAMES.get(sid, sid)})")
+    return out, _until_result(r), info
 
 
 def _operator(cname: str, nd: int):
@@ -410,6 +488,31 @@ class Plan:
         """`times` sweeps ping-ponging from d_buf0; the result is in buffer [times % 2]."""
         check(_lib.lib().lora_plan_run(self._h, _ptr(d_buf0), _ptr(d_buf1), int(times), _stream(stream)),
               "lora_plan_run")
+
+
+    # -- reductions on the device (these block until the result is on the host)
+    def stats(self, d_buf, begin: int = 0, end: int = 0, stream=None) -> GridStats:
+        """Statistics of the interior of ``d_buf`` over the outermost range [begin, end) (0, 0: the whole interior)."""
+        out = _lib.GridStats()
+        check(_lib.lib().lora_plan_stats(self._h, _ptr(d_buf), int(begin), int(end), ctypes.byref(out), _stream(stream)),
+              "lora_plan_stats")
+        return _tuple_of(GridStats, out)
+
+    def diff(self, d_a, d_b, begin: int = 0, end: int = 0, stream=None) -> GridDiff:
+        """Difference of two grids of this plan, d = a - b in fp64, over the outermost range [begin, end)."""
+        out = _lib.GridDiff()
+        check(_lib.lib().lora_plan_diff(self._h, _ptr(d_a), _ptr(d_b), int(begin), int(end), ctypes.byref(out), _stream(stream)),
+              "lora_plan_diff")
+        return _tuple_of(GridDiff, out)
+
+    def run_until(self, d_buf0, d_buf1, tol: float, rtol: float = 0.0, norm="max", check_every: int = 60, max_times: int = 6000,
+                  stream=None) -> UntilResult:
+        """Sweep in runs of ``check_every`` until the residual of one more sweep is <= tol + rtol * max|u| (see
+        lora_plan_run_until); ``d_buf0`` then holds level ``times_done``, bit for bit what ``run(times_done)`` gives."""
+        u, r = _until_arg(tol, rtol, norm, check_every, max_times), _lib.UntilResult()
+        check(_lib.lib().lora_plan_run_until(self._h, _ptr(d_buf0), _ptr(d_buf1), ctypes.byref(u), ctypes.byref(r), _stream(stream)),
+              "lora_plan_run_until")
+        return _until_result(r)
 
 
 def device_count() -> int:
