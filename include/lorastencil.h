@@ -345,6 +345,32 @@ typedef struct lora_grid_diff {
 } lora_grid_diff;
 int lora_plan_stats(lora_plan *plan, const void *d_buf, int begin, int end, lora_grid_stats *out, void *stream);
 int lora_plan_diff(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_diff *out, void *stream);
+/* One sweep's change in a single pass: *out = the lora_grid_diff of a = ONE raw sweep of d_in and b = d_in, over the outermost
+ * interior range [begin, end) -- "how far is this level from a fixed point?", asked of one buffer.  The sweep is exactly what
+ * lora_plan_step_region(plan, d_in, scratch, begin, end) would store (same taps, same order, bf16: the single rounding
+ * included), but the swept level is never written anywhere: the call reads d_in once and writes no grid memory at all.
+ * Ranges as for the reductions (0, 0: the whole interior; begin == end otherwise: the empty record), and begin obeys
+ * lora_plan_region_granularity like lora_plan_step_region.  BLOCKS, like the reductions, and answers their status codes in
+ * their order: LORA_EINVAL for a null pointer or a bad range; LORA_EUNSUPPORTED for a misaligned buffer, a plan without the
+ * kernel, or a stream that is capturing; LORA_ENODEVICE without a device.
+ *   Contract.  max_abs, a_abs_max, argmax, count and nonfinite are BIT FOR BIT what the two calls lora_plan_step_region(plan,
+ *   d_in, scratch, begin, end) and lora_plan_diff(plan, scratch, d_in, begin, end) give, non-finite data included; argmax is
+ *   the lowest padded linear index among equal maxima.  sum_sq sums the same finite d in this kernel's own fixed order: the
+ *   same call gives the same bits every time, whatever the plan's tuning options ("rows_per_thread", "panel_width",
+ *   "nt_store", "z_chunk", "cols_per_lane", ...) -- the launch geometry follows from dtype, extents, tap set and region
+ *   alone, and there are no atomics.  The buffer contract above holds: pieces of at most 16 bytes, nothing outside [base,
+ *   base + lora_plan_padded_bytes) is read, and halo values are read because the stencil needs them but never enter the
+ *   reduction as cells.
+ *   Which plans have the kernel (read-only option "fused_residual": 1 or 0): every 1D plan; 2D plans of the direct variant
+ *   and 3D fp64 plans with an even innermost extent; 3D bf16 plans.  Plans on the one-thread-per-point kernels (odd innermost
+ *   extent) and 2D plans of LORA_VARIANT_MFMA (whose sums run in another order than the direct taps) answer
+ *   LORA_EUNSUPPORTED. */
+int lora_plan_residual(lora_plan *plan, const void *d_in, int begin, int end, lora_grid_diff *out, void *stream);
+/* Test support, no device needed: replays on the host the tile -> workgroup -> cells map of lora_plan_residual's launch over
+ * [begin, end) (csrc/residual_tiles.h).  cover[padded linear index] is incremented once per cell a workgroup would reduce (the
+ * caller zeroes it: lora_padded_count ints): every interior cell of the range must come out 1, every other cell 0.
+ * *workgroups = the launch's size.  LORA_EUNSUPPORTED for a plan without the kernel. */
+int lora_debug_residual_cover(const lora_plan *plan, int begin, int end, int *cover, int *workgroups);
 /* Host only: *into becomes the record of the union of two DISJOINT regions (the own rows of N slabs: lora_plan_stats takes
  * lora_slab_plan, lora_slab_buffer(s, 2) and the own-row range of lora_slab_info as they are).  Start from a record of a
  * region, or from the empty one {+inf, -inf, 0, 0, 0, 0, 0}. */
@@ -355,18 +381,24 @@ void lora_grid_stats_merge(lora_grid_stats *into, const lora_grid_stats *part);
  *   The loop runs while times_done + check_every <= max_times.  Each round:
  *     lora_plan_run(plan, d_buf0, d_buf1, check_every, stream) -- an even run leaves the level in d_buf0 and both halos as a
  *     fresh run expects them;
- *     a PROBE: one raw lora_plan_step from d_buf0 into d_buf1 (under LORA_BC_PERIODIC after lora_plan_halo(..., LORA_HALO_WRAP)
- *     on d_buf0);
- *     diff(a = d_buf1, b = d_buf0) over the whole interior -> `last`; residual = last.max_abs (LORA_NORM_MAX) or
- *     sqrt(last.sum_sq / last.count) (LORA_NORM_RMS).
+ *     a PROBE of one raw sweep's change (under LORA_BC_PERIODIC after lora_plan_halo(..., LORA_HALO_WRAP) on d_buf0) -> `last`:
+ *       under LORA_NORM_MAX on a plan whose option "fused_residual" reads 1: ONE lora_plan_residual on d_buf0 (d_buf1 is not
+ *       touched by the probe);
+ *       otherwise (LORA_NORM_RMS, where sum_sq decides the stop; plans without that kernel): one raw lora_plan_step from
+ *       d_buf0 into d_buf1, then diff(a = d_buf1, b = d_buf0) over the whole interior.
+ *     The two forms agree bit for bit in last.{max_abs, a_abs_max, argmax, count, nonfinite} and so in everything they decide;
+ *     last.sum_sq carries the summation order of the form that ran.  The code picks the form from the plan and the norm.
+ *     residual = last.max_abs (LORA_NORM_MAX) or sqrt(last.sum_sq / last.count) (LORA_NORM_RMS).
  *   Stop with diverged = 1 when last.nonfinite > 0; else with converged = 1 when residual <= tol + rtol * last.a_abs_max;
  *   otherwise continue.
  *   On return d_buf0 holds level times_done, BIT FOR BIT what lora_plan_run(times_done) gives from the same input; d_buf1's
  *   interior is unspecified, as after any run, and its halo is as a run leaves it.  Not converging is not an error: LORA_OK
  *   with converged = 0.  `residual` is for level times_done -> times_done + 1 (+inf if no round ran); checks = rounds done.
- *   Cost per check: ONE single sweep plus ONE diff (about a sweep's bytes, read only) plus ONE synchronise of the host with
- *   the stream -- choose check_every accordingly (a check costs about eight sweeps of a six-sweep launch: 60 adds 12 % to
- *   a star2d1r run at 16384^2, 300 under 3 %).  Blocks like the reductions, and answers their status codes. */
+ *   Cost per check, fused probe: ONE read of the grid (no more than a single sweep's time; DESIGN.md 3.5 has the figures)
+ *   plus ONE synchronise of the host with the stream.  Two-pass probe: ONE single sweep plus ONE diff (about a sweep's
+ *   bytes, read only) plus the synchronise -- about eight sweeps of a six-sweep launch: check_every = 60 adds 12 % to a
+ *   star2d1r run at 16384^2, 300 under 3 %.  Choose check_every accordingly.  Blocks like the reductions, and answers their
+ *   status codes. */
 enum lora_norm { LORA_NORM_MAX = 0, LORA_NORM_RMS = 1 }; /* max |d|, sqrt(sum_sq / count) */
 typedef struct lora_until {
     double tol, rtol;

@@ -202,7 +202,7 @@ const char *kernel_name_3d_bf16_mfma2(const Plan &p);
 
 // ---- reductions over a box of a padded array (kernels_reduce.hip; host side and geometry: reduce.cpp) ----------------
 // The unit one lane loads: 16 bytes (two fp64 cells, eight bf16 cells) or 8 (fp64 rows of odd length).
-enum ReduceKind { KIND_F64X2 = 0, KIND_F64X1 = 1, KIND_BF16X8 = 2 };
+enum ReduceKind { KIND_F64X2 = 0, KIND_F64X1 = 1, KIND_BF16X8 = 2, KIND_CELL = 3 };  // KIND_CELL: no pieces, a record's index is a cell's (the fold of a fused residual)
 constexpr int kReduceMaxGroups = 1024;  // workgroups of a launch at most; record [kReduceMaxGroups] is the folded result
 struct ReduceRecord {  // what a workgroup leaves: stats {min, max, sum, sum_sq | nonfinite}, diff {max_abs, sum_sq, a_abs_max | argmax, nonfinite}
     double f[4];
@@ -226,6 +226,16 @@ bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a,
 hipError_t launch_reduce_stats(const ReduceArgs &a, int kind, int groups, const void *buf, ReduceRecord *partial, hipStream_t s);
 hipError_t launch_reduce_diff(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
                               hipStream_t s);
+hipError_t launch_reduce_fold_cells(int groups, ReduceRecord *partial, hipStream_t s);
+
+// ---- one sweep's change, reduced in the sweep (kernels_residual.hip; tile geometry: residual_tiles.h) -----------------
+struct ResidualTiles;
+// Whether the plan has the fused residual kernel: 1D, the tiled 2D direct-variant and 3D fp64 kernels' plans, 3D bf16.
+inline bool has_fused_residual(const Plan &p) {
+    return p.ndim == 1 || p.dtype == LORA_BF16 || (!p.generic && (p.ndim == 3 || p.variant == LORA_VARIANT_DIRECT));
+}
+// The records of `d = sweep(in) - in` over the tiles of `rt`, one per workgroup into partial[0 .. rt.groups), and the fold.
+hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, ReduceRecord *partial, hipStream_t s);
 
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,

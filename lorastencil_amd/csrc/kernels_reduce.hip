@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "engine.h"
+#include "reduce_device.h"
 
 namespace lora {
 
@@ -32,12 +33,6 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
-constexpr long long kNoIndex = 0x7fffffffffffffffLL;
-
-__device__ __forceinline__ bool finite64(double x) {
-    return (__double_as_longlong(x) & 0x7ff0000000000000LL) != 0x7ff0000000000000LL;
-}
-
 // A piece as loaded (raw) and cell j of it as a double (bf16 -> fp64 is exact: a bf16 is the upper half of an fp32).
 template <int KIND>
 struct PieceOf;
@@ -130,46 +125,6 @@ struct StatsAcc {
         r.i[1] = 0;
     }
 };
-
-// (`idx` is the cell offset of the PIECE that holds the maximum: lanes walk pieces in ascending order and take a piece on a
-// strictly larger maximum, merges prefer the lower offset, and the fold launch finds the cell inside the piece)
-struct DiffAcc {
-    double mx, sq, amax;  // mx = -1 while no finite difference was seen
-    long long idx, nf;
-    __device__ __forceinline__ void init() {
-        mx = -1.0;
-        sq = amax = 0.0;
-        idx = kNoIndex;
-        nf = 0;
-    }
-    __device__ __forceinline__ void merge(double omx, double osq, double oamax, long long oidx, long long onf) {
-        const bool take = omx > mx || (omx == mx && oidx < idx);
-        mx = take ? omx : mx;
-        idx = take ? oidx : idx;
-        sq += osq;
-        amax = oamax > amax ? oamax : amax;
-        nf += onf;
-    }
-    __device__ __forceinline__ void merge_lane(int m) {  // with the state of lane ^ m
-        merge(__shfl_xor(mx, m), __shfl_xor(sq, m), __shfl_xor(amax, m), __shfl_xor(idx, m), __shfl_xor(nf, m));
-    }
-    __device__ __forceinline__ void merge_record(const ReduceRecord &r) { merge(r.f[0], r.f[1], r.f[2], r.i[0], r.i[1]); }
-    __device__ __forceinline__ void to(ReduceRecord &r) const {
-        r.f[0] = mx;
-        r.f[1] = sq;
-        r.f[2] = amax;
-        r.f[3] = 0.0;
-        r.i[0] = idx;
-        r.i[1] = nf;
-    }
-};
-
-// a wave's 64 states into every lane, always in the same order; sums commute bit for bit, so both sides of a pair agree
-template <typename ACC>
-__device__ __forceinline__ void wave_reduce(ACC &acc) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) acc.merge_lane(m);
-}
 
 template <int KIND>
 __device__ __forceinline__ void reduce_piece(StatsAcc &acc, const ReduceArgs &a, const Cursor &c, const typename PieceOf<KIND>::Raw &ra,
@@ -302,8 +257,9 @@ __device__ __forceinline__ void resolve(DiffAcc &acc, const ReduceArgs &a, int k
         resolve_cell<KIND_F64X2>(acc, a, pa, pb);
     else if (kind == KIND_F64X1)
         resolve_cell<KIND_F64X1>(acc, a, pa, pb);
-    else
+    else if (kind == KIND_BF16X8)
         resolve_cell<KIND_BF16X8>(acc, a, pa, pb);
+    // (KIND_CELL: the records carry the cell's own index -- grid `a` of a fused residual is not in memory to be re-read)
 }
 
 
@@ -347,6 +303,13 @@ hipError_t launch_reduce_stats(const ReduceArgs &a, int kind, int groups, const 
 hipError_t launch_reduce_diff(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
                               hipStream_t s) {
     return launch<DiffAcc, true>(a, kind, groups, buf_a, buf_b, partial, s);
+}
+
+// the fold alone, over difference records that carry cell indices (kernels_residual.hip)
+hipError_t launch_reduce_fold_cells(int groups, ReduceRecord *partial, hipStream_t s) {
+    hipLaunchKernelGGL(combine_kernel<DiffAcc>, dim3(1), dim3(64), 0, s, partial, groups, ReduceArgs{}, (int) KIND_CELL,
+                       (const void *) nullptr, (const void *) nullptr);
+    return hipGetLastError();
 }
 
 }  // namespace lora

@@ -436,6 +436,7 @@ struct Option {
     Check check;
     int n;
     int v[4];
+    int (*derived)(const Plan &) = nullptr;  // READ_ONLY keys that are no field: computed from the plan on every read
 };
 constexpr Option flag(const char *name, int Plan::*f) { return {name, f, f, FLAG, 0, {}}; }
 constexpr Option range(const char *name, int Plan::*f, int lo, int hi) { return {name, f, f, RANGE, 2, {lo, hi}}; }
@@ -484,6 +485,8 @@ const Option kOptions[] = {
     read_only("variant", &Plan::variant),
     read_only("fused_eval", &Plan::fused_eval),
     read_only("boundary", &Plan::boundary),
+    // whether lora_plan_residual has a kernel for this plan (no part of the kernel signature or of the resolved state)
+    {"fused_residual", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_fused_residual(q) ? 1 : 0; }},
 };
 
 const Option *find_option(const char *key) {
@@ -688,7 +691,7 @@ int lora_plan_get_option(const lora_plan *plan, const char *key, int *value) {
 #ifndef LORA_DIAGNOSTICS
     if (o->check == lora::ABLATE) return LORA_EINVAL;
 #endif
-    *value = plan->p.*(o->get);
+    *value = o->derived ? o->derived(plan->p) : plan->p.*(o->get);
     return LORA_OK;
 }
 

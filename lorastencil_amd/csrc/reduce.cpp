@@ -1,5 +1,5 @@
 // reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip) and what is built on them: lora_plan_stats,
-// lora_plan_diff, lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until and its group-A form.
+// lora_plan_diff, lora_plan_residual (kernels_residual.hip), lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until and its group-A form.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "engine.h"
+#include "residual_tiles.h"
 
 namespace lora {
 
@@ -151,6 +152,33 @@ int diff_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, int
     return LORA_OK;
 }
 
+// one raw sweep of d_in against d_in over [begin, end) (a proper range of a plan that has the kernel): the folded record (blocks)
+int residual_range(lora_plan *plan, const void *d_in, int begin, int end, lora_grid_diff *out, hipStream_t s) {
+    const Plan &p = plan->p;
+    ResidualTiles rt;
+    if (!residual_tiles_setup(rt, p, begin, end)) return LORA_EINVAL;
+    ReduceRecord *records = nullptr;
+    if (int rc = ensure_records(plan, &records)) return rc;
+    const hipError_t e = launch_residual(p, rt, d_in, records, s);
+    if (e != hipSuccess) {
+        set_last_error("residual kernel launch", e);
+        return LORA_EHIP;
+    }
+    ReduceRecord rec;
+    LORA_HIP_TRY(hipMemcpyAsync(&rec, records + kReduceMaxGroups, sizeof rec, hipMemcpyDeviceToHost, s));
+    LORA_HIP_TRY(hipStreamSynchronize(s));
+    long long count = end - begin;
+    for (int d = 1; d < p.ndim; ++d) count *= p.dims[d];
+    const bool any = rec.f[0] >= 0.0;
+    *out = {any ? rec.f[0] : 0.0, rec.f[1], rec.f[2], any ? rec.i[0] : -1, count, rec.i[1]};
+    return LORA_OK;
+}
+
+int no_residual_kernel() {
+    set_last_error_text("this plan has no fused residual kernel (odd innermost extent, or the 2D matrix-pipe variant)");
+    return LORA_EUNSUPPORTED;
+}
+
 }  // namespace
 }  // namespace lora
 
@@ -189,6 +217,48 @@ int lora_plan_diff(lora_plan *plan, const void *d_a, const void *d_b, int begin,
     return lora::diff_range(plan, d_a, d_b, begin, end, out, s);
 }
 
+int lora_plan_residual(lora_plan *plan, const void *d_in, int begin, int end, lora_grid_diff *out, void *stream) {
+    if (!plan || !d_in || !out) return LORA_EINVAL;
+    const int some = lora::resolve_range(plan->p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(plan->p)) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_in, d_in)) return rc;
+    if (!lora::has_fused_residual(plan->p)) return lora::no_residual_kernel();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit(d_in, d_in, s)) return rc;
+    *out = {0.0, 0.0, 0.0, -1, 0, 0};
+    if (!some) return LORA_OK;
+    return lora::residual_range(plan, d_in, begin, end, out, s);
+}
+
+// Test support (no device): which cells the workgroups of lora_plan_residual's launch reduce -- residual_tiles.h replayed.
+int lora_debug_residual_cover(const lora_plan *plan, int begin, int end, int *cover, int *workgroups) {
+    if (!plan || !cover) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::resolve_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p)) return LORA_EINVAL;
+    if (!lora::has_fused_residual(p)) return lora::no_residual_kernel();
+    if (workgroups) *workgroups = 0;
+    lora::ResidualTiles rt;
+    if (!some || !lora::residual_tiles_setup(rt, p, begin, end)) return LORA_OK;
+    const int *hw = lora::halo_widths(p.ndim);
+    int halo[3] = {0, 0, 0};
+    long P[3] = {1, 1, 1};
+    for (int d = 3 - p.ndim; d < 3; ++d) {
+        halo[d] = hw[d - (3 - p.ndim)];
+        P[d] = rt.dims[d] + 2L * halo[d];
+    }
+    for (int g = 0; g < rt.groups; ++g)
+        for (long t = g; t < rt.tiles; t += rt.groups) {
+            int o[3], n[3];
+            lora::residual_tile_box(rt, t, o, n);
+            for (int z = o[0]; z < o[0] + n[0]; ++z)
+                for (int y = o[1]; y < o[1] + n[1]; ++y)
+                    for (int x = o[2]; x < o[2] + n[2]; ++x) cover[((z + halo[0]) * P[1] + (y + halo[1])) * P[2] + (x + halo[2])] += 1;
+        }
+    if (workgroups) *workgroups = rt.groups;
+    return LORA_OK;
+}
+
 void lora_grid_stats_merge(lora_grid_stats *into, const lora_grid_stats *part) {
     if (!into || !part) return;
     into->min = part->min < into->min ? part->min : into->min;
@@ -209,15 +279,23 @@ int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_
     if (int rc = lora::admit(d_buf0, d_buf1, s)) return rc;
     const Plan &p = plan->p;
     *r = {0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}};
+    // under the max norm every deciding field of the fused residual is bit for bit the two-pass probe's; sum_sq -- the RMS
+    // norm's -- is summed in another order there, so that norm keeps the two passes
+    const bool fused = u->norm == LORA_NORM_MAX && lora::has_fused_residual(p);
     while (r->times_done + u->check_every <= u->max_times) {
         // an even run: the level is back in d_buf0, both halos as a fresh run expects them
         if (int rc = lora_plan_run(plan, d_buf0, d_buf1, u->check_every, stream)) return rc;
         r->times_done += u->check_every;
-        // the probe: one raw sweep into the buffer whose interior a run leaves unspecified anyway
+        // the probe: one raw sweep's change -- reduced inside the sweep where the plan has that kernel, else the sweep into the
+        // buffer whose interior a run leaves unspecified anyway and the difference of the two
         if (p.boundary == LORA_BC_PERIODIC)
             if (int rc = lora_plan_halo(plan, d_buf0, nullptr, LORA_HALO_WRAP, stream)) return rc;
-        if (int rc = lora_plan_step(plan, d_buf0, d_buf1, stream)) return rc;
-        if (int rc = lora::diff_range(plan, d_buf1, d_buf0, 0, p.dims[0], &r->last, s)) return rc;
+        if (fused) {
+            if (int rc = lora::residual_range(plan, d_buf0, 0, p.dims[0], &r->last, s)) return rc;
+        } else {
+            if (int rc = lora_plan_step(plan, d_buf0, d_buf1, stream)) return rc;
+            if (int rc = lora::diff_range(plan, d_buf1, d_buf0, 0, p.dims[0], &r->last, s)) return rc;
+        }
         r->checks += 1;
         r->residual = u->norm == LORA_NORM_RMS ? std::sqrt(r->last.sum_sq / (double) r->last.count) : r->last.max_abs;
         if (r->last.nonfinite > 0) {

@@ -505,6 +505,15 @@ class Plan:
               "lora_plan_diff")
         return _tuple_of(GridDiff, out)
 
+    def residual(self, d_in, begin: int = 0, end: int = 0, stream=None) -> GridDiff:
+        """The change of ONE raw sweep of ``d_in``, d = sweep(d_in) - d_in, over the outermost range [begin, end), reduced inside
+        the sweep: the grid is read once and nothing is written.  The exact fields equal ``step_region`` into a second buffer
+        followed by ``diff``; plans without the kernel (option "fused_residual" == 0) raise LORA_EUNSUPPORTED."""
+        out = _lib.GridDiff()
+        check(_lib.lib().lora_plan_residual(self._h, _ptr(d_in), int(begin), int(end), ctypes.byref(out), _stream(stream)),
+              "lora_plan_residual")
+        return _tuple_of(GridDiff, out)
+
     def run_until(self, d_buf0, d_buf1, tol: float, rtol: float = 0.0, norm="max", check_every: int = 60, max_times: int = 6000,
                   stream=None) -> UntilResult:
         """Sweep in runs of ``check_every`` until the residual of one more sweep is <= tol + rtol * max|u| (see
