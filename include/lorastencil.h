@@ -178,6 +178,29 @@ int lora_plan_set_boundary(lora_plan *plan, int boundary);
 /* Boundary condition given to plans created afterwards on this thread, i.e. also to the host operators of group A
  * (what the CLIs' --bc flag sets).  Returns the previous value. */
 int lora_set_default_boundary(int boundary);
+/* A source term: while `d_source` is set, every application of the plan is u <- S(u) + f on the interior cells of the swept
+ * range -- out = fl(acc + f), where acc has exactly the bits the plan's single sweep without a source stores and + f is one
+ * separate fp64 addition.  f is a caller-owned device array laid out as a padded grid of the plan; its halo cells are never
+ * used, nothing outside [d_source, d_source + lora_plan_padded_bytes) is read, and it is never written.  The plan borrows
+ * the pointer (lora_plan_destroy frees nothing of it); NULL removes the source, after which the plan resolves exactly as
+ * before.  A single source sweep equals "plain sweep, then + f on the interior" bit for bit; a zero source equals no source as
+ * numbers, not necessarily as bits (-0.0 + 0.0 = +0.0).  Halo cells of the output are never written; in a fused launch the
+ * source adds to interior cells of the intermediate level only.
+ *   With a source, option "steps_per_launch" reads 2 for 2D plans of the direct variant with an even innermost extent under
+ * the reference and Dirichlet boundaries (1 if 1 was requested), and 1 for every other plan; the launch entries answer
+ * LORA_EUNSUPPORTED for any other depth.  Option "source" reads 1, "fused_residual" 0: lora_plan_residual answers
+ * LORA_EUNSUPPORTED, lora_plan_run_until probes with a step (which includes the source) and a difference.  A launch whose
+ * d_out is the source is LORA_EINVAL.  A cached graph is dropped (it holds the old pointer).
+ *   LORA_EINVAL for a null plan; LORA_EUNSUPPORTED for a pointer that is not 16-byte aligned, for a LORA_BF16 plan and for a
+ * 2D plan of the LORA_VARIANT_MFMA variant -- and lora_plan_set_variant(plan, LORA_VARIANT_MFMA) on a plan that has a source
+ * answers LORA_EUNSUPPORTED and leaves the plan as it was.  Needs no device: the pointer is only stored. */
+int lora_plan_set_source(lora_plan *plan, const void *d_source);
+/* The source given to the plans of the host operators of group A called afterwards on this thread: a padded HOST array of the
+ * operator's grid (it stays the caller's; NULL = none).  lora_run_host / lora_run_host_dtype / lora_run_host_until for
+ * LORA_F64 upload it beside the grid, outside the timed region; with one set, LORA_BF16 runs, lora_run_host_multi and
+ * lora_run_host_blocks answer LORA_EUNSUPPORTED.  lora_run_info.hbm_gbs then counts 3 x sizeof(T) bytes per point and sweep.
+ * Returns the previous value. */
+const double *lora_set_default_source(const double *padded_host_source);
 /* Normalised-weights mode for plans created afterwards on this thread, i.e. also for the host operators of group A
  * (what the CLIs' --normalize flag sets): the operator's effective taps are divided by their sum, so that runs longer
  * than the fp64 range of the reference's integer taps allows stay finite (box2d3r overflows at step ~129, SURVEY B7;

@@ -36,6 +36,7 @@ from .ops import (  # noqa: F401
     run_host,
     run_host_until,
     separable_3x3x3,
+    set_default_source,
     stats_merge,
     svd_7x7,
     to_bf16,

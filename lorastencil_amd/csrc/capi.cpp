@@ -54,6 +54,8 @@ int check_buffers(const void *a, const void *b) {
 // Otherwise the plan's own kernel family at any depth up to `depth` that it has: 1D the powers of two, 2D the even ones
 // (row-streaming kernel 4 / 2, workgroup-row kernel 6 / 4 / 2), 3D the plan's own and 2.
 static bool has_apps(const Plan &p, int napps, int depth, bool step2) {
+    // a plan with a source has the source kernels only: one application, and two where it resolved to two
+    if (p.source) return step2 ? p.steps_per_launch == 2 : (napps == 1 || (napps == 2 && depth >= 2 && p.steps_per_launch == 2));
     if (step2) return p.ndim != 1 && has_fused_kernels(p);  // (1D has no two-application entry of this kind)
     if (napps == 1) return true;
     if (napps < 2 || napps > depth) return false;
@@ -71,11 +73,14 @@ int launch_apps(const Plan &p, const Apps &a, const void *d_in, void *d_out, hip
     const int g = region_granularity(p);
     auto bad = [&](int begin, int end) { return begin < 0 || end > p.dims[0] || begin > end || begin % g != 0; };
     if (d_in == d_out || bad(b, e) || bad(a.begin2, a.end2)) return LORA_EINVAL;
+    if (p.source && p.source == d_out) return LORA_EINVAL;  // f is read while d_out is written
     const double *in = static_cast<const double *>(d_in);
     double *out = static_cast<double *>(d_out);
     const bool bf16 = p.dtype == LORA_BF16;
     hipError_t err;
-    if (n == 1 && bf16)
+    if (p.source)  // (fp64, never the 2D matrix-pipe variant: lora_plan_set_source)
+        err = n == 1 ? launch_source(p, in, out, b, e, s) : launch_source2(p, in, out, b, e, s);
+    else if (n == 1 && bf16)
         err = launch_3d_bf16(p, d_in, d_out, b, e, s);
     else if (n == 1 && p.generic)
         err = p.ndim == 2 ? launch_2d_generic(p, in, out, b, e, s) : launch_3d_generic(p, in, out, b, e, s);
@@ -108,9 +113,55 @@ int launch_apps(const Plan &p, const Apps &a, const void *d_in, void *d_out, hip
         err = p.stream3_active ? launch_3d_stream(p, 2, in, out, in, 0, b, e, s) : launch_3d_fused2(p, in, out, b, e, s);
     if (err != hipSuccess) {
         set_last_error(n == 1 ? "kernel launch" : "fused kernel launch", err);
+        if (p.source && lora_device_count() <= 0) {
+            g_last_error = "no HIP device visible";
+            return LORA_ENODEVICE;
+        }
         return LORA_EHIP;
     }
     return LORA_OK;
+}
+
+static thread_local const double *g_default_source = nullptr;
+
+// The thread's default source uploaded beside the grid and set on the plan of a host-buffer operator (fp64); freed with it.
+struct HostSource {
+    void *d = nullptr;
+    ~HostSource() {
+        if (d) (void) hipFree(d);
+    }
+};
+static int upload_default_source(lora_plan *plan, size_t bytes, HostSource &hs) {
+    if (!g_default_source) return LORA_OK;
+    if (hipMalloc(&hs.d, bytes) != hipSuccess) {
+        (void) hipGetLastError();
+        hs.d = nullptr;
+        return LORA_ENOMEM;
+    }
+    const hipError_t e = hipMemcpy(hs.d, g_default_source, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_last_error("source upload", e);
+        return LORA_EHIP;
+    }
+    return lora_plan_set_source(plan, hs.d);
+}
+
+int default_source_refused(const char *who) {
+    if (!g_default_source) return LORA_OK;
+    g_last_error = std::string(who) + " takes no source (lora_set_default_source)";
+    return LORA_EUNSUPPORTED;
+}
+
+int attach_default_source(lora_plan *plan, size_t bytes, void **d_source) {
+    HostSource hs;
+    const int rc = upload_default_source(plan, bytes, hs);
+    *d_source = hs.d;  // the caller frees it after the plan's last launch
+    hs.d = nullptr;
+    if (rc != LORA_OK && *d_source) {
+        (void) hipFree(*d_source);
+        *d_source = nullptr;
+    }
+    return rc;
 }
 
 }  // namespace lora
@@ -474,6 +525,7 @@ static void torus_drop(lora_plan *plan) {
 // the extended plan and its buffers, built on first need; nullptr: this plan's periodic runs stay single sweeps
 static lora_plan *torus_prepare(lora_plan *plan) {
     Plan &p = plan->p;
+    if (p.source) return nullptr;  // the extended plan is built from shape and taps: it would drop the source
     if (p.boundary != LORA_BC_PERIODIC || p.torus == 0 || p.steps_per_launch_req == 1 || p.variant != LORA_VARIANT_DIRECT) return nullptr;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) {
@@ -835,9 +887,17 @@ int lora_run_host(int shape, const double *in, double *out, const double *params
     return lora_run_host_dtype(shape, LORA_F64, in, out, params, times, dims, quiet, info);
 }
 
+const double *lora_set_default_source(const double *padded_host_source) {
+    const double *old = lora::g_default_source;
+    lora::g_default_source = padded_host_source;
+    return old;
+}
+
 int lora_run_host_dtype(int shape, int dtype, const void *in, void *out, const double *params, int times,
                         const int *dims, int quiet, lora_run_info *info) {
     if (!in || !out || !dims || times < 0) return LORA_EINVAL;
+    if (dtype == LORA_BF16)
+        if (int rc = lora::default_source_refused("a bf16 run")) return rc;
     if (lora_device_count() <= 0) {
         g_last_error = "no HIP device visible";
         return LORA_ENODEVICE;
@@ -855,10 +915,12 @@ int lora_run_host_dtype(int shape, int dtype, const void *in, void *out, const d
     const size_t esize = (dtype == LORA_BF16) ? 2 : sizeof(double);
     const size_t bytes = count * esize;
     DeviceBuffers dev;
+    lora::HostSource src;  // (declared before the plan's launches, freed after them)
     const auto t_total0 = clock::now();
     LORA_HIP_TRY(hipMalloc(&dev.b[0], bytes));
     LORA_HIP_TRY(hipMalloc(&dev.b[1], bytes));
     LORA_HIP_TRY(hipMemcpy(dev.b[0], in, bytes, hipMemcpyHostToDevice));  // whole padded input, halo included
+    if (int src_rc = lora::upload_default_source(plan, bytes, src)) return src_rc;  // the thread's default source, beside the grid
     // warm-up (the reference has none): one sweep into buf1, which is then cleared again
     if (times > 0) {
         rc = lora_plan_step(plan, dev.b[0], dev.b[1], nullptr);
@@ -908,7 +970,7 @@ int lora_run_host_dtype(int shape, int dtype, const void *in, void *out, const d
     ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
     ri.gstencils = points * times / ri.sweep_seconds / 1e9;
     ri.gstencils_refconv = ri.gstencils * F;
-    ri.hbm_gbs = points * times * 2.0 * esize / ri.sweep_seconds / 1e9;
+    ri.hbm_gbs = points * times * (plan->p.source ? 3.0 : 2.0) * esize / ri.sweep_seconds / 1e9;  // a source is one more read
     ri.variant = plan->p.variant;
     ri.steps_per_launch = plan->p.steps_per_launch;
     lora::g_last_info = ri;

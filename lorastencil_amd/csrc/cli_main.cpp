@@ -17,6 +17,8 @@
 //   --dtype=bf16       (lorastencil_3d only) store the grid in bf16, accumulate in fp32 (BASELINE config 5; new)
 //   --until=TOL        sweep until max |u(T+1) - u(T)| <= TOL, checked on the device every --check-every=N sweeps (N even,
 //                      default 60: a multiple of every launch depth); time_size becomes the cap (lora_run_host_until)
+//   --source=const:V   every sweep is u <- S(u) + f with f = V on every interior cell (lora_set_default_source); one GPU, fp64
+//   --source=point:V   ... f = V on the interior centre cell dims / 2 and 0 elsewhere
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -134,6 +136,8 @@ int main(int argc, char *argv[]) {
     int gpus = 1;
     int grid[2] = {0, 0};
     bool until = false, gpus_given = false;
+    int source_kind = 0;  // 0 none, 1 const, 2 point
+    double source_value = 0.0;
     lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -166,6 +170,18 @@ int main(int argc, char *argv[]) {
                 return 1;
             }
             until = true;
+        }
+        else if (a.rfind("--source=", 0) == 0) {
+            const std::string v = a.substr(9);
+            const bool is_const = v.rfind("const:", 0) == 0, is_point = v.rfind("point:", 0) == 0;
+            const std::string num = (is_const || is_point) ? v.substr(6) : "";
+            char *rest = nullptr;
+            source_value = std::strtod(num.c_str(), &rest);
+            if (num.empty() || *rest != '\0') {
+                std::cerr << "Invalid argument: --source=const:V or --source=point:V needs a number V.\n";
+                return 1;
+            }
+            source_kind = is_const ? 1 : 2;
         }
         else if (a.rfind("--check-every=", 0) == 0) {
             try {
@@ -221,6 +237,11 @@ int main(int argc, char *argv[]) {
         return 1;
     }
 
+    if (source_kind && (gpus_given || grid[0] > 0 || check || bf16)) {
+        std::cerr << "--source runs on one GPU in fp64 and the self-check knows no source: not with --gpus, --grid, --check or --dtype=bf16\n";
+        return 1;
+    }
+
     double params[49];
     lora_default_params(shape, params);
 
@@ -246,6 +267,29 @@ int main(int argc, char *argv[]) {
     const size_t count = lora_padded_count(shape, dims);
     std::vector<double> matrix(count, 0.0), output(count, 0.0);
     fill_input(matrix, shape, dims, fill);
+
+    // the source term: a padded grid like the input, zero outside the interior (halo cells of f are never used)
+    std::vector<double> source;
+    if (source_kind) {
+        source.assign(count, 0.0);
+        const int h[3] = {kDim == 1 ? 4 : (kDim == 2 ? 4 : 1), kDim == 2 ? 4 : 2, 4};  // halo widths, outermost first
+        size_t ext[3] = {1, 1, 1}, ld[3] = {1, 1, 1};
+        for (int d = 0; d < kDim; ++d) ext[d] = (size_t) dims[d] + 2 * h[d];
+        for (int d = kDim - 2; d >= 0; --d) ld[d] = ld[d + 1] * ext[d + 1];
+        auto at = [&](int i, int j, int k) -> double & {
+            const int x[3] = {i, j, k};
+            size_t off = 0;
+            for (int d = 0; d < kDim; ++d) off += (size_t) (x[d] + h[d]) * ld[d];
+            return source[off];
+        };
+        if (source_kind == 2)
+            at(dims[0] / 2, kDim > 1 ? dims[1] / 2 : 0, kDim > 2 ? dims[2] / 2 : 0) = source_value;
+        else
+            for (int i = 0; i < dims[0]; ++i)
+                for (int j = 0; j < (kDim > 1 ? dims[1] : 1); ++j)
+                    for (int k = 0; k < (kDim > 2 ? dims[2] : 1); ++k) at(i, j, k) = source_value;
+        lora_set_default_source(source.data());
+    }
 
     if (check && (custom_bc || normalize)) {
         std::cerr << "--check compares with the reference's boundary behaviour and taps; ignored with --bc / --normalize\n";
@@ -333,6 +377,8 @@ int main(int argc, char *argv[]) {
                     reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
                     how.check_every);
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
+    if (extra && source_kind)
+        std::printf("Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {
         lora_run_info ri;
         if (lora_last_run_info(&ri) == LORA_OK && ri.sweep_seconds > 0) {

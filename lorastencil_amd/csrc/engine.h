@@ -79,6 +79,7 @@ struct Plan : Resolved {
     bool generic = false;  // odd innermost extent: rows are only 8-byte aligned, the tiled kernels do not apply
     int boundary = LORA_BC_REFERENCE;  // what halo cells hold between sweeps (lora_plan_set_boundary)
     unsigned epoch = 0;   // bumped by every change of taps / options: invalidates a cached graph
+    const void *source = nullptr;  // lora_plan_set_source: the caller's padded grid f of u <- S(u) + f (borrowed; nullptr = none)
     // tuning knobs (lora_plan_set_option; plan.cpp: kOptions)
     int rows_per_thread = 8;  // 2D direct: output rows per lane (tile height = 4x this)
     int panel_width = 32;     // 2D: tile columns per L2 panel of the block->tile map
@@ -231,11 +232,24 @@ hipError_t launch_reduce_fold_cells(int groups, ReduceRecord *partial, hipStream
 // ---- one sweep's change, reduced in the sweep (kernels_residual.hip; tile geometry: residual_tiles.h) -----------------
 struct ResidualTiles;
 // Whether the plan has the fused residual kernel: 1D, the tiled 2D direct-variant and 3D fp64 kernels' plans, 3D bf16.
+// A plan that carries a source has none (a fused residual with a source is not built).
 inline bool has_fused_residual(const Plan &p) {
-    return p.ndim == 1 || p.dtype == LORA_BF16 || (!p.generic && (p.ndim == 3 || p.variant == LORA_VARIANT_DIRECT));
+    return !p.source && (p.ndim == 1 || p.dtype == LORA_BF16 || (!p.generic && (p.ndim == 3 || p.variant == LORA_VARIANT_DIRECT)));
 }
 // The records of `d = sweep(in) - in` over the tiles of `rt`, one per workgroup into partial[0 .. rt.groups), and the fold.
 hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, ReduceRecord *partial, hipStream_t s);
+
+// ---- sweeps with a source term, out = fl(acc + f) (kernels_source.hip: one application; kernels_2d_source.hip: two, 2D) -----
+// Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
+hipError_t launch_source(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
+hipError_t launch_source2(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
+const char *source_kernel_name(const Plan &p);
+const char *source2_kernel_name(const Plan &p);
+// Whether a plan with a source fuses two applications per launch: 2D, direct variant, even innermost extent, reference or
+// Dirichlet boundary, unless single sweeps were asked for.  Every other plan with a source runs single sweeps.
+inline bool source_fuses_two(const Plan &p) {
+    return p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT && !p.generic && p.boundary != LORA_BC_PERIODIC && p.steps_per_launch_req != 1;
+}
 
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,
@@ -265,6 +279,8 @@ void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
 void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus, reduction records)
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
+int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
+int attach_default_source(lora_plan *plan, size_t bytes, void **d_source);  // capi.cpp: upload the thread's default source (if any) and set it on the plan; *d_source is the caller's to hipFree
 const char *run_label(int shape);                  // the operator's first stdout line (e.g. 2d/gpu.cu:549)
 
 }  // namespace lora

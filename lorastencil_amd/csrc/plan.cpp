@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -407,6 +408,17 @@ static void resolve_3d(Plan &p) {
                                                       : kernel_name_3d_fused2(p);
 }
 
+// A plan that carries a source (lora_plan_set_source) runs the source kernels and nothing else: two applications per launch
+// where source_fuses_two says so, single sweeps otherwise.  Everything a fused family of the plain sweeps resolved is switched
+// off again, so that no predicate finds a kernel the plan will not run; the tap set and the taps' factor forms stay.
+static void resolve_source(Plan &p) {
+    p.steps_per_launch = source_fuses_two(p) ? 2 : 1;
+    p.wg_active = 0;
+    p.stream3_active = 0;
+    p.lanes3_active = 0;
+    p.kernel_name = p.steps_per_launch == 2 ? source2_kernel_name(p) : source_kernel_name(p);
+}
+
 void plan_refresh(Plan &p) {
     ++p.epoch;
     static_cast<Resolved &>(p) = Resolved{};  // nothing a refresh derives outlives the next one
@@ -416,6 +428,7 @@ void plan_refresh(Plan &p) {
         resolve_2d(p);
     else
         resolve_3d(p);
+    if (p.source) resolve_source(p);
 }
 
 // ---- options: one row per key -------------------------------------------------------------------------------------------
@@ -487,6 +500,8 @@ const Option kOptions[] = {
     read_only("boundary", &Plan::boundary),
     // whether lora_plan_residual has a kernel for this plan (no part of the kernel signature or of the resolved state)
     {"fused_residual", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_fused_residual(q) ? 1 : 0; }},
+    // whether the plan carries a source (lora_plan_set_source)
+    {"source", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return q.source ? 1 : 0; }},
 };
 
 const Option *find_option(const char *key) {
@@ -633,6 +648,10 @@ int lora_plan_set_variant(lora_plan *plan, int variant) {
     if (!plan) return LORA_EINVAL;
     if (variant == LORA_VARIANT_AUTO) variant = LORA_VARIANT_DIRECT;
     if (variant != LORA_VARIANT_DIRECT && variant != LORA_VARIANT_MFMA) return LORA_EINVAL;
+    if (variant == LORA_VARIANT_MFMA && plan->p.source) {
+        lora::set_last_error_text("a plan with a source has no matrix-pipe kernels: remove the source first");
+        return LORA_EUNSUPPORTED;
+    }
     if (variant == LORA_VARIANT_MFMA && plan->p.ndim == 3) {
         // bf16 box taps: in-plane passes on v_mfma_f32_16x16x32_bf16 (kernels_3d_bf16_mfma.hip)
         if (!lora::mfma3_applies(plan->p)) {
@@ -647,6 +666,28 @@ int lora_plan_set_variant(lora_plan *plan, int variant) {
     }
     plan->p.variant = variant;
     lora::plan_refresh(plan->p);
+    return LORA_OK;
+}
+
+int lora_plan_set_source(lora_plan *plan, const void *d_source) {
+    if (!plan) return LORA_EINVAL;
+    Plan &p = plan->p;
+    if (d_source) {
+        if (reinterpret_cast<uintptr_t>(d_source) & 15) {
+            lora::set_last_error_text("device buffers must be 16-byte aligned");
+            return LORA_EUNSUPPORTED;
+        }
+        if (p.dtype == LORA_BF16) {
+            lora::set_last_error_text("bf16 plans take no source");
+            return LORA_EUNSUPPORTED;
+        }
+        if (p.ndim == 2 && p.variant == LORA_VARIANT_MFMA) {
+            lora::set_last_error_text("the 2D matrix-pipe variant takes no source");
+            return LORA_EUNSUPPORTED;
+        }
+    }
+    p.source = d_source;  // borrowed: the plan owns no grid memory
+    lora::plan_refresh(p);  // bumps the epoch: a cached graph holds the old pointer
     return LORA_OK;
 }
 
@@ -748,6 +789,14 @@ const char *lora_plan_kernel_signature(const lora_plan *plan) {
         std::snprintf(buf, sizeof buf, "taps=%d,zc=%d,fzc=%d,bc=%d", p.tapset, p.z_chunk, p.fused_z_chunk, p.boundary);
     else if (p.ndim == 1)
         std::snprintf(buf, sizeof buf, "k=%d", p.steps_per_launch);
+    if (p.source) {  // the source kernels: their geometry follows dtype, extents, tap set and boundary alone
+        if (p.ndim == 1)
+            std::snprintf(buf, sizeof buf, "src=1");
+        else if (k == "stencil2d_source2_kernel")
+            std::snprintf(buf, sizeof buf, "taps=%d,k=2,bc=%d,src=1", p.tapset, p.boundary);
+        else
+            std::snprintf(buf, sizeof buf, "taps=%d,src=1", p.tapset);
+    }
     sig = k + "[" + buf + "]";
     return sig.c_str();
 }

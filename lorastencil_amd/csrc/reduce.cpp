@@ -321,11 +321,18 @@ int lora_run_host_until(int shape, int dtype, const void *in, void *out, const d
     lora_plan *plan = nullptr;
     int rc = lora_plan_create(&plan, shape, dtype, dims, params);
     if (rc != LORA_OK) return rc;
+    if (dtype == LORA_BF16)
+        if (int src_rc = lora::default_source_refused("a bf16 run")) {
+            lora_plan_destroy(plan);
+            return src_rc;
+        }
     struct Guard {
         lora_plan *p;
         void *b[2] = {nullptr, nullptr};
         hipStream_t s = nullptr;
+        void *src = nullptr;
         ~Guard() {
+            if (src) (void) hipFree(src);
             for (void *x : b)
                 if (x) (void) hipFree(x);
             if (s) (void) hipStreamDestroy(s);
@@ -341,6 +348,7 @@ int lora_run_host_until(int shape, int dtype, const void *in, void *out, const d
     LORA_HIP_TRY(hipMalloc(&g.b[1], bytes));
     LORA_HIP_TRY(hipMemcpy(g.b[0], in, bytes, hipMemcpyHostToDevice));  // whole padded input, halo included
     LORA_HIP_TRY(hipMemset(g.b[1], 0, bytes));
+    if (int src_rc = lora::attach_default_source(plan, bytes, &g.src)) return src_rc;  // the thread's default source, beside the grid
     LORA_HIP_TRY(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
     (void) lora_plan_prepare_run(plan, u->check_every);
     LORA_HIP_TRY(hipDeviceSynchronize());
@@ -363,7 +371,7 @@ int lora_run_host_until(int shape, int dtype, const void *in, void *out, const d
     ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
     ri.gstencils = points * times / ri.sweep_seconds / 1e9;
     ri.gstencils_refconv = ri.gstencils * F;
-    ri.hbm_gbs = points * times * 2.0 * esize / ri.sweep_seconds / 1e9;
+    ri.hbm_gbs = points * times * (plan->p.source ? 3.0 : 2.0) * esize / ri.sweep_seconds / 1e9;  // a source is one more read
     ri.variant = plan->p.variant;
     ri.steps_per_launch = plan->p.steps_per_launch;
     lora::set_last_run_info(ri);

@@ -753,6 +753,7 @@ int lora_slab_store(lora_slab *s, void *host_global_padded) {
 int lora_run_host_multi(int shape, int dtype, const void *in, void *out, const double *params, int times,
                         const int *dims, int ngpus, int quiet, lora_run_info *info) {
     if (!in || !out || !dims || times < 0 || ngpus < 1) return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("the slab driver")) return rc;  // its slabs build plans of their own: never ignored
     if (ngpus == 1) return lora_run_host_dtype(shape, dtype, in, out, params, times, dims, quiet, info);
     const int ndev = lora_device_count();
     if (ndev <= 0) {
@@ -860,6 +861,7 @@ int lora_run_host_multi(int shape, int dtype, const void *in, void *out, const d
 int lora_run_host_blocks(int shape, int dtype, const void *in, void *out, const double *params, int times, const int *dims,
                          const int *grid, int quiet, lora_run_info *info) {
     if (!in || !out || !dims || !grid || times < 0 || grid[0] < 1 || grid[1] < 1) return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("the block driver")) return rc;  // its blocks build plans of their own: never ignored
     const int n = grid[0] * grid[1];
     const int nd = lora_shape_ndim(shape);
     if (nd != 2 && nd != 3) return LORA_EUNSUPPORTED;

@@ -11,6 +11,7 @@ Everything computes in the HIP library; there is no Python/CPU implementation he
 from __future__ import annotations
 
 import ctypes
+import threading
 from typing import NamedTuple, Sequence
 
 import numpy as np
@@ -256,8 +257,51 @@ def stats_merge(*parts: GridStats) -> GridStats:
 
 
 # ---- group A: the reference's operators on host arrays -------------------------------------------------
-def run_host(shape, in_: np.ndarray, params=None, times: int = 1, quiet: bool = True, out: np.ndarray | None = None):
-    """Generic host-buffer operator.  Returns (out, RunInfo).  A uint16 input is taken as bf16 bit patterns."""
+_default_source = threading.local()  # keeps the array lora_set_default_source points at alive, per thread like the C side
+
+
+def set_default_source(source):
+    """The source term f (a padded float64 host array of the operator's grid, or None) that the host operators called
+    afterwards on this thread sweep with: u <- S(u) + f (lora_set_default_source).  Returns the previous array or None."""
+    old = getattr(_default_source, "array", None)
+    if source is None:
+        _lib.lib().lora_set_default_source(None)
+        _default_source.array = None
+        return old
+    if not (isinstance(source, np.ndarray) and source.dtype == np.float64 and source.flags["C_CONTIGUOUS"]):
+        raise ValueError("the source must be a C-contiguous float64 array")
+    _lib.lib().lora_set_default_source(source.ctypes.data)
+    _default_source.array = source
+    return old
+
+
+class _with_source:
+    """set the thread's default source for one host-operator call, restore the previous one afterwards"""
+
+    def __init__(self, source, padded):
+        if source is not None:
+            source = np.ascontiguousarray(source, dtype=np.float64)
+            if source.shape != tuple(padded):
+                raise ValueError(f"the source must be a padded array of the grid's shape {tuple(padded)}")
+        self.source = source
+
+    def __enter__(self):
+        if self.source is not None:
+            self.old = set_default_source(self.source)
+
+    def __exit__(self, *exc):
+        if self.source is not None:
+            set_default_source(self.old)
+
+
+def run_host(shape, in_: np.ndarray, params=None, times: int = 1, quiet: bool = True, out: np.ndarray | None = None, source=None):
+    """Generic host-buffer operator.  Returns (out, RunInfo).  A uint16 input is taken as bf16 bit patterns.  ``source``: a
+    padded float64 array f of the grid's shape: every sweep is u <- S(u) + f on the interior (fp64 grids)."""
+    with _with_source(source, in_.shape):
+        return _run_host(shape, in_, params, times, quiet, out)
+
+
+def _run_host(shape, in_, params, times, quiet, out):
     sid = shape_id(shape)
     if in_.dtype == np.uint16:
         in_ = np.ascontiguousarray(in_)
@@ -286,8 +330,14 @@ def run_host(shape, in_: np.ndarray, params=None, times: int = 1, quiet: bool = 
 
 
 def run_host_until(shape, in_: np.ndarray, tol: float, params=None, rtol: float = 0.0, norm="max", check_every: int = 60,
-                   max_times: int = 6000, quiet: bool = True):
-    """run_host with the run-until-steady driver (lora_run_host_until).  Returns (out, UntilResult, RunInfo)."""
+                   max_times: int = 6000, quiet: bool = True, source=None):
+    """run_host with the run-until-steady driver (lora_run_host_until).  Returns (out, UntilResult, RunInfo).  ``source`` as in
+    run_host."""
+    with _with_source(source, in_.shape):
+        return _run_host_until(shape, in_, tol, params, rtol, norm, check_every, max_times, quiet)
+
+
+def _run_host_until(shape, in_, tol, params, rtol, norm, check_every, max_times, quiet):
     sid = shape_id(shape)
     bf16 = in_.dtype == np.uint16
     in_ = np.ascontiguousarray(in_) if bf16 else np.ascontiguousarray(in_, dtype=np.float64)
@@ -416,6 +466,13 @@ class Plan:
         """"reference" (default: halo never written), "dirichlet" (halo fixed) or "periodic" -- applied by run()."""
         b = BOUNDARIES[boundary] if isinstance(boundary, str) else int(boundary)
         check(_lib.lib().lora_plan_set_boundary(self._h, b), "lora_plan_set_boundary")
+        return self
+
+    def set_source(self, d_source):
+        """The source term f of u <- S(u) + f: a padded device array of this plan (torch CUDA tensor or raw pointer), or None
+        to remove it.  The plan borrows the pointer: keep the array alive while it is set (lora_plan_set_source)."""
+        check(_lib.lib().lora_plan_set_source(self._h, None if d_source is None else _ptr(d_source)), "lora_plan_set_source")
+        self._source = d_source  # keeps a tensor alive as long as the plan points at it
         return self
 
     def set_option(self, key: str, value: int):
