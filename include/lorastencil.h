@@ -147,6 +147,13 @@ struct lora_until;
 struct lora_until_result;
 int lora_run_host_until(int shape, int dtype, const void *in, void *out, const double *params, const int *dims,
                         const struct lora_until *u, struct lora_until_result *r, int quiet, lora_run_info *info);
+/* Leapfrog stepping u(t+1) = S(u(t)) + c u(t-1) on host arrays (fp64; see lora_plan_run_leapfrog in group B): uploads the
+ * padded host arrays `in_cur` (level 0) and `in_prev` (level -1), runs `times` steps with lora_plan_run_leapfrog and copies
+ * level `times` (the whole padded array) to `out`.  Prints the operator's three lines
+ * unless `quiet`; fills lora_run_info with hbm_gbs counting 3 x 8 bytes per point and step and steps_per_launch = the plan's
+ * leapfrog depth.  LORA_EUNSUPPORTED while the thread has a default source (lora_set_default_source). */
+int lora_run_host_leapfrog(int shape, const double *in_cur, const double *in_prev, double *out, const double *params, double c,
+                           int times, const int *dims, int quiet, lora_run_info *info);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -347,6 +354,50 @@ typedef struct lora_run_profile {
 } lora_run_profile;
 int lora_plan_run_profiled(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *stream,
                            lora_run_profile *profile);
+
+/* ---- leapfrog stepping (NEW: two time levels, u(t+1) = S(u(t)) + c u(t-1); c = -1 is the wave equation, -1 < c < 0 a damped
+ * wave, and second-order Chebyshev / Richardson iterations have the same shape).  S is the plan's raw single sweep, as
+ * lora_plan_step applies it.  `c` and the buffers are call arguments, not plan state: no option, kernel name or signature of
+ * the plan changes, no cached graph is touched.
+ *   Status codes, in this order, before anything is dereferenced or launched: LORA_EINVAL for a null plan or pointer, a
+ * non-finite c, a bad range (begin obeys lora_plan_region_granularity), times < 0, and any two of a call's buffers being
+ * equal; LORA_EUNSUPPORTED for a buffer that is not 16-byte aligned and for plans without the kernels (below);
+ * LORA_ENODEVICE when the launch fails for want of a device.  All entries are asynchronous on `stream`. */
+/* 0: the plan has no leapfrog kernel (LORA_BF16 plans, 2D plans of LORA_VARIANT_MFMA, plans that currently carry a source);
+ * 1: single steps (every other plan); 2: also the two-step launch (2D plans of the direct variant with an even innermost
+ * extent).  A function of the plan alone; needs no device. */
+int lora_plan_leapfrog_depth(const lora_plan *plan);
+/* One step, in place: on every interior cell of the swept range d_prev = fl(acc + fl(c * d_prev)), where acc has exactly the
+ * bits the plan's plain single sweep from d_cur stores, c * d_prev is one fp64 multiplication and + one separate fp64
+ * addition (two roundings, never a fused multiply-add).  The new level overwrites the oldest one, so leapfrog needs two
+ * grids.  Of d_prev only the cells that are stored are read, each by the lane that stores it; its halo cells are never
+ * written and never enter a result; d_cur is never written; nothing outside the two padded arrays is touched.  A step equals
+ * "lora_plan_step_region into a spare grid, then + c * d_prev on the interior of the region" bit for bit. */
+int lora_plan_step_leapfrog(lora_plan *plan, const void *d_cur, void *d_prev, double c, void *stream);
+int lora_plan_step_leapfrog_region(lora_plan *plan, const void *d_cur, void *d_prev, double c, int begin, int end, void *stream);
+/* Two steps in one launch (plans of leapfrog depth 2; LORA_EUNSUPPORTED otherwise): d_out1 = S(d_cur) + c d_prev and
+ * d_out2 = S(d_out1) + c d_cur on the interior cells of rows [begin, end); the four buffers are pairwise distinct.  Level-1
+ * cells outside the interior take the value d_prev holds there (the halo of the buffer the level would live in under the
+ * in-place entry), so a launch equals two single steps bit for bit on any data; direct taps in row-major order at both levels
+ * whatever option "lowrank_valu" says.  Halo cells of d_out1 / d_out2 are never written, d_prev and d_cur never at all. */
+int lora_plan_step2_leapfrog(lora_plan *plan, const void *d_prev, const void *d_cur, void *d_out1, void *d_out2, double c,
+                             void *stream);
+int lora_plan_step2_leapfrog_region(lora_plan *plan, const void *d_prev, const void *d_cur, void *d_out1, void *d_out2, double c,
+                                    int begin, int end, void *stream);
+/* `times` steps from d_prev = level -1 and d_cur = level 0: afterwards level `times` is in d_cur if `times` is even and in
+ * d_prev if it is odd, level `times` - 1 in the other buffer; times == 0 touches nothing.  Under LORA_BC_REFERENCE and
+ * LORA_BC_DIRICHLET no halo cell is ever written: each buffer keeps the halo the caller gave it (the same halo in both is a
+ * fixed boundary).  Under LORA_BC_PERIODIC d_cur's halo is wrapped before the first step and every new level after its step
+ * (lora_plan_halo with LORA_HALO_WRAP, with its LORA_EUNSUPPORTED for extents below the halo width); single steps only.
+ *   Plans of depth 2 under the other two boundaries run times / 4 pairs of two-step launches through two scratch grids owned
+ * by the plan -- (prev, cur) -> (s0, s1) -> (prev, cur); their halos are copied from d_prev and d_cur once per run; they are
+ * allocated on first need or by lora_plan_prepare_leapfrog and freed with the plan -- and times % 4 single steps after them;
+ * option "scratch" = 0 means single steps only.  Launches directly (no hipGraph).  Whatever the schedule, the result is bit
+ * for bit that of `times` single steps. */
+int lora_plan_run_leapfrog(lora_plan *plan, void *d_prev, void *d_cur, double c, int times, void *stream);
+/* Allocates now what lora_plan_run_leapfrog(plan, ..., times, ...) would allocate on first need.  Optional and idempotent. */
+int lora_plan_prepare_leapfrog(lora_plan *plan, int times);
+/* The group-A form is lora_run_host_leapfrog (section A). */
 
 /* ---- reductions over grids on the device (NEW: the reference prints its "Result range" from a host loop over the copied-back
  * array).  Both read the interior cells of the outermost range [begin, end) as lora_plan_step_region counts it (begin == end

@@ -34,6 +34,7 @@ from .ops import (  # noqa: F401
     padded_shape,
     reference_input,
     run_host,
+    run_host_leapfrog,
     run_host_until,
     separable_3x3x3,
     set_default_source,

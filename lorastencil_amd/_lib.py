@@ -223,6 +223,15 @@ SIGNATURES = {
     "lora_plan_run_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Until), ctypes.POINTER(UntilResult), _vp]),
     "lora_run_host_until": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _dp, _ip, ctypes.POINTER(Until),
                                            ctypes.POINTER(UntilResult), ctypes.c_int, ctypes.POINTER(RunInfo)]),
+    "lora_plan_leapfrog_depth": (ctypes.c_int, [_vp]),
+    "lora_plan_step_leapfrog": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
+    "lora_plan_step_leapfrog_region": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp]),
+    "lora_plan_step2_leapfrog": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
+    "lora_plan_step2_leapfrog_region": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp]),
+    "lora_plan_run_leapfrog": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_int, _vp]),
+    "lora_plan_prepare_leapfrog": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lora_run_host_leapfrog": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int,
+                                              ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),
     "lora_default_params": (ctypes.c_int, [ctypes.c_int, _dp]),
     "lora_effective_weights": (ctypes.c_int, [ctypes.c_int, _dp, _dp]),

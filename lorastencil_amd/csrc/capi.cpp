@@ -1031,6 +1031,7 @@ void release_run_state(lora_plan *plan) {
     if (plan->scratch) (void) hipFree(plan->scratch);
     plan->scratch = nullptr;
     torus_drop(plan);
+    release_leapfrog_state(plan);
     if (plan->reduce_buf) (void) hipFree(plan->reduce_buf);
     plan->reduce_buf = nullptr;
 }

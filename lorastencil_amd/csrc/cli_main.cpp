@@ -19,6 +19,9 @@
 //                      default 60: a multiple of every launch depth); time_size becomes the cap (lora_run_host_until)
 //   --source=const:V   every sweep is u <- S(u) + f with f = V on every interior cell (lora_set_default_source); one GPU, fp64
 //   --source=point:V   ... f = V on the interior centre cell dims / 2 and 0 elsewhere
+//   --leapfrog[=C]     time_size leapfrog steps u(t+1) = S(u(t)) + C u(t-1) from u(-1) = u(0), i.e. zero initial velocity
+//                      (lora_run_host_leapfrog; default C = -1, the wave equation); one GPU, fp64
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -138,6 +141,8 @@ int main(int argc, char *argv[]) {
     bool until = false, gpus_given = false;
     int source_kind = 0;  // 0 none, 1 const, 2 point
     double source_value = 0.0;
+    bool leapfrog = false;
+    double leapfrog_c = -1.0;
     lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -182,6 +187,18 @@ int main(int argc, char *argv[]) {
                 return 1;
             }
             source_kind = is_const ? 1 : 2;
+        }
+        else if (a == "--leapfrog")
+            leapfrog = true;
+        else if (a.rfind("--leapfrog=", 0) == 0) {
+            const std::string v = a.substr(11);
+            char *rest = nullptr;
+            leapfrog_c = std::strtod(v.c_str(), &rest);
+            if (v.empty() || *rest != '\0' || !std::isfinite(leapfrog_c)) {
+                std::cerr << "Invalid argument: --leapfrog=C needs a finite number C.\n";
+                return 1;
+            }
+            leapfrog = true;
         }
         else if (a.rfind("--check-every=", 0) == 0) {
             try {
@@ -230,6 +247,11 @@ int main(int argc, char *argv[]) {
             std::cerr << "Unknown option: " << a << "\n";
             return 1;
         }
+    }
+
+    if (leapfrog && (gpus_given || grid[0] > 0 || check || until || source_kind || bf16)) {
+        std::cerr << "--leapfrog runs on one GPU in fp64 for a fixed number of steps without a source: not with --gpus, --grid, --check, --until, --source or --dtype=bf16\n";
+        return 1;
     }
 
     if (until && (gpus_given || grid[0] > 0 || check)) {
@@ -304,7 +326,14 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     lora_until_result reached = {};
-    if (until) {
+    if (leapfrog) {
+        // prev = cur: zero initial velocity; the operator prints the reference's three lines itself
+        const int rc = lora_run_host_leapfrog(shape, matrix.data(), matrix.data(), output.data(), params, leapfrog_c, times, dims, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+    } else if (until) {
         // time_size is the cap; the operator prints the reference's three lines for the sweeps it did
         how.max_times = times;
         std::vector<uint16_t> in16, out16;
@@ -377,6 +406,7 @@ int main(int argc, char *argv[]) {
                     reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
                     how.check_every);
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
+    if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
     if (extra && source_kind)
         std::printf("Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {

@@ -251,6 +251,18 @@ inline bool source_fuses_two(const Plan &p) {
     return p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT && !p.generic && p.boundary != LORA_BC_PERIODIC && p.steps_per_launch_req != 1;
 }
 
+// ---- leapfrog steps, prev <- S(cur) + c prev in place (kernels_leapfrog.hip: one step; kernels_2d_leapfrog.hip: two, 2D) ----
+// Picked by the leapfrog entries of leapfrog.cpp and by nothing else.
+hipError_t launch_leapfrog(const Plan &p, const double *cur, double *prev, double c, int begin, int end, hipStream_t s);
+hipError_t launch_leapfrog2(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
+                            int end, hipStream_t s);
+// 0: no leapfrog kernel (bf16, the 2D matrix-pipe variant, a plan with a source); 1: single steps; 2: also the two-step launch
+// (2D, direct variant, even innermost extent).
+inline int leapfrog_depth(const Plan &p) {
+    if (p.dtype != LORA_F64 || p.source || (p.ndim == 2 && p.variant != LORA_VARIANT_DIRECT)) return 0;
+    return p.ndim == 2 && !p.generic ? 2 : 1;
+}
+
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,
 // [begin2, end2) (register-resident 3D kernels only; empty = none).
@@ -277,6 +289,7 @@ int region_granularity(const Plan &p);
 void set_last_error(const char *what, hipError_t e);
 void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
+void release_leapfrog_state(lora_plan *plan);      // leapfrog.cpp: the two scratch grids of lora_plan_run_leapfrog
 void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus, reduction records)
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
@@ -309,4 +322,8 @@ struct lora_plan {
     // the reductions' records (reduce.cpp): one per workgroup and the folded one, allocated on first need
     void *reduce_buf = nullptr;
     int reduce_device = -1;
+    // lora_plan_run_leapfrog's two scratch grids (leapfrog.cpp), allocated on first need
+    void *leap_scratch[2] = {nullptr, nullptr};
+    size_t leap_bytes = 0;
+    int leap_device = -1;
 };

@@ -354,6 +354,24 @@ def _run_host_until(shape, in_, tol, params, rtol, norm, check_every, max_times,
     return out, _until_result(r), info
 
 
+def run_host_leapfrog(shape, cur: np.ndarray, prev: np.ndarray, c: float = -1.0, times: int = 1, params=None, quiet: bool = True):
+    """``times`` leapfrog steps u(t+1) = S(u(t)) + c u(t-1) from the padded float64 host arrays ``cur`` (level 0) and ``prev``
+    (level -1) (lora_run_host_leapfrog).  Returns (level ``times`` as a padded array, RunInfo)."""
+    sid = shape_id(shape)
+    cur = np.ascontiguousarray(cur, dtype=np.float64)
+    prev = np.ascontiguousarray(prev, dtype=np.float64)
+    h = halo(sid)
+    if cur.ndim != len(h) or prev.shape != cur.shape:
+        raise ValueError("cur and prev must be padded arrays of the shape's rank and of one size")
+    dims = [cur.shape[i] - 2 * h[i] for i in range(cur.ndim)]
+    out = np.zeros_like(cur)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    info = RunInfo()
+    check(_lib.lib().lora_run_host_leapfrog(sid, _p(cur), _p(prev), _p(out), pp, float(c), int(times), _dims_arg(dims), int(quiet),
+                                            ctypes.byref(info)), f"lora_run_host_leapfrog({SHAPE_NAMES.get(sid, sid)})")
+    return out, info
+
+
 def _operator(cname: str, nd: int):
     def op(in_, out, params, times, *sizes):
         if len(sizes) != nd:
@@ -546,6 +564,39 @@ class Plan:
         check(_lib.lib().lora_plan_run(self._h, _ptr(d_buf0), _ptr(d_buf1), int(times), _stream(stream)),
               "lora_plan_run")
 
+    # -- leapfrog stepping: u(t+1) = S(u(t)) + c u(t-1), the new level stored over the oldest one
+    @property
+    def leapfrog_depth(self) -> int:
+        """0: no leapfrog kernel; 1: single steps; 2: also the two-step launch (lora_plan_leapfrog_depth)."""
+        return _lib.lib().lora_plan_leapfrog_depth(self._h)
+
+    def step_leapfrog(self, d_cur, d_prev, c: float = -1.0, stream=None):
+        """One step in place: d_prev <- S(d_cur) + c * d_prev on the interior (lora_plan_step_leapfrog)."""
+        check(_lib.lib().lora_plan_step_leapfrog(self._h, _ptr(d_cur), _ptr(d_prev), float(c), _stream(stream)), "lora_plan_step_leapfrog")
+
+    def step_leapfrog_region(self, d_cur, d_prev, c: float, begin: int, end: int, stream=None):
+        check(_lib.lib().lora_plan_step_leapfrog_region(self._h, _ptr(d_cur), _ptr(d_prev), float(c), int(begin), int(end), _stream(stream)),
+              "lora_plan_step_leapfrog_region")
+
+    def step2_leapfrog(self, d_prev, d_cur, d_out1, d_out2, c: float = -1.0, stream=None):
+        """Two steps in one launch: d_out1 = S(d_cur) + c d_prev, d_out2 = S(d_out1) + c d_cur (lora_plan_step2_leapfrog)."""
+        check(_lib.lib().lora_plan_step2_leapfrog(self._h, _ptr(d_prev), _ptr(d_cur), _ptr(d_out1), _ptr(d_out2), float(c), _stream(stream)),
+              "lora_plan_step2_leapfrog")
+
+    def step2_leapfrog_region(self, d_prev, d_cur, d_out1, d_out2, c: float, begin: int, end: int, stream=None):
+        check(_lib.lib().lora_plan_step2_leapfrog_region(self._h, _ptr(d_prev), _ptr(d_cur), _ptr(d_out1), _ptr(d_out2), float(c), int(begin),
+                                                         int(end), _stream(stream)), "lora_plan_step2_leapfrog_region")
+
+    def run_leapfrog(self, d_prev, d_cur, c: float = -1.0, times: int = 1, stream=None):
+        """``times`` steps from d_prev = level -1, d_cur = level 0; level ``times`` ends in d_cur if ``times`` is even, in d_prev if
+        odd (lora_plan_run_leapfrog)."""
+        check(_lib.lib().lora_plan_run_leapfrog(self._h, _ptr(d_prev), _ptr(d_cur), float(c), int(times), _stream(stream)),
+              "lora_plan_run_leapfrog")
+
+    def prepare_leapfrog(self, times: int):
+        """Allocate now what ``run_leapfrog(..., times)`` would allocate on first need (its two scratch grids)."""
+        check(_lib.lib().lora_plan_prepare_leapfrog(self._h, int(times)), "lora_plan_prepare_leapfrog")
+        return self
 
     # -- reductions on the device (these block until the result is on the host)
     def stats(self, d_buf, begin: int = 0, end: int = 0, stream=None) -> GridStats:
