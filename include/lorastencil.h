@@ -154,6 +154,17 @@ int lora_run_host_until(int shape, int dtype, const void *in, void *out, const d
  * leapfrog depth.  LORA_EUNSUPPORTED while the thread has a default source (lora_set_default_source). */
 int lora_run_host_leapfrog(int shape, const double *in_cur, const double *in_prev, double *out, const double *params, double c,
                            int times, const int *dims, int quiet, lora_run_info *info);
+/* The Chebyshev semi-iteration for u = S(u) + f on host arrays (fp64; see lora_plan_run_chebyshev_until in group B): uploads
+ * the padded host array `in` as BOTH levels and `source` (a padded host array of f, or NULL: none) beside it, runs `times` steps
+ * of lora_plan_run_leapfrog_src with lora_chebyshev_coeffs(rho, 1, times) -- or, with `u` not NULL, lora_plan_run_chebyshev_until
+ * (`times` is then ignored, `r` must not be NULL) -- and copies the newest level (the whole padded array) to `out`.  With
+ * u == NULL, `r` may be NULL; if it is not, r->times_done = times.  Prints the operator's three lines unless `quiet`; fills
+ * lora_run_info with hbm_gbs counting 4 x 8 bytes per point and step with a source and 3 x 8 without, and steps_per_launch = the
+ * plan's leapfrog depth; the timed region holds the steps and their probes.  LORA_EINVAL unless 0 <= rho < 1;
+ * LORA_EUNSUPPORTED while the thread has a default source (lora_set_default_source): the source is an argument here. */
+int lora_run_host_chebyshev(int shape, const double *in, const double *source, double *out, const double *params, double rho,
+                            int times, const struct lora_until *u, struct lora_until_result *r, const int *dims, int quiet,
+                            lora_run_info *info);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -399,6 +410,53 @@ int lora_plan_run_leapfrog(lora_plan *plan, void *d_prev, void *d_cur, double c,
 int lora_plan_prepare_leapfrog(lora_plan *plan, int times);
 /* The group-A form is lora_run_host_leapfrog (section A). */
 
+/* ---- leapfrog steps with a source and a scale (NEW): u+ = a (S(u) + f) + c u-.  a = 1, c = -1 is a forced wave equation; per-step
+ * a = w(k), c = 1 - w(k) is the Chebyshev semi-iteration below.  `f` (d_f: a padded device grid of the plan, or NULL for none),
+ * `a`, `c` and the buffers are call arguments, not plan state: no option, kernel name, signature or leapfrog depth of the plan
+ * changes.  The plans are exactly those of lora_plan_leapfrog_depth; in particular a plan on which lora_plan_set_source was
+ * called is refused with LORA_EUNSUPPORTED, as the leapfrog entries refuse it.
+ *   Status codes, in this order, before anything is dereferenced or launched: LORA_EINVAL for a null plan or pointer (d_f may
+ * be null), a non-finite a or c, a bad range, times < 0, ncoef < 1, and any two of a call's buffers being equal (d_f included);
+ * LORA_EUNSUPPORTED for a buffer that is not 16-byte aligned and for a refused plan; LORA_ENODEVICE when the launch fails for
+ * want of a device.  Asynchronous on `stream` unless stated. */
+/* One step, in place: on every interior cell of the swept range
+ *     t = fl(acc + f)   (d_f == NULL: t = acc, no addition at all)      d_prev = fl( fl(a * t) + fl(c * d_prev) )
+ * where acc has exactly the bits the plan's plain single sweep of d_cur stores and every other operation is a separate fp64
+ * rounding, never a fused multiply-add.  With d_f == NULL and a == 1 a step equals lora_plan_step_leapfrog bit for bit on
+ * non-NaN data; with d_f it equals "source sweep into a spare grid, then a * spare + c * d_prev as two multiplications and one
+ * addition" bit for bit.  f is read with the store's own addressing and predicate: its halo cells are never used, it is never
+ * written; d_cur is never written; of d_prev only the cells stored are read, each by the lane that stores it; nothing outside
+ * the padded arrays is touched. */
+int lora_plan_step_leapfrog_src(lora_plan *plan, const void *d_cur, void *d_prev, const void *d_f, double a, double c, void *stream);
+int lora_plan_step_leapfrog_src_region(lora_plan *plan, const void *d_cur, void *d_prev, const void *d_f, double a, double c, int begin,
+                                       int end, void *stream);
+/* Two steps in one launch (plans of leapfrog depth 2; LORA_EUNSUPPORTED otherwise): d_out1 = a1 (S(d_cur) + f) + c1 d_prev and
+ * d_out2 = a2 (S(d_out1) + f) + c2 d_cur on the interior cells of rows [begin, end), with the rounding rule above at both
+ * levels; the buffers are pairwise distinct.  Level-1 cells outside the interior take the value d_prev holds there; direct taps
+ * in row-major order at both levels whatever option "lowrank_valu" says: a launch equals two single steps bit for bit on any
+ * data.  Halo cells of d_out1 / d_out2 are never written, d_prev, d_cur and d_f never at all. */
+int lora_plan_step2_leapfrog_src(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1, void *d_out2,
+                                 double a1, double c1, double a2, double c2, void *stream);
+int lora_plan_step2_leapfrog_src_region(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1,
+                                        void *d_out2, double a1, double c1, double a2, double c2, int begin, int end, void *stream);
+/* `times` steps from d_prev = level -1 and d_cur = level 0; step i (0-based) uses a[min(i, ncoef - 1)] and c[min(i, ncoef - 1)]
+ * (ncoef == 1: constant coefficients, the forced wave).  The host arrays are read during the call only; LORA_EINVAL for a
+ * non-finite entry among those that will be used.  Buffer placement, the three boundary modes and the schedule are
+ * lora_plan_run_leapfrog's: times / 4 pairs of two-step launches through the plan's two scratch grids (the same two;
+ * lora_plan_prepare_leapfrog allocates them), times % 4 single steps at the end, single steps only under LORA_BC_PERIODIC and
+ * with option "scratch" = 0, direct launches.  Whatever the schedule, the result is bit for bit that of `times` single steps. */
+int lora_plan_run_leapfrog_src(lora_plan *plan, void *d_prev, void *d_cur, const void *d_f, const double *a, const double *c, int ncoef,
+                               int times, void *stream);
+/* Host only: the Chebyshev schedule for an iteration matrix S whose spectrum lies in [-rho, rho]:  w(1) = 1,
+ * w(2) = 1 / (1 - rho^2 / 2),  w(k+1) = 1 / (1 - rho^2 w(k) / 4).  For step k = first_step + i (steps count from 1) a[i] = w(k)
+ * and c[i] = 1 - w(k); a[0] == 1 and c[0] == 0 exactly for first_step == 1.  The caller supplies rho; for the 5-point Jacobi taps
+ * (1/4 on the four neighbours) on an m x n interior with zero (Dirichlet) halos it is (cos(pi / (m+1)) + cos(pi / (n+1))) / 2.
+ * With it the residual after k steps is at most 2 s^k / (1 + s^2k) of the first, s = rho / (1 + sqrt(1 - rho^2)), for a
+ * symmetric S; rho = 0 gives w = 1 throughout (plain sweeps).  An underestimated rho slows convergence, it does not break it
+ * while rho < 1.  LORA_EINVAL unless 0 <= rho < 1 (NaN included), first_step >= 1, count >= 0. */
+int lora_chebyshev_coeffs(double rho, int first_step, int count, double *a, double *c);
+/* The group-A form is lora_run_host_chebyshev (section A); lora_plan_run_chebyshev_until follows lora_plan_run_until below. */
+
 /* ---- reductions over grids on the device (NEW: the reference prints its "Result range" from a host loop over the copied-back
  * array).  Both read the interior cells of the outermost range [begin, end) as lora_plan_step_region counts it (begin == end
  * == 0: the whole interior; begin == end otherwise: no cell, the empty record), accumulate in fp64, and return the same bits
@@ -484,6 +542,19 @@ typedef struct lora_until_result {
     lora_grid_diff last;
 } lora_until_result;
 int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_until *u, lora_until_result *r, void *stream);
+/* Solve u = S(u) + f by the Chebyshev semi-iteration until the TRUE residual is small.  d_cur is level 0; d_prev may hold any
+ * FINITE values (step 1 has c = 0, and 0 x NaN is NaN); d_f may be NULL.  `u` obeys lora_plan_run_until's rules (even
+ * check_every >= 2, ...); LORA_EINVAL also unless 0 <= rho < 1; the plans and the other status codes are those of
+ * lora_plan_run_leapfrog_src, then the reductions'.  Each round runs check_every steps of lora_plan_run_leapfrog_src with the
+ * schedule's next coefficients (lora_chebyshev_coeffs(rho, times_done + 1, check_every)) and then probes the newest level:
+ * `last` = the lora_grid_diff of a = S(d_cur) + f against b = d_cur over the whole interior, bit for bit in max_abs, a_abs_max,
+ * argmax, count and nonfinite what a source sweep into a spare grid plus lora_plan_diff give.  The probe sweeps into a third
+ * grid owned by the plan (allocated on first need, freed with the plan) and changes neither d_prev nor d_cur.  Stop rule and
+ * result fields are lora_plan_run_until's.  On return d_cur holds level times_done, bit for bit what
+ * lora_plan_run_leapfrog_src(times_done) with the same coefficients gives, and d_prev the level before it.  BLOCKS, and answers
+ * the reductions' status codes.  Cost of a probe: one single sweep with a source plus one difference. */
+int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, const void *d_f, double rho, const lora_until *u,
+                                  lora_until_result *r, void *stream);
 void lora_plan_destroy(lora_plan *plan);
 
 /* ========================================================================================

@@ -18,6 +18,7 @@ from .ops import (  # noqa: F401
     LoraError,
     Plan,
     UntilResult,
+    chebyshev_coeffs,
     default_params,
     device_count,
     effective_weights,
@@ -34,6 +35,7 @@ from .ops import (  # noqa: F401
     padded_shape,
     reference_input,
     run_host,
+    run_host_chebyshev,
     run_host_leapfrog,
     run_host_until,
     separable_3x3x3,

@@ -21,6 +21,9 @@
 //   --source=point:V   ... f = V on the interior centre cell dims / 2 and 0 elsewhere
 //   --leapfrog[=C]     time_size leapfrog steps u(t+1) = S(u(t)) + C u(t-1) from u(-1) = u(0), i.e. zero initial velocity
 //                      (lora_run_host_leapfrog; default C = -1, the wave equation); one GPU, fp64
+//   --chebyshev=RHO    solve u = S(u) + f by the Chebyshev semi-iteration for a spectrum of S inside [-RHO, RHO], 0 <= RHO < 1
+//                      (lora_run_host_chebyshev): time_size steps, or with --until=TOL until the true residual
+//                      max |S(u) + f - u| <= TOL (time_size is the cap); f from --source= when given; one GPU, fp64
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -143,6 +146,8 @@ int main(int argc, char *argv[]) {
     double source_value = 0.0;
     bool leapfrog = false;
     double leapfrog_c = -1.0;
+    bool chebyshev = false;
+    double chebyshev_rho = 0.0;
     lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -200,6 +205,16 @@ int main(int argc, char *argv[]) {
             }
             leapfrog = true;
         }
+        else if (a.rfind("--chebyshev=", 0) == 0) {
+            const std::string v = a.substr(12);
+            char *rest = nullptr;
+            chebyshev_rho = std::strtod(v.c_str(), &rest);
+            if (v.empty() || *rest != '\0' || !(chebyshev_rho >= 0.0 && chebyshev_rho < 1.0)) {
+                std::cerr << "Invalid argument: --chebyshev=RHO needs a number RHO with 0 <= RHO < 1.\n";
+                return 1;
+            }
+            chebyshev = true;
+        }
         else if (a.rfind("--check-every=", 0) == 0) {
             try {
                 size_t used = 0;
@@ -251,6 +266,11 @@ int main(int argc, char *argv[]) {
 
     if (leapfrog && (gpus_given || grid[0] > 0 || check || until || source_kind || bf16)) {
         std::cerr << "--leapfrog runs on one GPU in fp64 for a fixed number of steps without a source: not with --gpus, --grid, --check, --until, --source or --dtype=bf16\n";
+        return 1;
+    }
+
+    if (chebyshev && (gpus_given || grid[0] > 0 || check || leapfrog || bf16)) {
+        std::cerr << "--chebyshev runs on one GPU in fp64 against its own residual: not with --gpus, --grid, --check, --leapfrog or --dtype=bf16\n";
         return 1;
     }
 
@@ -310,7 +330,7 @@ int main(int argc, char *argv[]) {
             for (int i = 0; i < dims[0]; ++i)
                 for (int j = 0; j < (kDim > 1 ? dims[1] : 1); ++j)
                     for (int k = 0; k < (kDim > 2 ? dims[2] : 1); ++k) at(i, j, k) = source_value;
-        lora_set_default_source(source.data());
+        if (!chebyshev) lora_set_default_source(source.data());  // (a Chebyshev run takes its source as an argument)
     }
 
     if (check && (custom_bc || normalize)) {
@@ -329,6 +349,15 @@ int main(int argc, char *argv[]) {
     if (leapfrog) {
         // prev = cur: zero initial velocity; the operator prints the reference's three lines itself
         const int rc = lora_run_host_leapfrog(shape, matrix.data(), matrix.data(), output.data(), params, leapfrog_c, times, dims, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+    } else if (chebyshev) {
+        // both starting levels are the input; with --until time_size is the cap; the operator prints the reference's three lines
+        how.max_times = times;
+        const int rc = lora_run_host_chebyshev(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params,
+                                               chebyshev_rho, times, until ? &how : nullptr, &reached, dims, 0, nullptr);
         if (rc != LORA_OK) {
             std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
             return 1;
@@ -401,14 +430,19 @@ int main(int argc, char *argv[]) {
             break;
     }
 
-    if (extra && until)
+    if (extra && chebyshev) std::printf("Chebyshev: u(k+1) = w(k+1) (S(u(k)) + f) + (1 - w(k+1)) u(k-1), rho = %g, steps = %d\n", chebyshev_rho, reached.times_done);
+    if (extra && until && chebyshev)
+        std::printf("Until: times_done = %d, %s, residual = %g (max |S(u) + f - u|, tol %g, checked every %d steps)\n", reached.times_done,
+                    reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
+                    how.check_every);
+    else if (extra && until)
         std::printf("Until: times_done = %d, %s, residual = %g (max |u(T+1) - u(T)|, tol %g, checked every %d sweeps)\n", reached.times_done,
                     reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
                     how.check_every);
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
     if (extra && source_kind)
-        std::printf("Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
+        std::printf(chebyshev ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {
         lora_run_info ri;
         if (lora_last_run_info(&ri) == LORA_OK && ri.sweep_seconds > 0) {

@@ -263,6 +263,14 @@ inline int leapfrog_depth(const Plan &p) {
     return p.ndim == 2 && !p.generic ? 2 : 1;
 }
 
+// ---- scaled leapfrog steps with a source, prev <- a (S(cur) + f) + c prev (kernels_leapfrog_src.hip: one step;
+// kernels_2d_leapfrog_src.hip: two, 2D).  f is a call argument (nullptr = none), never the plan's source; the plans are those
+// of leapfrog_depth().  Picked by the *_leapfrog_src entries of leapfrog.cpp and by nothing else.
+hipError_t launch_leapfrog_src(const Plan &p, const double *cur, double *prev, const double *f, double a, double c, int begin, int end,
+                               hipStream_t s);
+hipError_t launch_leapfrog2_src(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
+                                double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s);
+
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,
 // [begin2, end2) (register-resident 3D kernels only; empty = none).
@@ -289,8 +297,10 @@ int region_granularity(const Plan &p);
 void set_last_error(const char *what, hipError_t e);
 void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
-void release_leapfrog_state(lora_plan *plan);      // leapfrog.cpp: the two scratch grids of lora_plan_run_leapfrog
+void release_leapfrog_state(lora_plan *plan);      // leapfrog.cpp: the two scratch grids of lora_plan_run_leapfrog[_src], the probe grid of lora_plan_run_chebyshev_until
 void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus, reduction records)
+int admit_reduction(const void *a, const void *b, hipStream_t s);  // reduce.cpp: what every reduction entry checks before it touches the device
+int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_diff over the whole interior, unchecked (blocks)
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
 int attach_default_source(lora_plan *plan, size_t bytes, void **d_source);  // capi.cpp: upload the thread's default source (if any) and set it on the plan; *d_source is the caller's to hipFree
@@ -326,4 +336,8 @@ struct lora_plan {
     void *leap_scratch[2] = {nullptr, nullptr};
     size_t leap_bytes = 0;
     int leap_device = -1;
+    // lora_plan_run_chebyshev_until's probe grid (chebyshev.cpp): S(u) + f of the newest level, allocated on first need
+    void *cheb_probe = nullptr;
+    size_t cheb_bytes = 0;
+    int cheb_device = -1;
 };

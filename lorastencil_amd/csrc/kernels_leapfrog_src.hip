@@ -1,0 +1,585 @@
+// kernels_leapfrog_src.hip -- ONE scaled leapfrog step with a source in place for gfx950 (lora_plan_step_leapfrog_src;
+// DESIGN 3.8): on every interior cell of the swept range
+//     t = fl(acc + f)   (no source: t = acc, no addition at all)        prev = fl(fl(a * t) + fl(c * prev))
+// where `acc` has exactly the bits the plan's single sweep of `cur` stores and every other operation is one separate fp64
+// rounding, never a fused multiply-add.  a = 1 without a source is the leapfrog step of kernels_leapfrog.hip bit for bit;
+// a = 1, c = -1 with one is a forced wave equation; per-step a = w, c = 1 - w is the Chebyshev semi-iteration.
+//
+// Each kernel restates the geometry and the per-point arithmetic of the leapfrog kernel of its family (kernels_leapfrog.hip,
+// which restates the single-sweep kernels), once with a source (SRC) and once without: "no source" is its own instantiation
+// and not "add a zero" (-0.0 + 0.0 changes bits).
+// `prev` is updated IN PLACE: a lane reads of it only the cells it is about to store -- the 16-byte piece (generic kernels and
+// the 1D tail: the cell) at the store's address, under the store's predicate.  `f` is read with the same addressing and
+// predicate: its halo cells are never used, it is never written, `cur` is never written.
+// The geometry is a function of dtype, extents, tap set and region alone: no tuning option moves a cell.
+#include <hip/hip_runtime.h>
+
+#include "device_common.h"
+
+namespace lora {
+
+namespace {
+
+// a * (acc + f) + c * prev, every operation its own rounding: contraction is switched off around the expression
+template <bool SRC>
+__device__ __forceinline__ double leap_src(double acc, double f, double sa, double c, double prev) {
+#pragma clang fp contract(off)
+    double t = acc;
+    if constexpr (SRC) t = acc + f;
+    const double x = sa * t;
+    const double y = c * prev;
+    return x + y;
+}
+
+// the cell / the 16-byte piece of f at an offset the caller's predicate has admitted (no source: no load)
+template <bool SRC>
+__device__ __forceinline__ double src_cell(const double *f, long off) {
+    if constexpr (SRC) return f[off];
+    return 0.0;
+}
+template <bool SRC>
+__device__ __forceinline__ d2 src_piece(const double *f, long off) {
+    if constexpr (SRC) return *reinterpret_cast<const d2 *>(f + off);
+    d2 z;
+    z.x = 0.0;
+    z.y = 0.0;
+    return z;
+}
+
+// ---- 1D ----------------------------------------------------------------------------------------------------------------
+template <bool SRC>
+__global__ __launch_bounds__(256) void stencil1d_leapfrog_src_kernel(const double *__restrict__ in, double *__restrict__ prev,
+                                                                     const double *__restrict__ f, int begin, int end,
+                                                                     const double sa, const double c, const Taps9 W) {
+    const long pair = (long) blockIdx.x * 256 + threadIdx.x;
+    const long i = begin + 2 * pair;  // begin is even (checked on the host)
+    if (i >= end) return;
+    if (i + 1 < end) {
+        const d2 fv = *reinterpret_cast<const d2 *>(prev + i + 4);
+        const d2 sv = src_piece<SRC>(f, i + 4);
+        double win[10];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            const d2 v = *reinterpret_cast<const d2 *>(in + i + 2 * q);
+            win[2 * q] = v.x;
+            win[2 * q + 1] = v.y;
+        }
+        double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            a0 = fma(W.w[t], win[t], a0);
+            a1 = fma(W.w[t], win[t + 1], a1);
+        }
+        d2 r;
+        r.x = leap_src<SRC>(a0, sv.x, sa, c, fv.x);
+        r.y = leap_src<SRC>(a1, sv.y, sa, c, fv.y);
+        *reinterpret_cast<d2 *>(prev + i + 4) = r;
+    } else {
+        // odd tail: one point, scalar loads stay inside the padded arrays
+        double a0 = 0.0;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) a0 = fma(W.w[t], in[i + t], a0);
+        prev[i + 4] = leap_src<SRC>(a0, src_cell<SRC>(f, i + 4), sa, c, prev[i + 4]);
+    }
+}
+
+// ---- 2D, even innermost extent -------------------------------------------------------------------------------------------
+constexpr int kTileW = 128;               // output columns per tile: 64 lanes x 2
+constexpr int kLdsW = kTileW + 8;         // staged columns (halo 3 each side, widened to 4 for alignment)
+constexpr int kChunksPerRow = kLdsW / 2;  // 16-byte chunks per staged row
+constexpr int kRPT = 8;                   // output rows per lane: tiles of 32 x 128
+
+struct ArgsLeapSrc2D {
+    const double *in;
+    double *prev;
+    const double *f;  // the source (nullptr: none, the !SRC instantiations)
+    double sa, c;
+    int ld;         // padded row length n + 8
+    int m, n;       // interior extents
+    int row_begin;  // first interior row of this launch
+    int row_end;    // one past the last interior row of this launch
+    int tiles_x, tiles_y;
+    int panel_w;
+};
+
+template <int TAPSET, bool SRC>
+__global__ __launch_bounds__(256, 3) void stencil2d_leapfrog_src_kernel(const ArgsLeapSrc2D a, const Taps49 W) {
+    constexpr int RPT = kRPT;
+    constexpr int TH = 4 * RPT;
+    constexpr int LH = TH + 6;
+    constexpr int NCHUNK = LH * kChunksPerRow;
+    constexpr int NIT = (NCHUNK + 255) / 256;
+    __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = tid >> 6;
+    int ty, tx;
+    panel_major(xcd_contiguous(blockIdx.x, gridDim.x), a.tiles_x, a.tiles_y, a.panel_w, ty, tx);
+    const int i0 = a.row_begin + ty * TH;  // first interior row of the tile
+    const int j0 = tx * kTileW;            // first interior column of the tile
+    const int col = j0 + 2 * lane;
+
+    // ---- stage the input window: padded rows i0+1 .. i0+TH+6, padded columns j0 .. j0+135; behind its loads, the pieces
+    //      of prev and f this lane's stores will cover (the store's address and predicate) --------------------------------------
+    d2 fv[RPT], sv[RPT];
+    {
+        d2 stage[NIT];
+        const int max_row = a.m + 7;  // last padded row
+        const int max_col = a.n + 6;  // last 16-byte chunk start in a padded row
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int k = tid + it * 256;
+            if (NCHUNK % 256 == 0 || k < NCHUNK) {
+                const int r = k / kChunksPerRow;
+                const int c = k - r * kChunksPerRow;
+                const int gr = min(i0 + 1 + r, max_row);
+                const int gc = min(j0 + 2 * c, max_col);
+                stage[it] = *reinterpret_cast<const d2 *>(a.in + (size_t) gr * a.ld + gc);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            const int row = i0 + wv * RPT + r;
+            fv[r].x = 0.0;
+            fv[r].y = 0.0;
+            sv[r] = fv[r];
+            if (col < a.n && row < a.row_end) {
+                const size_t cell = (size_t) (row + 4) * a.ld + (col + 4);
+                fv[r] = *reinterpret_cast<const d2 *>(a.prev + cell);
+                sv[r] = src_piece<SRC>(a.f, (long) cell);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int k = tid + it * 256;
+            if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(tile + 2 * k) = stage[it];
+        }
+    }
+    __syncthreads();
+
+    // ---- compute: lane owns tile columns 2*lane+4, 2*lane+5 (window 2*lane .. 2*lane+9) ----------
+    double acc0[RPT], acc1[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        acc0[r] = 0.0;
+        acc1[r] = 0.0;
+    }
+    const double *strip = tile + (wv * RPT) * kLdsW + 2 * lane;
+    d2 cur[5], nxt[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) cur[q] = *reinterpret_cast<const d2 *>(strip + 2 * q);
+#pragma unroll
+    for (int j = 0; j < RPT + 6; ++j) {
+        if (j + 1 < RPT + 6) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) nxt[q] = *reinterpret_cast<const d2 *>(strip + (j + 1) * kLdsW + 2 * q);
+        }
+        double win[10];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            win[2 * q] = cur[q].x;
+            win[2 * q + 1] = cur[q].y;
+        }
+        // input row j of the strip is tap row dy = j - r of output row r
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            const int dy = j - r;
+            if (dy >= 0 && dy < 7) {
+#pragma unroll
+                for (int dx = 0; dx < 7; ++dx) {
+                    if (tap_on<TAPSET>(dy, dx)) {
+                        const double wt = W.w[dy * 7 + dx];
+                        acc0[r] = fma(wt, win[dx + 1], acc0[r]);
+                        acc1[r] = fma(wt, win[dx + 2], acc1[r]);
+                    }
+                }
+            }
+        }
+        // pin the partial sums (see stencil2d_direct_kernel)
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            if (j - r >= 0 && j - r < 7) asm volatile("" : "+v"(acc0[r]), "+v"(acc1[r]));
+        }
+        // output row j-6 is complete: a (acc + f) + c prev, store over prev (16 bytes per lane); halo cells are never written
+        if (j >= 6) {
+            const int r = j - 6;
+            const int row = i0 + wv * RPT + r;
+            if (col < a.n && row < a.row_end) {
+                d2 v;
+                v.x = leap_src<SRC>(acc0[r], sv[r].x, a.sa, a.c, fv[r].x);
+                v.y = leap_src<SRC>(acc1[r], sv[r].y, a.sa, a.c, fv[r].y);
+                *reinterpret_cast<d2 *>(a.prev + (size_t) (row + 4) * a.ld + (col + 4)) = v;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 5; ++q) cur[q] = nxt[q];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int TAPSET, bool SRC>
+hipError_t launch_leap2d(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
+                         hipStream_t s) {
+    constexpr int TH = 4 * kRPT;
+    ArgsLeapSrc2D a;
+    a.in = in;
+    a.prev = prev;
+    a.f = f;
+    a.sa = sa;
+    a.c = c;
+    a.m = p.dims[0];
+    a.n = p.dims[1];
+    a.ld = a.n + 8;
+    a.row_begin = begin;
+    a.row_end = end;
+    a.tiles_x = (a.n + kTileW - 1) / kTileW;
+    a.tiles_y = (end - begin + TH - 1) / TH;
+    a.panel_w = a.tiles_x < 32 ? a.tiles_x : 32;  // the block -> tile map only: which workgroup computes a tile
+    Taps49 w;
+    for (int k = 0; k < 49; ++k) w.w[k] = p.w[k];
+    const long nblocks = (long) a.tiles_x * a.tiles_y;
+    if (nblocks <= 0) return hipSuccess;
+    if (nblocks > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((stencil2d_leapfrog_src_kernel<TAPSET, SRC>), dim3((unsigned) nblocks), dim3(256), 0, s, a, w);
+    return hipGetLastError();
+}
+
+// ---- 3D fp64, even innermost extent --------------------------------------------------------------------------------------
+template <int TAPSET>
+__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
+    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
+}
+
+constexpr int kRY = 4;      // rows per lane: columns of 16 rows x 128
+constexpr int kZChunk = 16; // output planes per workgroup
+
+struct ArgsLeapSrc3D {
+    const double *in;
+    double *prev;
+    const double *f;     // the source (nullptr: none, the !SRC instantiations)
+    double sa, c;
+    int h, m, n;         // interior extents
+    int ld;              // padded row length n + 8
+    long plane;          // padded plane size (m + 4) * (n + 8)
+    int z_begin, z_end;  // interior plane range of this launch
+    int zc;              // output planes per workgroup
+    int tiles_x, tiles_y;
+};
+
+// (with a source the four pieces of f per plane do not fit the 128 registers of four workgroups per CU beside the prev pieces:
+// three then, as the 2D kernel has)
+template <int TAPSET, bool SRC>
+__global__ __launch_bounds__(256, SRC ? 3 : 4) void stencil3d_leapfrog_src_kernel(const ArgsLeapSrc3D a, const Taps27 W) {
+    constexpr int RY = kRY;
+    constexpr int TY = 4 * RY;
+    constexpr int LH = TY + 2;
+    constexpr int NCHUNK = LH * kChunksPerRow;
+    constexpr int NIT = (NCHUNK + 255) / 256;
+    __shared__ __attribute__((aligned(16))) double tile[2][LH * kLdsW];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = tid >> 6;
+
+    const int lin = xcd_contiguous(blockIdx.x, gridDim.x);
+    const int per_chunk = a.tiles_x * a.tiles_y;
+    const int chunk = lin / per_chunk;
+    const int rem = lin - chunk * per_chunk;
+    const int ty = rem / a.tiles_x;
+    const int tx = rem - ty * a.tiles_x;
+    const int k0 = a.z_begin + chunk * a.zc;  // first interior plane of the chunk
+    const int i0 = ty * TY;
+    const int j0 = tx * kTileW;
+    const int zc = min(a.zc, a.z_end - k0);   // output planes this workgroup really owns
+    const int nplanes = zc + 2;               // input planes: padded k0 .. k0+zc+1
+
+    long goff[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int k = tid + it * 256;
+        const int r = k / kChunksPerRow;
+        const int c = k - r * kChunksPerRow;
+        const int gr = min(i0 + 1 + r, a.m + 3);  // padded rows i0+1 .. i0+TY+2
+        const int gc = min(j0 + 2 * c, a.n + 6);
+        goff[it] = (long) gr * a.ld + gc;
+    }
+    d2 stage[NIT];
+    auto load_plane = [&](int p) {
+        const double *src = a.in + (long) min(k0 + p, a.h + 1) * a.plane;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            if (NCHUNK % 256 == 0 || tid + it * 256 < NCHUNK) stage[it] = *reinterpret_cast<const d2 *>(src + goff[it]);
+        }
+    };
+    auto write_plane = [&](int buf) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int k = tid + it * 256;
+            if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(&tile[buf][2 * k]) = stage[it];
+        }
+    };
+
+    double acc0[3][RY], acc1[3][RY];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int r = 0; r < RY; ++r) {
+            acc0[s][r] = 0.0;
+            acc1[s][r] = 0.0;
+        }
+
+    const int col = j0 + 2 * lane;
+    const bool col_ok = col < a.n;
+    const int strip_off = (wv * RY) * kLdsW + 2 * lane + 2;  // window = tile cols 2*lane+2 .. 2*lane+7
+    const long cell_off = (long) (i0 + wv * RY + 2) * a.ld + (col + 4);
+    double *const prev_col = a.prev + cell_off;
+
+    load_plane(0);
+    write_plane(0);
+    __syncthreads();
+
+    auto consume = [&](int p, auto phase_tag) {
+        constexpr int PHASE = decltype(phase_tag)::value;
+        const bool more = p + 1 < nplanes;
+        if (more) load_plane(p + 1);
+        // the prev and f pieces of output plane o = p - 2, which this step completes: the store's address and predicate
+        const int o = p - 2;
+        const bool store_plane = o >= 0 && o < zc && col_ok;
+        d2 fv[RY], sv[RY];
+#pragma unroll
+        for (int r = 0; r < RY; ++r) {
+            fv[r].x = 0.0;
+            fv[r].y = 0.0;
+            sv[r] = fv[r];
+            if (store_plane && i0 + wv * RY + r < a.m) {
+                const long off = (long) (k0 + o + 1) * a.plane + (long) r * a.ld;
+                fv[r] = *reinterpret_cast<const d2 *>(prev_col + off);
+                sv[r] = src_piece<SRC>(a.f, cell_off + off);
+            }
+        }
+        const double *strip = &tile[p & 1][strip_off];
+#pragma unroll
+        for (int j = 0; j < RY + 2; ++j) {
+            double win[6];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const d2 v = *reinterpret_cast<const d2 *>(strip + j * kLdsW + 2 * q);
+                win[2 * q] = v.x;
+                win[2 * q + 1] = v.y;
+            }
+#pragma unroll
+            for (int dz = 0; dz < 3; ++dz) {
+                const int s = (PHASE - dz + 3) % 3;
+#pragma unroll
+                for (int r = 0; r < RY; ++r) {
+                    const int dy = j - r;
+                    if (dy >= 0 && dy < 3) {
+#pragma unroll
+                        for (int dx = 0; dx < 3; ++dx) {
+                            if (tap_on3<TAPSET>(dz, dy, dx)) {
+                                const double wt = W.w[dz * 9 + dy * 3 + dx];
+                                acc0[s][r] = fma(wt, win[dx + 1], acc0[s][r]);
+                                acc1[s][r] = fma(wt, win[dx + 2], acc1[s][r]);
+                            }
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int r = 0; r < RY; ++r) asm volatile("" : "+v"(acc0[s][r]), "+v"(acc1[s][r]));
+
+        // output plane o = p - 2 is complete (it received dz = 0, 1, 2 from planes o, o+1, o+2)
+        {
+            constexpr int s = (PHASE - 2 + 3) % 3;
+            if (store_plane) {
+                double *dst = prev_col + (long) (k0 + o + 1) * a.plane;
+#pragma unroll
+                for (int r = 0; r < RY; ++r) {
+                    if (i0 + wv * RY + r < a.m) {
+                        d2 v;
+                        v.x = leap_src<SRC>(acc0[s][r], sv[r].x, a.sa, a.c, fv[r].x);
+                        v.y = leap_src<SRC>(acc1[s][r], sv[r].y, a.sa, a.c, fv[r].y);
+                        *reinterpret_cast<d2 *>(dst + (long) r * a.ld) = v;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < RY; ++r) {
+                acc0[s][r] = 0.0;
+                acc1[s][r] = 0.0;
+            }
+        }
+        if (more) write_plane((p + 1) & 1);
+        __syncthreads();
+    };
+
+    for (int p = 0; p < nplanes; p += 3) {
+        consume(p, std::integral_constant<int, 0>{});
+        if (p + 1 < nplanes) consume(p + 1, std::integral_constant<int, 1>{});
+        if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
+    }
+}
+
+template <int TAPSET, bool SRC>
+hipError_t launch_leap3d(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
+                         hipStream_t s) {
+    constexpr int TY = 4 * kRY;
+    ArgsLeapSrc3D a;
+    a.in = in;
+    a.prev = prev;
+    a.f = f;
+    a.sa = sa;
+    a.c = c;
+    a.h = p.dims[0];
+    a.m = p.dims[1];
+    a.n = p.dims[2];
+    a.ld = a.n + 8;
+    a.plane = (long) (a.m + 4) * (a.n + 8);
+    a.z_begin = begin;
+    a.z_end = end;
+    a.tiles_x = (a.n + kTileW - 1) / kTileW;
+    a.tiles_y = (a.m + TY - 1) / TY;
+    // enough workgroups to fill 256 CUs a few times over, chunks as long as that allows: a function of the extents alone
+    {
+        const long tiles = (long) a.tiles_x * a.tiles_y;
+        int zc = kZChunk;
+        while (zc > 4 && tiles * ((a.h + zc - 1) / zc) < 2048) zc = (zc == kZChunk) ? 7 : 4;
+        a.zc = zc;
+    }
+    const long chunks = ((long) end - begin + a.zc - 1) / a.zc;
+    const long nblocks = chunks * a.tiles_x * a.tiles_y;
+    if (nblocks <= 0) return hipSuccess;
+    if (nblocks > 0x7fffffffL) return hipErrorInvalidValue;
+    Taps27 w;
+    for (int k = 0; k < 27; ++k) w.w[k] = p.w[k];
+    hipLaunchKernelGGL((stencil3d_leapfrog_src_kernel<TAPSET, SRC>), dim3((unsigned) nblocks), dim3(256), 0, s, a, w);
+    return hipGetLastError();
+}
+
+// ---- odd innermost extent: one thread per point ---------------------------------------------------------------------------
+template <bool SRC>
+__global__ __launch_bounds__(256) void stencil2d_generic_leapfrog_src_kernel(const double *__restrict__ in, double *__restrict__ prev,
+                                                                             const double *__restrict__ f, const double sa, const double cf,
+                                                                             int m, int n, int row_begin, int row_end, const Taps49 W) {
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = row_begin + blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (j >= n || i >= row_end) return;
+    const long ld = n + 8;
+    const long cell = (long) (i + 4) * ld + (j + 4);
+    const double fv = prev[cell];
+    const double sv = src_cell<SRC>(f, cell);
+    const double *c = in + cell;
+    double s = 0.0;
+#pragma unroll
+    for (int dy = 0; dy < 7; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 7; ++dx) {
+            const double w = W.w[dy * 7 + dx];
+            if (w != 0.0) s = fma(w, c[(dy - 3) * ld + (dx - 3)], s);
+        }
+    prev[cell] = leap_src<SRC>(s, sv, sa, cf, fv);
+}
+
+template <bool SRC>
+__global__ __launch_bounds__(256) void stencil3d_generic_leapfrog_src_kernel(const double *__restrict__ in, double *__restrict__ prev,
+                                                                             const double *__restrict__ f, const double sa, const double cf,
+                                                                             int h, int m, int n, int z_begin, int z_end, const Taps27 W) {
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int k = z_begin + blockIdx.z;
+    if (j >= n || i >= m || k >= z_end) return;
+    const long ld = n + 8, plane = (long) (m + 4) * ld;
+    const long cell = (long) (k + 1) * plane + (long) (i + 2) * ld + (j + 4);
+    const double fv = prev[cell];
+    const double sv = src_cell<SRC>(f, cell);
+    const double *c = in + cell;
+    double s = 0.0;
+#pragma unroll
+    for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const double w = W.w[dz * 9 + dy * 3 + dx];
+                if (w != 0.0) s = fma(w, c[(dz - 1) * plane + (dy - 1) * ld + (dx - 1)], s);
+            }
+    prev[cell] = leap_src<SRC>(s, sv, sa, cf, fv);
+}
+
+template <bool SRC>
+hipError_t launch_leap2d_generic(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
+                                 hipStream_t s) {
+    Taps49 w;
+    for (int k = 0; k < 49; ++k) w.w[k] = p.w[k];
+    const unsigned gx = (p.dims[1] + 63) / 64;
+    const int rows = 65535 * 4;  // grid.y is limited to 65535
+    for (int b = begin; b < end; b += rows) {
+        const int e = b + rows < end ? b + rows : end;
+        hipLaunchKernelGGL(stencil2d_generic_leapfrog_src_kernel<SRC>, dim3(gx, (e - b + 3) / 4), dim3(256), 0, s, in, prev, f, sa, c,
+                           p.dims[0], p.dims[1], b, e, w);
+    }
+    return hipGetLastError();
+}
+
+template <bool SRC>
+hipError_t launch_leap3d_generic(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
+                                 hipStream_t s) {
+    Taps27 w;
+    for (int k = 0; k < 27; ++k) w.w[k] = p.w[k];
+    for (int b = begin; b < end; b += 65535) {
+        const int e = b + 65535 < end ? b + 65535 : end;
+        const dim3 grid((p.dims[2] + 63) / 64, (p.dims[1] + 3) / 4, e - b);
+        if (grid.y > 65535u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(stencil3d_generic_leapfrog_src_kernel<SRC>, grid, dim3(256), 0, s, in, prev, f, sa, c, p.dims[0], p.dims[1], p.dims[2], b,
+                           e, w);
+    }
+    return hipGetLastError();
+}
+
+template <bool SRC>
+hipError_t launch_leapfrog_src_t(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
+                                 hipStream_t s) {
+    if (p.ndim == 1) {
+        if (begin & 1) return hipErrorInvalidValue;
+        Taps9 w;
+        for (int t = 0; t < 9; ++t) w.w[t] = p.w[t];
+        const long pairs = ((long) end - begin + 1) / 2;
+        const long blocks = (pairs + 255) / 256;
+        hipLaunchKernelGGL(stencil1d_leapfrog_src_kernel<SRC>, dim3((unsigned) blocks), dim3(256), 0, s, in, prev, f, begin, end, sa, c, w);
+        return hipGetLastError();
+    }
+    if (p.generic)
+        return p.ndim == 2 ? launch_leap2d_generic<SRC>(p, in, prev, f, sa, c, begin, end, s)
+                           : launch_leap3d_generic<SRC>(p, in, prev, f, sa, c, begin, end, s);
+    if (p.ndim == 2) {
+        switch (p.tapset) {
+            case TAPS2D_DIAMOND:
+                return launch_leap2d<TAPS2D_DIAMOND, SRC>(p, in, prev, f, sa, c, begin, end, s);
+            case TAPS2D_STAR:
+                return launch_leap2d<TAPS2D_STAR, SRC>(p, in, prev, f, sa, c, begin, end, s);
+            default:
+                return launch_leap2d<TAPS2D_BOX, SRC>(p, in, prev, f, sa, c, begin, end, s);
+        }
+    }
+    if (p.tapset == TAPS3D_STAR) return launch_leap3d<TAPS3D_STAR, SRC>(p, in, prev, f, sa, c, begin, end, s);
+    return launch_leap3d<TAPS3D_BOX, SRC>(p, in, prev, f, sa, c, begin, end, s);
+}
+
+}  // namespace
+
+// One step prev <- a (S(in) + f) + c prev over [begin, end) of the outermost dimension, in place over `prev`; f == nullptr: no
+// source (fp64 plans; the 2D matrix-pipe variant, bf16 and plans that carry a source never get here: the entries of
+// chebyshev.cpp refuse them).
+hipError_t launch_leapfrog_src(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
+                               hipStream_t s) {
+    if (end <= begin) return hipSuccess;
+    return f ? launch_leapfrog_src_t<true>(p, in, prev, f, sa, c, begin, end, s)
+             : launch_leapfrog_src_t<false>(p, in, prev, nullptr, sa, c, begin, end, s);
+}
+
+}  // namespace lora

@@ -13,13 +13,26 @@
 
 namespace lora {
 
-void release_leapfrog_state(lora_plan *plan) {
+namespace {
+
+// the two scratch grids alone (the probe grid of a Chebyshev run in progress stays)
+void release_scratch(lora_plan *plan) {
     for (void *&b : plan->leap_scratch) {
         if (b) (void) hipFree(b);
         b = nullptr;
     }
     plan->leap_bytes = 0;
     plan->leap_device = -1;
+}
+
+}  // namespace
+
+void release_leapfrog_state(lora_plan *plan) {
+    release_scratch(plan);
+    if (plan->cheb_probe) (void) hipFree(plan->cheb_probe);
+    plan->cheb_probe = nullptr;
+    plan->cheb_bytes = 0;
+    plan->cheb_device = -1;
 }
 
 namespace {
@@ -65,6 +78,28 @@ int step2(const Plan &p, const void *d_prev, const void *d_cur, void *d_out1, vo
     return e == hipSuccess ? LORA_OK : failed("two-step leapfrog kernel launch", e);
 }
 
+int step1_src(const Plan &p, const void *d_cur, void *d_prev, const void *d_f, double a, double c, int begin, int end, hipStream_t s) {
+    const hipError_t e = launch_leapfrog_src(p, static_cast<const double *>(d_cur), static_cast<double *>(d_prev),
+                                             static_cast<const double *>(d_f), a, c, begin, end, s);
+    return e == hipSuccess ? LORA_OK : failed("leapfrog kernel launch (source, scale)", e);
+}
+
+int step2_src(const Plan &p, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1, void *d_out2, double a1, double c1,
+              double a2, double c2, int begin, int end, hipStream_t s) {
+    const hipError_t e = launch_leapfrog2_src(p, static_cast<const double *>(d_prev), static_cast<const double *>(d_cur),
+                                              static_cast<const double *>(d_f), static_cast<double *>(d_out1),
+                                              static_cast<double *>(d_out2), a1, c1, a2, c2, begin, end, s);
+    return e == hipSuccess ? LORA_OK : failed("two-step leapfrog kernel launch (source, scale)", e);
+}
+
+// whether any two of the n buffers are equal (null entries -- an absent source -- equal nothing)
+bool any_equal(const void *const *b, int n) {
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (b[i] && b[i] == b[j]) return true;
+    return false;
+}
+
 bool scratch_ready(const lora_plan *plan) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) {
@@ -81,13 +116,13 @@ bool ensure_scratch(lora_plan *plan) {
         (void) hipGetLastError();
         return false;
     }
-    release_leapfrog_state(plan);
+    release_scratch(plan);
     const size_t bytes = lora_plan_padded_bytes(plan);
     for (void *&b : plan->leap_scratch) {
         // (pads beyond the halo ring do not exist; the ring is copied per run, the interior written before it is read)
         if (hipMalloc(&b, bytes) != hipSuccess || hipMemset(b, 0, bytes) != hipSuccess) {
             (void) hipGetLastError();
-            release_leapfrog_state(plan);
+            release_scratch(plan);
             return false;
         }
     }
@@ -200,6 +235,103 @@ int lora_plan_run_leapfrog(lora_plan *plan, void *d_prev, void *d_cur, double c,
     }
     for (int i = done; i < times; ++i) {
         if (int rc = lora::step1(p, lv[1], lv[0], c, 0, m, s)) return rc;
+        std::swap(lv[0], lv[1]);
+    }
+    return LORA_OK;
+}
+
+// ---- a (S(u) + f) + c u-: the same entries with a source and a scale as call arguments ------------------------
+int lora_plan_step_leapfrog_src_region(lora_plan *plan, const void *d_cur, void *d_prev, const void *d_f, double a, double c, int begin,
+                                       int end, void *stream) {
+    if (!plan || !d_cur || !d_prev || !std::isfinite(a) || !std::isfinite(c)) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const void *b[3] = {d_cur, d_prev, d_f};
+    if (lora::bad_range(p, begin, end) || lora::any_equal(b, 3)) return LORA_EINVAL;
+    for (const void *x : b)
+        if (lora::misaligned(x)) return lora::unsupported("device buffers must be 16-byte aligned");
+    if (int rc = lora::plan_refused(p, false)) return rc;
+    return lora::step1_src(p, d_cur, d_prev, d_f, a, c, begin, end, static_cast<hipStream_t>(stream));
+}
+
+int lora_plan_step_leapfrog_src(lora_plan *plan, const void *d_cur, void *d_prev, const void *d_f, double a, double c, void *stream) {
+    if (!plan) return LORA_EINVAL;
+    return lora_plan_step_leapfrog_src_region(plan, d_cur, d_prev, d_f, a, c, 0, plan->p.dims[0], stream);
+}
+
+int lora_plan_step2_leapfrog_src_region(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1,
+                                        void *d_out2, double a1, double c1, double a2, double c2, int begin, int end, void *stream) {
+    if (!plan || !d_prev || !d_cur || !d_out1 || !d_out2) return LORA_EINVAL;
+    if (!std::isfinite(a1) || !std::isfinite(c1) || !std::isfinite(a2) || !std::isfinite(c2)) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const void *b[5] = {d_prev, d_cur, d_out1, d_out2, d_f};
+    if (lora::bad_range(p, begin, end) || lora::any_equal(b, 5)) return LORA_EINVAL;
+    for (const void *x : b)
+        if (lora::misaligned(x)) return lora::unsupported("device buffers must be 16-byte aligned");
+    if (int rc = lora::plan_refused(p, true)) return rc;
+    return lora::step2_src(p, d_prev, d_cur, d_f, d_out1, d_out2, a1, c1, a2, c2, begin, end, static_cast<hipStream_t>(stream));
+}
+
+int lora_plan_step2_leapfrog_src(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1, void *d_out2,
+                                 double a1, double c1, double a2, double c2, void *stream) {
+    if (!plan) return LORA_EINVAL;
+    return lora_plan_step2_leapfrog_src_region(plan, d_prev, d_cur, d_f, d_out1, d_out2, a1, c1, a2, c2, 0, plan->p.dims[0], stream);
+}
+
+int lora_plan_run_leapfrog_src(lora_plan *plan, void *d_prev, void *d_cur, const void *d_f, const double *a, const double *c, int ncoef,
+                               int times, void *stream) {
+    if (!plan || !d_prev || !d_cur || !a || !c || ncoef < 1 || times < 0) return LORA_EINVAL;
+    for (int i = 0; i < std::min(times, ncoef); ++i)  // the entries this run uses
+        if (!std::isfinite(a[i]) || !std::isfinite(c[i])) return LORA_EINVAL;
+    const void *b[3] = {d_prev, d_cur, d_f};
+    if (lora::any_equal(b, 3)) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    for (const void *x : b)
+        if (lora::misaligned(x)) return lora::unsupported("device buffers must be 16-byte aligned");
+    if (int rc = lora::plan_refused(p, false)) return rc;
+    if (times == 0) return LORA_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int m = p.dims[0];
+    auto A = [&](int i) { return a[std::min(i, ncoef - 1)]; };
+    auto C = [&](int i) { return c[std::min(i, ncoef - 1)]; };
+    void *lv[2] = {d_prev, d_cur};  // lv[1] holds the newest level, lv[0] the one before it
+
+    if (p.boundary == LORA_BC_PERIODIC) {
+        // as lora_plan_run_leapfrog: the newest level always carries its periodic images; the older one's halo is never read
+        auto wrap = [&](void *buf) -> int {
+            const int rc = lora_plan_halo(plan, buf, nullptr, LORA_HALO_WRAP, stream);
+            if (rc == LORA_EHIP && lora_device_count() <= 0) {
+                lora::set_last_error_text("no HIP device visible");
+                return LORA_ENODEVICE;
+            }
+            return rc;
+        };
+        if (int rc = wrap(lv[1])) return rc;
+        for (int i = 0; i < times; ++i) {
+            if (int rc = lora::step1_src(p, lv[1], lv[0], d_f, A(i), C(i), 0, m, s)) return rc;
+            if (int rc = wrap(lv[0])) return rc;
+            std::swap(lv[0], lv[1]);
+        }
+        return LORA_OK;
+    }
+
+    // lora_plan_run_leapfrog's schedule and scratch grids: (prev, cur) -> (s0, s1) -> (prev, cur), steps 4k .. 4k + 3
+    int done = 0;
+    if (lora::run_fuses(p, times) && lora::ensure_scratch(plan)) {
+        void *s0 = plan->leap_scratch[0], *s1 = plan->leap_scratch[1];
+        const void *all[5] = {d_prev, d_cur, d_f, s0, s1};
+        if (!lora::any_equal(all, 5)) {
+            if (int rc = lora_plan_halo(plan, s0, d_prev, LORA_HALO_COPY, stream)) return rc;
+            if (int rc = lora_plan_halo(plan, s1, d_cur, LORA_HALO_COPY, stream)) return rc;
+            for (int k = 0; k < times / 4; ++k) {
+                const int i = 4 * k;
+                if (int rc = lora::step2_src(p, d_prev, d_cur, d_f, s0, s1, A(i), C(i), A(i + 1), C(i + 1), 0, m, s)) return rc;
+                if (int rc = lora::step2_src(p, s0, s1, d_f, d_prev, d_cur, A(i + 2), C(i + 2), A(i + 3), C(i + 3), 0, m, s)) return rc;
+            }
+            done = times / 4 * 4;
+        }
+    }
+    for (int i = done; i < times; ++i) {
+        if (int rc = lora::step1_src(p, lv[1], lv[0], d_f, A(i), C(i), 0, m, s)) return rc;
         std::swap(lv[0], lv[1]);
     }
     return LORA_OK;

@@ -180,6 +180,12 @@ int no_residual_kernel() {
 }
 
 }  // namespace
+
+int admit_reduction(const void *a, const void *b, hipStream_t s) { return admit(a, b, s); }
+int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s) {
+    return diff_range(plan, d_a, d_b, 0, plan->p.dims[0], out, s);
+}
+
 }  // namespace lora
 
 using lora::Plan;

@@ -372,6 +372,43 @@ def run_host_leapfrog(shape, cur: np.ndarray, prev: np.ndarray, c: float = -1.0,
     return out, info
 
 
+def chebyshev_coeffs(rho: float, first_step: int = 1, count: int = 1):
+    """The Chebyshev schedule for a spectrum inside [-rho, rho] (lora_chebyshev_coeffs; host only): (a, c) as float64 arrays with
+    a[i] = w(first_step + i), c[i] = 1 - a[i]; w(1) = 1, w(2) = 1 / (1 - rho^2 / 2), w(k+1) = 1 / (1 - rho^2 w(k) / 4).  For the
+    5-point Jacobi taps on an m x n interior with zero halos rho = (cos(pi / (m+1)) + cos(pi / (n+1))) / 2."""
+    n = max(int(count), 0)
+    a, c = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    check(_lib.lib().lora_chebyshev_coeffs(float(rho), int(first_step), int(count), _p(a), _p(c)), "lora_chebyshev_coeffs")
+    return a[:n], c[:n]
+
+
+def run_host_chebyshev(shape, in_: np.ndarray, rho: float, times: int = 0, source=None, tol=None, rtol: float = 0.0, norm="max",
+                       check_every: int = 60, max_times: int = 6000, params=None, quiet: bool = True):
+    """The Chebyshev semi-iteration for u = S(u) + f from the padded float64 host array ``in_`` (both starting levels), ``source``
+    a padded host array of f or None (lora_run_host_chebyshev).  ``tol`` None: ``times`` steps; else until the true residual is
+    <= tol + rtol * max|S(u) + f|, checked every ``check_every`` steps, ``max_times`` at most.  Returns (the newest level as a
+    padded array, UntilResult, RunInfo)."""
+    sid = shape_id(shape)
+    in_ = np.ascontiguousarray(in_, dtype=np.float64)
+    h = halo(sid)
+    if in_.ndim != len(h):
+        raise ValueError("in_ must be a padded array of the shape's rank")
+    src = None
+    if source is not None:
+        src = np.ascontiguousarray(source, dtype=np.float64)
+        if src.shape != in_.shape:
+            raise ValueError("source must be a padded array of in_'s size")
+    dims = [in_.shape[i] - 2 * h[i] for i in range(in_.ndim)]
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    u = None if tol is None else ctypes.byref(_until_arg(tol, rtol, norm, check_every, max_times))
+    r, info = _lib.UntilResult(), RunInfo()
+    check(_lib.lib().lora_run_host_chebyshev(sid, _p(in_), None if src is None else _p(src), _p(out), pp, float(rho), int(times), u,
+                                             ctypes.byref(r), _dims_arg(dims), int(quiet), ctypes.byref(info)),
+          f"lora_run_host_chebyshev({SHAPE_NAMES.get(sid, sid)})")
+    return out, _until_result(r), info
+
+
 def _operator(cname: str, nd: int):
     def op(in_, out, params, times, *sizes):
         if len(sizes) != nd:
@@ -399,6 +436,11 @@ def _ptr(x) -> int:
     if hasattr(x, "data_ptr"):
         return int(x.data_ptr())
     return int(x)
+
+
+def _optr(x):
+    """an optional device buffer: None is the null pointer"""
+    return None if x is None else _ptr(x)
 
 
 def _stream(stream) -> int:
@@ -597,6 +639,48 @@ class Plan:
         """Allocate now what ``run_leapfrog(..., times)`` would allocate on first need (its two scratch grids)."""
         check(_lib.lib().lora_plan_prepare_leapfrog(self._h, int(times)), "lora_plan_prepare_leapfrog")
         return self
+
+    # -- leapfrog steps with a source and a scale: u+ = a (S(u) + f) + c u-; d_f is a padded device grid or None
+    def step_leapfrog_src(self, d_cur, d_prev, d_f, a: float = 1.0, c: float = -1.0, stream=None):
+        """One step in place: d_prev <- a * (S(d_cur) + d_f) + c * d_prev on the interior (lora_plan_step_leapfrog_src)."""
+        check(_lib.lib().lora_plan_step_leapfrog_src(self._h, _ptr(d_cur), _ptr(d_prev), _optr(d_f), float(a), float(c), _stream(stream)),
+              "lora_plan_step_leapfrog_src")
+
+    def step_leapfrog_src_region(self, d_cur, d_prev, d_f, a: float, c: float, begin: int, end: int, stream=None):
+        check(_lib.lib().lora_plan_step_leapfrog_src_region(self._h, _ptr(d_cur), _ptr(d_prev), _optr(d_f), float(a), float(c), int(begin),
+                                                            int(end), _stream(stream)), "lora_plan_step_leapfrog_src_region")
+
+    def step2_leapfrog_src(self, d_prev, d_cur, d_f, d_out1, d_out2, a1: float, c1: float, a2: float, c2: float, stream=None):
+        """Two steps in one launch: d_out1 = a1 (S(d_cur) + f) + c1 d_prev, d_out2 = a2 (S(d_out1) + f) + c2 d_cur
+        (lora_plan_step2_leapfrog_src)."""
+        check(_lib.lib().lora_plan_step2_leapfrog_src(self._h, _ptr(d_prev), _ptr(d_cur), _optr(d_f), _ptr(d_out1), _ptr(d_out2), float(a1),
+                                                      float(c1), float(a2), float(c2), _stream(stream)), "lora_plan_step2_leapfrog_src")
+
+    def step2_leapfrog_src_region(self, d_prev, d_cur, d_f, d_out1, d_out2, a1: float, c1: float, a2: float, c2: float, begin: int,
+                                  end: int, stream=None):
+        check(_lib.lib().lora_plan_step2_leapfrog_src_region(self._h, _ptr(d_prev), _ptr(d_cur), _optr(d_f), _ptr(d_out1), _ptr(d_out2),
+                                                             float(a1), float(c1), float(a2), float(c2), int(begin), int(end),
+                                                             _stream(stream)), "lora_plan_step2_leapfrog_src_region")
+
+    def run_leapfrog_src(self, d_prev, d_cur, d_f, a, c, times: int = 1, stream=None):
+        """``times`` steps; step i uses a[min(i, len - 1)], c[min(i, len - 1)] (scalars: constant coefficients).  The newest level
+        ends in ``d_cur`` if ``times`` is even, in ``d_prev`` if odd (lora_plan_run_leapfrog_src)."""
+        aa = np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64)
+        cc = np.ascontiguousarray(np.atleast_1d(c), dtype=np.float64)
+        if aa.ndim != 1 or aa.shape != cc.shape:
+            raise ValueError("a and c must be scalars or 1D arrays of one length")
+        check(_lib.lib().lora_plan_run_leapfrog_src(self._h, _ptr(d_prev), _ptr(d_cur), _optr(d_f), _p(aa), _p(cc), int(aa.size),
+                                                    int(times), _stream(stream)), "lora_plan_run_leapfrog_src")
+
+    def run_chebyshev_until(self, d_prev, d_cur, d_f, rho: float, tol: float, rtol: float = 0.0, norm="max", check_every: int = 60,
+                            max_times: int = 6000, stream=None) -> "UntilResult":
+        """Chebyshev steps in runs of ``check_every`` until the TRUE residual max|S(u) + f - u| is <= tol + rtol * max|S(u) + f|
+        (lora_plan_run_chebyshev_until); ``d_cur`` (level 0 going in; ``d_prev`` any finite values) then holds level
+        ``times_done``, bit for bit what ``run_leapfrog_src`` with ``chebyshev_coeffs(rho, 1, times_done)`` gives."""
+        u, r = _until_arg(tol, rtol, norm, check_every, max_times), _lib.UntilResult()
+        check(_lib.lib().lora_plan_run_chebyshev_until(self._h, _ptr(d_prev), _ptr(d_cur), _optr(d_f), float(rho), ctypes.byref(u),
+                                                       ctypes.byref(r), _stream(stream)), "lora_plan_run_chebyshev_until")
+        return _until_result(r)
 
     # -- reductions on the device (these block until the result is on the host)
     def stats(self, d_buf, begin: int = 0, end: int = 0, stream=None) -> GridStats:
