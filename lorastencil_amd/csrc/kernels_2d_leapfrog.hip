@@ -9,7 +9,8 @@
 //
 // Arithmetic: the DIRECT taps of the plan's tap set in row-major order at both levels, always -- one fma per tap from an
 // accumulator of 0, then fl(acc + fl(c * x)) in two roundings (contraction off).  That is the single leapfrog step's
-// arithmetic (kernels_leapfrog.hip) at each level, so a launch equals two single steps bit for bit on any data.
+// arithmetic (kernels_step.hip, EPI_LEAP) at each level, through the same taps_row and leap of step_epilogue.h, so a launch
+// equals two single steps bit for bit on any data.
 //
 // Boundary: a level-1 cell outside the interior takes the value prev holds at that cell -- the halo of the buffer the level
 // lives in under the in-place driver.  The ring is 3 and the pad 4, so such a cell is always inside the padded array; a cell
@@ -25,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "step_epilogue.h"
 
 namespace lora {
 
@@ -43,32 +45,6 @@ struct ArgsLeap2 {
     int row_begin, row_end;
     int tiles_x, tiles_y, panel_w;
 };
-
-// acc + c * x in two roundings: contraction is switched off around the expression
-__device__ __forceinline__ double leap(double acc, double c, double x) {
-#pragma clang fp contract(off)
-    const double t = c * x;
-    return acc + t;
-}
-
-// One window row (8 values) into the accumulators of the rows it contributes to: direct taps, row-major order.
-template <int TAPSET, int R>
-__device__ __forceinline__ void taps_row(int j, const double (&win)[8], double (&acc0)[R], double (&acc1)[R], const Taps49 &W) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int dy = j - r;
-        if (dy >= 0 && dy < 7) {
-#pragma unroll
-            for (int dx = 0; dx < 7; ++dx) {
-                if (tap_on<TAPSET>(dy, dx)) {
-                    const double wt = W.w[dy * 7 + dx];
-                    acc0[r] = fma(wt, win[dx], acc0[r]);
-                    acc1[r] = fma(wt, win[dx + 1], acc1[r]);
-                }
-            }
-        }
-    }
-}
 
 template <int TAPSET, int R1>
 __global__ __launch_bounds__(256, 3) void stencil2d_leapfrog2_kernel(const ArgsLeap2 a, const Taps49 W) {

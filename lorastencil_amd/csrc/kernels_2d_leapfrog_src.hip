@@ -10,8 +10,9 @@
 //
 // Arithmetic: the DIRECT taps of the plan's tap set in row-major order at both levels, always -- one fma per tap from an
 // accumulator of 0, then t = fl(acc + f) (no source: t = acc) and fl(fl(a t) + fl(c x)), every operation its own rounding
-// (contraction off).  That is the single step's arithmetic (kernels_leapfrog_src.hip) at each level, so a launch equals two
-// single steps bit for bit on any data.  "No source" is its own instantiation, not "add a zero".
+// (contraction off).  That is the single step's arithmetic (kernels_step.hip) at each level, through the same taps_row and
+// leap_src of step_epilogue.h, so a launch equals two single steps bit for bit on any data.  "No source" is its own
+// instantiation, not "add a zero".
 //
 // Boundary: a level-1 cell outside the interior takes the value prev holds at that cell, as in stencil2d_leapfrog2_kernel.
 //
@@ -24,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "step_epilogue.h"
 
 namespace lora {
 
@@ -43,36 +45,6 @@ struct ArgsLeapSrc2 {
     int row_begin, row_end;
     int tiles_x, tiles_y, panel_w;
 };
-
-// a * (acc + f) + c * x, every operation its own rounding: contraction is switched off around the expression
-template <bool SRC>
-__device__ __forceinline__ double leap_src(double acc, double f, double sa, double c, double x) {
-#pragma clang fp contract(off)
-    double t = acc;
-    if constexpr (SRC) t = acc + f;
-    const double p = sa * t;
-    const double q = c * x;
-    return p + q;
-}
-
-// One window row (8 values) into the accumulators of the rows it contributes to: direct taps, row-major order.
-template <int TAPSET, int R>
-__device__ __forceinline__ void taps_row(int j, const double (&win)[8], double (&acc0)[R], double (&acc1)[R], const Taps49 &W) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int dy = j - r;
-        if (dy >= 0 && dy < 7) {
-#pragma unroll
-            for (int dx = 0; dx < 7; ++dx) {
-                if (tap_on<TAPSET>(dy, dx)) {
-                    const double wt = W.w[dy * 7 + dx];
-                    acc0[r] = fma(wt, win[dx], acc0[r]);
-                    acc1[r] = fma(wt, win[dx + 1], acc1[r]);
-                }
-            }
-        }
-    }
-}
 
 template <int TAPSET, int R1, bool SRC>
 __global__ __launch_bounds__(256, 3) void stencil2d_leapfrog2_src_kernel(const ArgsLeapSrc2 a, const Taps49 W) {

@@ -9,8 +9,8 @@
 //
 // Arithmetic: the DIRECT taps of the plan's tap set in row-major order at both levels, always -- never the structured forms
 // of rows_2d.h, whatever the plan's fused_eval says -- one fma per tap from an accumulator of 0, then ONE separate fp64
-// addition of f.  That is the single source sweep's arithmetic (kernels_source.hip) at each level, so a launch equals two
-// single source sweeps bit for bit on any data.
+// addition of f.  That is the single source sweep's arithmetic (kernels_step.hip, EPI_SOURCE) at each level, so a launch
+// equals two single source sweeps bit for bit on any data.  The tap loop is taps_row of step_epilogue.h.
 //
 // Boundary: level-1 cells outside the interior take no source; they are 0 under the reference boundary and the input halo
 // under Dirichlet, as in stencil2d_fused2_kernel.  The source adds to interior cells only.
@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "step_epilogue.h"
 
 namespace lora {
 
@@ -40,25 +41,6 @@ struct ArgsSource2 {
     int tiles_x, tiles_y, panel_w;
     int dirichlet;  // level-1 cells outside the interior keep the input halo value instead of 0
 };
-
-// One window row (8 values) into the accumulators of the rows it contributes to: direct taps, row-major order.
-template <int TAPSET, int R>
-__device__ __forceinline__ void taps_row(int j, const double (&win)[8], double (&acc0)[R], double (&acc1)[R], const Taps49 &W) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int dy = j - r;
-        if (dy >= 0 && dy < 7) {
-#pragma unroll
-            for (int dx = 0; dx < 7; ++dx) {
-                if (tap_on<TAPSET>(dy, dx)) {
-                    const double wt = W.w[dy * 7 + dx];
-                    acc0[r] = fma(wt, win[dx], acc0[r]);
-                    acc1[r] = fma(wt, win[dx + 1], acc1[r]);
-                }
-            }
-        }
-    }
-}
 
 template <int TAPSET, int R1>
 __global__ __launch_bounds__(256, 3) void stencil2d_source2_kernel(const ArgsSource2 a, const Taps49 W) {

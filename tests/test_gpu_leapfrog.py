@@ -1,4 +1,4 @@
-"""GPU tests of leapfrog stepping (lora_plan_step_leapfrog ... lora_run_host_leapfrog; kernels_leapfrog.hip,
+"""GPU tests of leapfrog stepping (lora_plan_step_leapfrog ... lora_run_host_leapfrog; kernels_step.hip,
 kernels_2d_leapfrog.hip): u(t+1) = S(u(t)) + c u(t-1), the new level stored over the oldest one.
 
 Contract under test: one step is prev = fl(acc + fl(c * prev)) on the interior cells of the swept range, acc the bits of the

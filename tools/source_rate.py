@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rate of the sweeps with a source term beside the plain sweeps of the same plan:
-   python tools/source_rate.py [--out profiles/source_rate.jsonl] [--reps 24] [--small]
+   python tools/source_rate.py [--out profiles/source_rate.jsonl] [--reps 24] [--small] [--lib PATH]
 
 One process.  Per configuration, after a warm-up, `reps` rounds that ALTERNATE the things compared, each between two device
 events of its own; medians are reported, and beside every ratio the spread of two identical launches in the same rounds.
@@ -108,7 +108,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "source_rate.jsonl"))
     ap.add_argument("--reps", type=int, default=24)
     ap.add_argument("--small", action="store_true", help="a quick rehearsal on small grids")
+    ap.add_argument("--lib", help="time this build of liblorastencil_hip.so instead of the tree's (A/B against another commit)")
     args = ap.parse_args()
+    if args.lib:
+        L._lib.LIB_PATH = os.path.abspath(args.lib)  # before the first call into the engine
     assert args.reps >= 20 or args.small
     configs = [("star2d1r", (2048, 2048)), ("box2d3r", (1024, 1024)), ("box3d1r", (128, 128, 128))] if args.small else \
               [("star2d1r", (16384, 16384)), ("box2d3r", (8192, 8192)), ("box3d1r", (768, 768, 768))]
