@@ -498,6 +498,23 @@ int lora_plan_diff(lora_plan *plan, const void *d_a, const void *d_b, int begin,
  *   extent) and 2D plans of LORA_VARIANT_MFMA (whose sums run in another order than the direct taps) answer
  *   LORA_EUNSUPPORTED. */
 int lora_plan_residual(lora_plan *plan, const void *d_in, int begin, int end, lora_grid_diff *out, void *stream);
+/* The TRUE residual of u = S(u) + f in one pass: *out = the lora_grid_diff of a = S(d_in) + f against b = d_in over the
+ * outermost interior range [begin, end), ranges and granularity as lora_plan_residual.  d_f is a padded fp64 grid of the plan's
+ * layout and a CALL ARGUMENT like the f of the *_leapfrog_src entries, never plan state: no option, kernel name, signature or
+ * depth of the plan changes.  The launch reads d_in once and the interior cells of d_f once (16-byte pieces at the reduced
+ * cells' own padded indices, 8 bytes for the odd tail point in 1D: no halo cell of d_f is ever loaded, nothing outside [d_f,
+ * d_f + lora_plan_padded_bytes) is read) and writes no grid memory at all.  BLOCKS like the reductions.
+ *   Contract.  max_abs, a_abs_max, argmax, count and nonfinite are BIT FOR BIT what a single sweep over [begin, end) of a plan
+ *   that carries f as its source (lora_plan_set_source + lora_plan_step_region) into a spare grid, then lora_plan_diff(spare,
+ *   d_in, begin, end) give -- a = fl(acc + f), one rounding on top of the sweep's bits -- non-finite data in d_in or in interior
+ *   cells of f included; argmax is the lowest padded index among equal maxima; sum_sq sums the same finite d in the kernel's own
+ *   fixed order, the same bits every time whatever the plan's tuning options.  d_f == NULL is exactly lora_plan_residual, on
+ *   the same plans (bf16 included), in all six fields.
+ *   Status, in this order, before anything is dereferenced or launched: LORA_EINVAL for a null plan, d_in or out, a bad range
+ *   or begin, or d_f == d_in; LORA_EUNSUPPORTED for a misaligned d_in or d_f; LORA_EUNSUPPORTED, with d_f != NULL, for a plan
+ *   whose option "fused_residual" reads 0, a LORA_BF16 plan (a source is fp64) and a plan on which lora_plan_set_source was
+ *   called; then the reductions' codes (a capturing stream, LORA_ENODEVICE). */
+int lora_plan_residual_src(lora_plan *plan, const void *d_in, const void *d_f, int begin, int end, lora_grid_diff *out, void *stream);
 /* Test support, no device needed: replays on the host the tile -> workgroup -> cells map of lora_plan_residual's launch over
  * [begin, end) (csrc/residual_tiles.h).  cover[padded linear index] is incremented once per cell a workgroup would reduce (the
  * caller zeroes it: lora_padded_count ints): every interior cell of the range must come out 1, every other cell 0.
@@ -548,11 +565,15 @@ int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_
  * lora_plan_run_leapfrog_src, then the reductions'.  Each round runs check_every steps of lora_plan_run_leapfrog_src with the
  * schedule's next coefficients (lora_chebyshev_coeffs(rho, times_done + 1, check_every)) and then probes the newest level:
  * `last` = the lora_grid_diff of a = S(d_cur) + f against b = d_cur over the whole interior, bit for bit in max_abs, a_abs_max,
- * argmax, count and nonfinite what a source sweep into a spare grid plus lora_plan_diff give.  The probe sweeps into a third
- * grid owned by the plan (allocated on first need, freed with the plan) and changes neither d_prev nor d_cur.  Stop rule and
+ * argmax, count and nonfinite what a source sweep into a spare grid plus lora_plan_diff give.  Under LORA_NORM_MAX on a plan
+ * whose option "fused_residual" reads 1 the probe is ONE lora_plan_residual_src(d_cur, d_f): no third grid is allocated or
+ * touched, and last.sum_sq carries that kernel's order.  Otherwise (LORA_NORM_RMS, where sum_sq decides the stop; plans
+ * without that kernel) the probe sweeps into a third grid owned by the plan (allocated on first need of this form, freed with
+ * the plan) and takes the difference.  Neither form changes d_prev or d_cur.  Stop rule and
  * result fields are lora_plan_run_until's.  On return d_cur holds level times_done, bit for bit what
  * lora_plan_run_leapfrog_src(times_done) with the same coefficients gives, and d_prev the level before it.  BLOCKS, and answers
- * the reductions' status codes.  Cost of a probe: one single sweep with a source plus one difference. */
+ * the reductions' status codes.  Cost of a probe: fused, one read of d_cur and of d_f; two-pass, one single sweep
+ * with a source plus one difference. */
 int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, const void *d_f, double rho, const lora_until *u,
                                   lora_until_result *r, void *stream);
 void lora_plan_destroy(lora_plan *plan);

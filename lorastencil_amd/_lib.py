@@ -218,6 +218,7 @@ SIGNATURES = {
     "lora_plan_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridStats), _vp]),
     "lora_plan_diff": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDiff), _vp]),
     "lora_plan_residual": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDiff), _vp]),
+    "lora_plan_residual_src": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDiff), _vp]),
     "lora_debug_residual_cover": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "lora_grid_stats_merge": (None, [ctypes.POINTER(GridStats), ctypes.POINTER(GridStats)]),
     "lora_plan_run_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Until), ctypes.POINTER(UntilResult), _vp]),

@@ -97,14 +97,19 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
     if (int rc = lora::admit_reduction(d_prev, d_cur, s)) return rc;
     *r = {0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}};
     if (u->max_times < u->check_every) return LORA_OK;
-    if (!lora::ensure_probe(plan)) return LORA_ENOMEM;
-    if (plan->cheb_probe == d_prev || plan->cheb_probe == d_cur || plan->cheb_probe == d_f) return LORA_EINVAL;
+    // under the max norm every deciding field of the fused residual (lora_plan_residual_src) is bit for bit the two-pass
+    // probe's; sum_sq -- the RMS norm's -- is summed in another order there, so that norm keeps the two passes and their grid
+    const bool fused = u->norm == LORA_NORM_MAX && lora::has_fused_residual(p);
+    if (!fused) {
+        if (!lora::ensure_probe(plan)) return LORA_ENOMEM;
+        if (plan->cheb_probe == d_prev || plan->cheb_probe == d_cur || plan->cheb_probe == d_f) return LORA_EINVAL;
+    }
     (void) lora_plan_prepare_leapfrog(plan, u->check_every);
 
-    // the probe's sweep: the plan's own single sweep with f as its source -- a copy of the plan's resolved state, so the
-    // caller's plan keeps its options, kernel name, signature and leapfrog depth
+    // the two-pass probe's sweep (unused by the fused one): the plan's own single sweep with f as its source -- a copy of
+    // the plan's resolved state, so the caller's plan keeps its options, kernel name, signature and leapfrog depth
     Plan probe = p;
-    probe.source = d_f;
+    if (!fused) probe.source = d_f;
     lora::Omega om(rho);
     std::vector<double> a(u->check_every), c(u->check_every);
     while (r->times_done + u->check_every <= u->max_times) {
@@ -115,9 +120,14 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
         // an even run: the newest level is back in d_cur (under the periodic boundary with its images)
         if (int rc = lora_plan_run_leapfrog_src(plan, d_prev, d_cur, d_f, a.data(), c.data(), u->check_every, u->check_every, stream)) return rc;
         r->times_done += u->check_every;
-        // the TRUE residual S(u) + f - u of that level: one sweep into the probe grid, one difference; d_prev and d_cur untouched
-        if (int rc = lora::launch_apps(probe, {1, 0, p.dims[0]}, d_cur, plan->cheb_probe, s)) return rc;
-        if (int rc = lora::diff_whole(plan, plan->cheb_probe, d_cur, &r->last, s)) return rc;
+        // the TRUE residual S(u) + f - u of that level, d_prev and d_cur untouched: reduced inside one sweep where the plan has
+        // that kernel, else one sweep into the probe grid and one difference
+        if (fused) {
+            if (int rc = lora::residual_whole(plan, d_cur, d_f, &r->last, s)) return rc;
+        } else {
+            if (int rc = lora::launch_apps(probe, {1, 0, p.dims[0]}, d_cur, plan->cheb_probe, s)) return rc;
+            if (int rc = lora::diff_whole(plan, plan->cheb_probe, d_cur, &r->last, s)) return rc;
+        }
         r->checks += 1;
         r->residual = u->norm == LORA_NORM_RMS ? std::sqrt(r->last.sum_sq / (double) r->last.count) : r->last.max_abs;
         if (r->last.nonfinite > 0) {

@@ -232,12 +232,13 @@ hipError_t launch_reduce_fold_cells(int groups, ReduceRecord *partial, hipStream
 // ---- one sweep's change, reduced in the sweep (kernels_residual.hip; tile geometry: residual_tiles.h) -----------------
 struct ResidualTiles;
 // Whether the plan has the fused residual kernel: 1D, the tiled 2D direct-variant and 3D fp64 kernels' plans, 3D bf16.
-// A plan that carries a source has none (a fused residual with a source is not built).
+// A plan that carries a source has none: the source of lora_plan_residual_src is a call argument.
 inline bool has_fused_residual(const Plan &p) {
     return !p.source && (p.ndim == 1 || p.dtype == LORA_BF16 || (!p.generic && (p.ndim == 3 || p.variant == LORA_VARIANT_DIRECT)));
 }
-// The records of `d = sweep(in) - in` over the tiles of `rt`, one per workgroup into partial[0 .. rt.groups), and the fold.
-hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, ReduceRecord *partial, hipStream_t s);
+// The records of `d = a - in` over the tiles of `rt`, one per workgroup into partial[0 .. rt.groups), and the fold:
+// a = sweep(in), or with `f` (fp64 plans only; nullptr = none) a = fl(sweep(in) + f), f read at the reduced cells alone.
+hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, const double *f, ReduceRecord *partial, hipStream_t s);
 
 // ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_source.hip: two, 2D) -------
 // Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
@@ -300,6 +301,7 @@ void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info r
 void release_leapfrog_state(lora_plan *plan);      // leapfrog.cpp: the two scratch grids of lora_plan_run_leapfrog[_src], the probe grid of lora_plan_run_chebyshev_until
 void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus, reduction records)
 int admit_reduction(const void *a, const void *b, hipStream_t s);  // reduce.cpp: what every reduction entry checks before it touches the device
+int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_residual_src over the whole interior, unchecked (blocks)
 int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_diff over the whole interior, unchecked (blocks)
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
@@ -336,7 +338,8 @@ struct lora_plan {
     void *leap_scratch[2] = {nullptr, nullptr};
     size_t leap_bytes = 0;
     int leap_device = -1;
-    // lora_plan_run_chebyshev_until's probe grid (chebyshev.cpp): S(u) + f of the newest level, allocated on first need
+    // lora_plan_run_chebyshev_until's probe grid (chebyshev.cpp): S(u) + f of the newest level, allocated on first need of the
+    // two-pass probe (the RMS norm, plans without the fused residual kernel)
     void *cheb_probe = nullptr;
     size_t cheb_bytes = 0;
     int cheb_device = -1;

@@ -18,6 +18,9 @@
 // index): a lane does not meet its cells in ascending order here.  Lanes, waves and the workgroup fold as there (xor
 // butterfly, waves through LDS in wave order), the records by combine_kernel as KIND_CELL.  No atomics; records are
 // written with plain vector stores.
+//
+// With a source (lora_plan_residual_src; template parameter SRC of the three fp64 families): a = fl(sweep(in) + f), f read at
+// the reduced cells alone -- DESIGN 3.5c.  SRC = false is the code above, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -25,6 +28,7 @@
 #include "device_common.h"
 #include "reduce_device.h"
 #include "residual_tiles.h"
+#include "step_epilogue.h"
 
 namespace lora {
 
@@ -72,6 +76,15 @@ __device__ __forceinline__ void reduce_cells(DiffAcc &acc, const double (&a)[N],
     acc.merge(pm, s, am, pm >= 0.0 ? idx0 + found : kNoIndex, nf);
 }
 
+// The value reduced as `a` when the call has a source: fl(acc + f), one rounding on top of the sweep's bits -- the update rule
+// EPI_SOURCE of step_epilogue.h, which is what a plan that carries f as its source stores.  Without one, acc itself: "no
+// source" is not "add a zero" (-0.0 + 0.0 changes bits), so SRC = false never reaches an addition.
+template <bool SRC>
+__device__ __forceinline__ double with_source(double acc, double f) {
+    if constexpr (SRC) return step_epilogue<EPI_SOURCE>(acc, f, 0.0, 0.0, 0.0);
+    return acc;
+}
+
 // the workgroup's record into its own slot
 __device__ __forceinline__ void finish(DiffAcc &acc, ReduceRecord *__restrict__ partial) {
     wave_reduce(acc);
@@ -88,8 +101,11 @@ __device__ __forceinline__ void finish(DiffAcc &acc, ReduceRecord *__restrict__ 
 }
 
 // ---- 1D (kernels_1d.hip: stencil1d_kernel) -------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void residual1d_kernel(const double *__restrict__ in, const ResidualTiles rt, const Taps9 W,
-                                                              ReduceRecord *__restrict__ partial) {
+// SRC: f is read at the lane's own cells only -- padded index i + 4, even: one 16-byte piece, the odd tail point by one
+// 8-byte load -- under the predicate that guards reduce_cells, so no halo cell of f is ever loaded.
+template <bool SRC>
+__global__ __launch_bounds__(kThreads) void residual1d_kernel(const double *__restrict__ in, const double *__restrict__ f, const ResidualTiles rt,
+                                                              const Taps9 W, ReduceRecord *__restrict__ partial) {
     DiffAcc acc;
     acc.init();
     for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
@@ -99,6 +115,7 @@ __global__ __launch_bounds__(kThreads) void residual1d_kernel(const double *__re
         const int left = o[2] + n[2] - i;
         if (left <= 0) continue;
         double win[10];
+        d2 fv = {0.0, 0.0};
         if (left >= 2) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) {
@@ -106,10 +123,12 @@ __global__ __launch_bounds__(kThreads) void residual1d_kernel(const double *__re
                 win[2 * q] = v.x;
                 win[2 * q + 1] = v.y;
             }
+            if constexpr (SRC) fv = *reinterpret_cast<const d2 *>(f + i + 4);
         } else {  // odd tail: one point, scalar loads stay inside the padded array
 #pragma unroll
             for (int q = 0; q < 9; ++q) win[q] = in[i + q];
             win[9] = 0.0;
+            if constexpr (SRC) fv.x = f[i + 4];
         }
         double a0 = 0.0, a1 = 0.0;
 #pragma unroll
@@ -117,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void residual1d_kernel(const double *__re
             a0 = fma(W.w[q], win[q], a0);
             a1 = fma(W.w[q], win[q + 1], a1);
         }
-        const double a[2] = {a0, a1}, b[2] = {win[4], win[5]};
+        const double a[2] = {with_source<SRC>(a0, fv.x), with_source<SRC>(a1, fv.y)}, b[2] = {win[4], win[5]};
         reduce_cells<2>(acc, a, b, left >= 2 ? 2 : 1, (long long) i + 4);
     }
     finish(acc, partial);
@@ -128,14 +147,17 @@ constexpr int kTileW = 128;
 constexpr int kLdsW = kTileW + 8;
 constexpr int kChunksPerRow = kLdsW / 2;
 
-template <int TAPSET>
-__global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *__restrict__ in, const ResidualTiles rt, const Taps49 W,
-                                                                 ReduceRecord *__restrict__ partial) {
+// SRC: a lane's 16-byte piece of f of an output row (the row's two own cells) is issued four window rows before that row
+// completes, so at most four pieces are in flight; each is predicated as the reduce_cells call it feeds.
+template <int TAPSET, bool SRC>
+__global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *__restrict__ in, const double *__restrict__ f,
+                                                                 const ResidualTiles rt, const Taps49 W, ReduceRecord *__restrict__ partial) {
     constexpr int RPT = 8;
     constexpr int TH = 4 * RPT;
     constexpr int LH = TH + 6;
     constexpr int NCHUNK = LH * kChunksPerRow;
     constexpr int NIT = (NCHUNK + 255) / 256;
+    constexpr int kAhead = 4;  // window rows between the load of a row's piece of f and its use: 6 (and all eight up front) spill at three workgroups per CU
     __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
 
     const int tid = threadIdx.x;
@@ -148,6 +170,8 @@ __global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *_
         int o[3], nn[3];
         residual_tile_box(rt, t, o, nn);
         const int i0 = o[1], j0 = o[2], row_end = o[1] + nn[1];
+        const int col = j0 + 2 * lane;
+        d2 fv[SRC ? RPT : 1] = {};
         // ---- stage the input window: padded rows i0+1 .. i0+TH+6, padded columns j0 .. j0+135 (clamped into the array)
         {
             d2 stage[NIT];
@@ -180,7 +204,6 @@ __global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *_
             acc1[r] = 0.0;
         }
         const double *strip = tile + (wv * RPT) * kLdsW + 2 * lane;
-        const int col = j0 + 2 * lane;
         d2 cur[5], nxt[5];
 #pragma unroll
         for (int q = 0; q < 5; ++q) cur[q] = *reinterpret_cast<const d2 *>(strip + 2 * q);
@@ -189,6 +212,13 @@ __global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *_
             if (j + 1 < RPT + 6) {
 #pragma unroll
                 for (int q = 0; q < 5; ++q) nxt[q] = *reinterpret_cast<const d2 *>(strip + (j + 1) * kLdsW + 2 * q);
+            }
+            if constexpr (SRC) {  // the piece of f of output row j - 6 + kAhead, which completes kAhead window rows from here
+                const int r = j - 6 + kAhead;
+                if (r >= 0 && r < RPT) {
+                    const int row = i0 + wv * RPT + r;
+                    if (col < n && row < row_end) fv[r] = *reinterpret_cast<const d2 *>(f + (size_t) (row + 4) * ld + (col + 4));
+                }
             }
             double win[10];
 #pragma unroll
@@ -221,7 +251,8 @@ __global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *_
                 const int row = i0 + wv * RPT + r;
                 if (col < n && row < row_end) {  // (n and col are even: both cells or none)
                     const d2 c = *reinterpret_cast<const d2 *>(strip + (r + 3) * kLdsW + 4);
-                    const double a[2] = {acc0[r], acc1[r]}, b[2] = {c.x, c.y};
+                    const d2 fr = fv[SRC ? r : 0];
+                    const double a[2] = {with_source<SRC>(acc0[r], fr.x), with_source<SRC>(acc1[r], fr.y)}, b[2] = {c.x, c.y};
                     reduce_cells<2>(dacc, a, b, 2, (long long) (row + 4) * ld + (col + 4));
                 }
             }
@@ -240,9 +271,15 @@ __host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
     return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
 }
 
-template <int TAPSET>
-__global__ __launch_bounds__(kThreads, 4) void residual3d_kernel(const double *__restrict__ in, const ResidualTiles rt, const Taps27 W,
-                                                                 ReduceRecord *__restrict__ partial) {
+// SRC: the four 16-byte pieces of f of output plane o = p - 2 (one per row of the lane, at its two own cells) are issued at
+// the head of consume(p), beside the next plane's loads, and used in its epilogue; predicated as the reduce_cells they feed.
+// Eight more live registers through the tap loop: SRC = true is bounded to three workgroups per CU, as the 3D source step.
+// The launch is still cut by residual_tiles.h's 3D cap of 1024 workgroups (four per CU of 256): with SRC a quarter of them
+// waits for a slot when the region has that many tiles.
+template <int TAPSET, bool SRC>
+__global__ __launch_bounds__(kThreads, SRC ? 3 : 4) void residual3d_kernel(const double *__restrict__ in, const double *__restrict__ f,
+                                                                           const ResidualTiles rt, const Taps27 W,
+                                                                           ReduceRecord *__restrict__ partial) {
     constexpr int RY = 4;
     constexpr int TY = 4 * RY;
     constexpr int LH = TY + 2;
@@ -311,6 +348,16 @@ __global__ __launch_bounds__(kThreads, 4) void residual3d_kernel(const double *_
             constexpr int PHASE = decltype(phase_tag)::value;
             const bool more = p + 1 < nplanes;
             if (more) load_plane(p + 1);
+            d2 fv[SRC ? RY : 1] = {};
+            if constexpr (SRC) {
+                if (p >= 2 && p - 2 < zc && col_ok) {
+                    const double *fp = f + (long) (k0 + p - 1) * plane + cell0;  // (p >= 2: a plane inside d_f)
+#pragma unroll
+                    for (int r = 0; r < RY; ++r) {
+                        if (i0 + wv * RY + r < row_end) fv[r] = *reinterpret_cast<const d2 *>(fp + (long) r * ld);
+                    }
+                }
+            }
             const double *strip = &tile[p & 1][strip_off];
 #pragma unroll
             for (int j = 0; j < RY + 2; ++j) {
@@ -357,7 +404,8 @@ __global__ __launch_bounds__(kThreads, 4) void residual3d_kernel(const double *_
                     for (int r = 0; r < RY; ++r) {
                         if (i0 + wv * RY + r < row_end) {
                             const d2 c = *reinterpret_cast<const d2 *>(centre + r * kLdsW);
-                            const double a[2] = {acc0[s][r], acc1[s][r]}, b[2] = {c.x, c.y};
+                            const d2 fr = fv[SRC ? r : 0];
+                            const double a[2] = {with_source<SRC>(acc0[s][r], fr.x), with_source<SRC>(acc1[s][r], fr.y)}, b[2] = {c.x, c.y};
                             reduce_cells<2>(dacc, a, b, 2, base + (long) r * ld);
                         }
                     }
@@ -620,10 +668,41 @@ void launch_bf16(const Plan &p, const ResidualTiles &rt, const void *in, ReduceR
 
 }  // namespace
 
-hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, ReduceRecord *partial, hipStream_t s) {
-    if (!has_fused_residual(p) || rt.groups < 1 || rt.groups > kReduceMaxGroups) return hipErrorInvalidValue;
-    const double *din = static_cast<const double *>(in);
+namespace {
+
+template <bool SRC>
+void launch_f64(const Plan &p, const ResidualTiles &rt, const double *din, const double *f, ReduceRecord *partial, hipStream_t s) {
     const dim3 grid((unsigned) rt.groups), block(kThreads);
+    if (p.ndim == 1) {
+        Taps9 w;
+        for (int k = 0; k < 9; ++k) w.w[k] = p.w[k];
+        hipLaunchKernelGGL(residual1d_kernel<SRC>, grid, block, 0, s, din, f, rt, w, partial);
+    } else if (p.ndim == 2) {
+        Taps49 w;
+        for (int k = 0; k < 49; ++k) w.w[k] = p.w[k];
+        if (p.tapset == TAPS2D_DIAMOND)
+            hipLaunchKernelGGL((residual2d_kernel<TAPS2D_DIAMOND, SRC>), grid, block, 0, s, din, f, rt, w, partial);
+        else if (p.tapset == TAPS2D_STAR)
+            hipLaunchKernelGGL((residual2d_kernel<TAPS2D_STAR, SRC>), grid, block, 0, s, din, f, rt, w, partial);
+        else
+            hipLaunchKernelGGL((residual2d_kernel<TAPS2D_BOX, SRC>), grid, block, 0, s, din, f, rt, w, partial);
+    } else {
+        Taps27 w;
+        for (int k = 0; k < 27; ++k) w.w[k] = p.w[k];
+        if (p.tapset == TAPS3D_STAR)
+            hipLaunchKernelGGL((residual3d_kernel<TAPS3D_STAR, SRC>), grid, block, 0, s, din, f, rt, w, partial);
+        else
+            hipLaunchKernelGGL((residual3d_kernel<TAPS3D_BOX, SRC>), grid, block, 0, s, din, f, rt, w, partial);
+    }
+}
+
+}  // namespace
+
+// f: the source of `a = sweep(in) + f` (fp64 plans only), nullptr = none -- the kernels without the operand
+hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, const double *f, ReduceRecord *partial, hipStream_t s) {
+    if (!has_fused_residual(p) || rt.groups < 1 || rt.groups > kReduceMaxGroups) return hipErrorInvalidValue;
+    if (f && p.dtype == LORA_BF16) return hipErrorInvalidValue;
+    const double *din = static_cast<const double *>(in);
     if (p.dtype == LORA_BF16) {
         if (p.tapset == TAPS3D_SEP)
             launch_bf16<TAPS3D_SEP>(p, rt, in, partial, s);
@@ -631,26 +710,10 @@ hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *i
             launch_bf16<TAPS3D_STAR>(p, rt, in, partial, s);
         else
             launch_bf16<TAPS3D_BOX>(p, rt, in, partial, s);
-    } else if (p.ndim == 1) {
-        Taps9 w;
-        for (int k = 0; k < 9; ++k) w.w[k] = p.w[k];
-        hipLaunchKernelGGL(residual1d_kernel, grid, block, 0, s, din, rt, w, partial);
-    } else if (p.ndim == 2) {
-        Taps49 w;
-        for (int k = 0; k < 49; ++k) w.w[k] = p.w[k];
-        if (p.tapset == TAPS2D_DIAMOND)
-            hipLaunchKernelGGL(residual2d_kernel<TAPS2D_DIAMOND>, grid, block, 0, s, din, rt, w, partial);
-        else if (p.tapset == TAPS2D_STAR)
-            hipLaunchKernelGGL(residual2d_kernel<TAPS2D_STAR>, grid, block, 0, s, din, rt, w, partial);
-        else
-            hipLaunchKernelGGL(residual2d_kernel<TAPS2D_BOX>, grid, block, 0, s, din, rt, w, partial);
+    } else if (f) {
+        launch_f64<true>(p, rt, din, f, partial, s);
     } else {
-        Taps27 w;
-        for (int k = 0; k < 27; ++k) w.w[k] = p.w[k];
-        if (p.tapset == TAPS3D_STAR)
-            hipLaunchKernelGGL(residual3d_kernel<TAPS3D_STAR>, grid, block, 0, s, din, rt, w, partial);
-        else
-            hipLaunchKernelGGL(residual3d_kernel<TAPS3D_BOX>, grid, block, 0, s, din, rt, w, partial);
+        launch_f64<false>(p, rt, din, nullptr, partial, s);
     }
     if (hipError_t e = hipGetLastError()) return e;
     return launch_reduce_fold_cells(rt.groups, partial, s);

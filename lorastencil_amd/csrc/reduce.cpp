@@ -1,5 +1,5 @@
 // reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip) and what is built on them: lora_plan_stats,
-// lora_plan_diff, lora_plan_residual (kernels_residual.hip), lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until and its group-A form.
+// lora_plan_diff, lora_plan_residual and lora_plan_residual_src (kernels_residual.hip), lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until and its group-A form.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -152,14 +152,15 @@ int diff_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, int
     return LORA_OK;
 }
 
-// one raw sweep of d_in against d_in over [begin, end) (a proper range of a plan that has the kernel): the folded record (blocks)
-int residual_range(lora_plan *plan, const void *d_in, int begin, int end, lora_grid_diff *out, hipStream_t s) {
+// one raw sweep of d_in (plus d_f, where given) against d_in over [begin, end) (a proper range of a plan that has the
+// kernel): the folded record (blocks)
+int residual_range(lora_plan *plan, const void *d_in, const void *d_f, int begin, int end, lora_grid_diff *out, hipStream_t s) {
     const Plan &p = plan->p;
     ResidualTiles rt;
     if (!residual_tiles_setup(rt, p, begin, end)) return LORA_EINVAL;
     ReduceRecord *records = nullptr;
     if (int rc = ensure_records(plan, &records)) return rc;
-    const hipError_t e = launch_residual(p, rt, d_in, records, s);
+    const hipError_t e = launch_residual(p, rt, d_in, static_cast<const double *>(d_f), records, s);
     if (e != hipSuccess) {
         set_last_error("residual kernel launch", e);
         return LORA_EHIP;
@@ -182,6 +183,9 @@ int no_residual_kernel() {
 }  // namespace
 
 int admit_reduction(const void *a, const void *b, hipStream_t s) { return admit(a, b, s); }
+int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s) {
+    return residual_range(plan, d_in, d_f, 0, plan->p.dims[0], out, s);
+}
 int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s) {
     return diff_range(plan, d_a, d_b, 0, plan->p.dims[0], out, s);
 }
@@ -233,7 +237,32 @@ int lora_plan_residual(lora_plan *plan, const void *d_in, int begin, int end, lo
     if (int rc = lora::admit(d_in, d_in, s)) return rc;
     *out = {0.0, 0.0, 0.0, -1, 0, 0};
     if (!some) return LORA_OK;
-    return lora::residual_range(plan, d_in, begin, end, out, s);
+    return lora::residual_range(plan, d_in, nullptr, begin, end, out, s);
+}
+
+int lora_plan_residual_src(lora_plan *plan, const void *d_in, const void *d_f, int begin, int end, lora_grid_diff *out, void *stream) {
+    if (!d_f) return lora_plan_residual(plan, d_in, begin, end, out, stream);
+    if (!plan || !d_in || !out) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::resolve_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p) || d_f == d_in) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_in, d_f)) return rc;
+    // no kernel, bf16, a plan with a source -- all LORA_EUNSUPPORTED.  A plan with a source also reads "fused_residual" 0; it
+    // gets the text that names the cause
+    if (!p.source && !lora::has_fused_residual(p)) return lora::no_residual_kernel();
+    if (p.dtype == LORA_BF16) {
+        lora::set_last_error_text("a source is fp64: bf16 plans have no fused residual with a source");
+        return LORA_EUNSUPPORTED;
+    }
+    if (p.source) {
+        lora::set_last_error_text("a plan with a source has no fused residual kernel: the source of lora_plan_residual_src is a call argument");
+        return LORA_EUNSUPPORTED;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit(d_in, d_f, s)) return rc;
+    *out = {0.0, 0.0, 0.0, -1, 0, 0};
+    if (!some) return LORA_OK;
+    return lora::residual_range(plan, d_in, d_f, begin, end, out, s);
 }
 
 // Test support (no device): which cells the workgroups of lora_plan_residual's launch reduce -- residual_tiles.h replayed.
@@ -297,7 +326,7 @@ int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_
         if (p.boundary == LORA_BC_PERIODIC)
             if (int rc = lora_plan_halo(plan, d_buf0, nullptr, LORA_HALO_WRAP, stream)) return rc;
         if (fused) {
-            if (int rc = lora::residual_range(plan, d_buf0, 0, p.dims[0], &r->last, s)) return rc;
+            if (int rc = lora::residual_range(plan, d_buf0, nullptr, 0, p.dims[0], &r->last, s)) return rc;
         } else {
             if (int rc = lora_plan_step(plan, d_buf0, d_buf1, stream)) return rc;
             if (int rc = lora::diff_range(plan, d_buf1, d_buf0, 0, p.dims[0], &r->last, s)) return rc;

@@ -10,6 +10,9 @@
 // tiles g, g + G, g + 2 G, ... in that order into ONE record.  Nothing here looks at a tuning option or at the device, so
 // the order in which every cell enters the sums is a function of dtype, extents and region alone.  The cap is the number
 // of workgroups resident at once on 256 CUs (2D: three per CU by its 41 KB of LDS, else four), never above kReduceMaxGroups.
+// One launch does not fit its cap: the 3D fp64 kernels with a source operand (lora_plan_residual_src) are bounded to three
+// workgroups per CU by their registers, so of 1024 workgroups 768 are resident and the rest follow as slots free up.  The cap
+// stays 1024 there too: the tiles a workgroup walks, and so the order of every sum, do not depend on whether f is given.
 //
 // The decode is plain integer arithmetic: the kernels run it, and lora_debug_residual_cover replays it on the host.
 #pragma once

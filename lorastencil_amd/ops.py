@@ -676,7 +676,9 @@ class Plan:
                             max_times: int = 6000, stream=None) -> "UntilResult":
         """Chebyshev steps in runs of ``check_every`` until the TRUE residual max|S(u) + f - u| is <= tol + rtol * max|S(u) + f|
         (lora_plan_run_chebyshev_until); ``d_cur`` (level 0 going in; ``d_prev`` any finite values) then holds level
-        ``times_done``, bit for bit what ``run_leapfrog_src`` with ``chebyshev_coeffs(rho, 1, times_done)`` gives."""
+        ``times_done``, bit for bit what ``run_leapfrog_src`` with ``chebyshev_coeffs(rho, 1, times_done)`` gives.  The probe:
+        under ``norm="max"`` on a plan whose option "fused_residual" reads 1, one ``residual_src(d_cur, d_f)`` (no third grid);
+        under ``norm="rms"`` and on plans without that kernel, a source sweep into a grid the plan owns plus ``diff``."""
         u, r = _until_arg(tol, rtol, norm, check_every, max_times), _lib.UntilResult()
         check(_lib.lib().lora_plan_run_chebyshev_until(self._h, _ptr(d_prev), _ptr(d_cur), _optr(d_f), float(rho), ctypes.byref(u),
                                                        ctypes.byref(r), _stream(stream)), "lora_plan_run_chebyshev_until")
@@ -704,6 +706,16 @@ class Plan:
         out = _lib.GridDiff()
         check(_lib.lib().lora_plan_residual(self._h, _ptr(d_in), int(begin), int(end), ctypes.byref(out), _stream(stream)),
               "lora_plan_residual")
+        return _tuple_of(GridDiff, out)
+
+    def residual_src(self, d_in, d_f, begin: int = 0, end: int = 0, stream=None) -> GridDiff:
+        """The TRUE residual of u = S(u) + f, d = (sweep(d_in) + d_f) - d_in, over the outermost range [begin, end), reduced inside
+        the sweep (lora_plan_residual_src): ``d_in`` and the interior of ``d_f`` are read once and nothing is written.  ``d_f`` is
+        an argument, never the plan's source; ``None`` passes NULL, which is exactly ``residual``.  The exact fields equal a
+        source sweep into a second buffer followed by ``diff``."""
+        out = _lib.GridDiff()
+        check(_lib.lib().lora_plan_residual_src(self._h, _ptr(d_in), _optr(d_f), int(begin), int(end), ctypes.byref(out),
+                                                _stream(stream)), "lora_plan_residual_src")
         return _tuple_of(GridDiff, out)
 
     def run_until(self, d_buf0, d_buf1, tol: float, rtol: float = 0.0, norm="max", check_every: int = 60, max_times: int = 6000,
