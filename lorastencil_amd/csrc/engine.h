@@ -240,7 +240,7 @@ inline bool has_fused_residual(const Plan &p) {
 // a = sweep(in), or with `f` (fp64 plans only; nullptr = none) a = fl(sweep(in) + f), f read at the reduced cells alone.
 hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, const double *f, ReduceRecord *partial, hipStream_t s);
 
-// ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_source.hip: two, 2D) -------
+// ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_step2.hip: two, 2D) -------
 // Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
 hipError_t launch_source(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
 hipError_t launch_source2(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
@@ -252,7 +252,7 @@ inline bool source_fuses_two(const Plan &p) {
     return p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT && !p.generic && p.boundary != LORA_BC_PERIODIC && p.steps_per_launch_req != 1;
 }
 
-// ---- leapfrog steps, prev <- S(cur) + c prev in place (kernels_step.hip: one step; kernels_2d_leapfrog.hip: two, 2D) --------
+// ---- leapfrog steps, prev <- S(cur) + c prev in place (kernels_step.hip: one step; kernels_2d_step2.hip: two, 2D) --------
 // Picked by the leapfrog entries of leapfrog.cpp and by nothing else.
 hipError_t launch_leapfrog(const Plan &p, const double *cur, double *prev, double c, int begin, int end, hipStream_t s);
 hipError_t launch_leapfrog2(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
@@ -265,7 +265,7 @@ inline int leapfrog_depth(const Plan &p) {
 }
 
 // ---- scaled leapfrog steps with a source, prev <- a (S(cur) + f) + c prev (kernels_step.hip: one step;
-// kernels_2d_leapfrog_src.hip: two, 2D).  f is a call argument (nullptr = none), never the plan's source; the plans are those
+// kernels_2d_step2.hip: two, 2D).  f is a call argument (nullptr = none), never the plan's source; the plans are those
 // of leapfrog_depth().  Picked by the *_leapfrog_src entries of leapfrog.cpp and by nothing else.
 hipError_t launch_leapfrog_src(const Plan &p, const double *cur, double *prev, const double *f, double a, double c, int begin, int end,
                                hipStream_t s);

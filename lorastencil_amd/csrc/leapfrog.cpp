@@ -1,5 +1,5 @@
 // leapfrog.cpp -- the leapfrog entries of the C ABI (include/lorastencil.h): u(t+1) = S(u(t)) + c u(t-1), the new level stored
-// over the oldest one.  One step in place (kernels_step.hip), two steps per launch in 2D (kernels_2d_leapfrog.hip), the
+// over the oldest one.  One step in place (kernels_step.hip), two steps per launch in 2D (kernels_2d_step2.hip), the
 // run driver and the host-buffer operator.  `c` and the buffers are call arguments: nothing here changes what a plan resolves
 // to, and no run is cached in a graph.
 #include <hip/hip_runtime.h>

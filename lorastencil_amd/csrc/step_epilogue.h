@@ -1,7 +1,6 @@
 // step_epilogue.h -- the ONE definition of what a step kernel does with a finished tap sum, and of the direct tap loop of
-// the 2D two-step kernels.  Shared by kernels_step.hip (one step per launch) and kernels_2d_source.hip,
-// kernels_2d_leapfrog.hip, kernels_2d_leapfrog_src.hip (two per launch): "a two-step launch equals two single steps bit for
-// bit" holds because both sides call these functions.
+// the 2D two-step kernel.  Shared by kernels_step.hip (one step per launch) and kernels_2d_step2.hip (two per
+// launch): "a two-step launch equals two single steps bit for bit" holds because both sides call these functions.
 #pragma once
 
 #include "device_common.h"

@@ -1,5 +1,5 @@
 """GPU tests of leapfrog stepping (lora_plan_step_leapfrog ... lora_run_host_leapfrog; kernels_step.hip,
-kernels_2d_leapfrog.hip): u(t+1) = S(u(t)) + c u(t-1), the new level stored over the oldest one.
+kernels_2d_step2.hip): u(t+1) = S(u(t)) + c u(t-1), the new level stored over the oldest one.
 
 Contract under test: one step is prev = fl(acc + fl(c * prev)) on the interior cells of the swept range, acc the bits of the
 plan's plain single sweep of cur, in two roundings; halo cells of prev never written and never used, cur never written; the 2D
@@ -12,7 +12,7 @@ are intact and every read-only buffer is unchanged bit for bit.
 
 Shapes: the cases, regions and offsets of tests/test_gpu_source.py -- the single-step kernels have the tiles of the source
 kernels (1D 512 points per workgroup; 2D 32 rows x 128 columns; 3D 16 rows x 128 columns x chunks of 4 planes; odd innermost
-extents one thread per point) and the two-step kernel those of stencil2d_source2_kernel (4 R1 - 6 rows x 122 columns, R1 = 6
+extents one thread per point) and the two-step kernel those of the source rule's (4 R1 - 6 rows x 122 columns, R1 = 6
 for the star, 10 for diamond and box):
   one cell                      (1,)       (1, 2)       (1, 1, 2)
   partial tile + two tiles per direction, regions that begin and end inside a tile, the empty region

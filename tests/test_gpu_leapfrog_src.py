@@ -1,5 +1,5 @@
 """GPU tests of the scaled leapfrog step with a source and of the Chebyshev semi-iteration built on it (lora_plan_step_leapfrog_src
-... lora_run_host_chebyshev; kernels_step.hip, kernels_2d_leapfrog_src.hip, chebyshev.cpp):
+... lora_run_host_chebyshev; kernels_step.hip, kernels_2d_step2.hip, chebyshev.cpp):
 u+ = a (S(u) + f) + c u-, the new level stored over the oldest one.
 
 Contract under test: one step is t = fl(acc + f) (no f: t = acc), prev = fl(fl(a t) + fl(c prev)) on the interior cells of the swept

@@ -1,4 +1,4 @@
-"""GPU tests of the source term (lora_plan_set_source; kernels_step.hip, kernels_2d_source.hip): u <- S(u) + f.
+"""GPU tests of the source term (lora_plan_set_source; kernels_step.hip, kernels_2d_step2.hip): u <- S(u) + f.
 
 Contract under test: out = fl(acc + f) on the interior cells of the swept range, acc the bits of the plan's plain single sweep;
 halo cells of out never written, halo cells of f never used, f never written; two applications per launch (2D) equal two single
@@ -13,7 +13,7 @@ Shapes, from the tile constants as built:
                  kTileW = 128).  3D: 16 rows x 128 columns x chunks of 4 planes on grids this small (kRY = 4; the chunk rule
                  16 -> 7 -> 4 of launch_step3d).  Odd innermost extents: one thread per point, blocks of 4 rows x 64 columns.
   two per launch 2D: 4 R1 - 6 rows x 122 columns, R1 = 6 for the star (18 rows), 10 for diamond and box (34 rows)
-                 (kernels_2d_source.hip: launch_source2).
+                 (kernels_2d_step2.hip: launch_source2).
   one cell                      (1,)       (1, 2)       (1, 1, 2)
   partial tile + two tiles per direction, regions that begin and end inside a tile, the empty region
                                 (1027,) = 2 x 512 + 3, with the odd tail point

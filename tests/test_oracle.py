@@ -11,6 +11,7 @@ from oracle import oracle as o
 
 def test_rng_matches_libc_rand():
     libc = ctypes.CDLL("libc.so.6")
+    libc.srand(1)  # the default seed, whatever drew from the process-wide generator before this test
     r = o.Rng()
     assert [r.next() for _ in range(5000)] == [libc.rand() for _ in range(5000)]
 

@@ -9,7 +9,7 @@ bar is against code this change does not touch, with the 10 % margin section 3.5
   single step      lora_plan_step_leapfrog_src with f / without f / lora_plan_step_leapfrog (the yardstick) / that once more (the
                    spread).  Bars: with f <= 4/3 x leapfrog x 1.10 (four grids of traffic against three); without f <= leapfrog
                    x 1.10.
-  two per launch   2D only: lora_plan_step2_leapfrog_src with f / a stencil2d_leapfrog2_kernel launch / that once more / two single
+  two per launch   2D only: lora_plan_step2_leapfrog_src with f / a lora_plan_step2_leapfrog launch / that once more / two single
                    steps with f.  Bars: <= 5/4 x leapfrog2 x 1.10 (five grids against four), and faster than two single steps by
                    more than the spread.
   solve            star2d1r 2048^2 (--small: 256^2), 5-point Jacobi taps, zero halos, f = 0.125: steps and wall time to
