@@ -224,6 +224,9 @@ const double *lora_set_default_source(const double *padded_host_source);
  * than the fp64 range of the reference's integer taps allows stay finite (box2d3r overflows at step ~129, SURVEY B7;
  * BASELINE config 3 asks for 200).  Not reference behaviour.  Returns the previous value. */
 int lora_set_default_normalize(int on);
+/* Option "leap3" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_leapfrog and
+ * lora_run_host_chebyshev (what lorastencil_3d's --leap3 flag sets).  Returns the previous value. */
+int lora_set_default_leap3(int on);
 /* Integer options.  Results never depend on them except where stated.
  *   steps_per_launch  0 auto / 1 / 2 (2D also 4 with the row-streaming kernel and 6 with the workgroup-row kernel, 3D fp64
  *                     also 3 with the plane-streaming kernel, 1D also 4, 8, 16, 32) : applications per launch in
@@ -236,6 +239,12 @@ int lora_set_default_normalize(int on);
  *                     nested-profile form) : structured evaluation of the taps inside the fused 2D kernels (summation
  *                     order changes: identical while values are exact integers, ~1 ulp afterwards)
  *   z_chunk, fused_z_chunk             3D output planes per workgroup (single-sweep / fused kernels; 0 = auto)
+ *   leap3             0 (default) / 1 : 3D fp64 plans with an even innermost extent and no source get the two-step leapfrog
+ *                     launch (kernels_3d_step2.hip; lora_plan_leapfrog_depth reads 2, the lora_plan_step2_leapfrog* entries
+ *                     work, leapfrog and Chebyshev runs take pairs of launches).  Any non-zero value reads back as 1; no
+ *                     effect on other plans, and none on the kernel name, signature or depth of the plain sweeps.  Same
+ *                     bits either way.  Measured: a launch takes 0.72 - 0.89 of the time
+ *                     of two single steps, a run of 120 steps 0.79 - 0.95; off until the default is decided on those figures
  *   stream3           3D fp64 fused launches: 1 = plane-streaming kernel (kernels_3d_planes.hip: LDS-DMA plane ring, three
  *                     applications per launch for the 7-point star, two for the box), 0 = the two-application tile kernel,
  *                     -1 (default) = by grid size: three applications from ~1.2e8 points (star), the plane-streaming
@@ -376,7 +385,8 @@ int lora_plan_run_profiled(lora_plan *plan, void *d_buf0, void *d_buf1, int time
  * LORA_ENODEVICE when the launch fails for want of a device.  All entries are asynchronous on `stream`. */
 /* 0: the plan has no leapfrog kernel (LORA_BF16 plans, 2D plans of LORA_VARIANT_MFMA, plans that currently carry a source);
  * 1: single steps (every other plan); 2: also the two-step launch (2D plans of the direct variant with an even innermost
- * extent).  A function of the plan alone; needs no device. */
+ * extent; 3D plans with an even innermost extent on which option "leap3" is 1 -- without the option a 3D plan reads 1).  A
+ * function of the plan alone; needs no device. */
 int lora_plan_leapfrog_depth(const lora_plan *plan);
 /* One step, in place: on every interior cell of the swept range d_prev = fl(acc + fl(c * d_prev)), where acc has exactly the
  * bits the plan's plain single sweep from d_cur stores, c * d_prev is one fp64 multiplication and + one separate fp64
@@ -390,7 +400,11 @@ int lora_plan_step_leapfrog_region(lora_plan *plan, const void *d_cur, void *d_p
  * d_out2 = S(d_out1) + c d_cur on the interior cells of rows [begin, end); the four buffers are pairwise distinct.  Level-1
  * cells outside the interior take the value d_prev holds there (the halo of the buffer the level would live in under the
  * in-place entry), so a launch equals two single steps bit for bit on any data; direct taps in row-major order at both levels
- * whatever option "lowrank_valu" says.  Halo cells of d_out1 / d_out2 are never written, d_prev and d_cur never at all. */
+ * whatever option "lowrank_valu" says.  Halo cells of d_out1 / d_out2 are never written, d_prev and d_cur never at all.
+ *   3D (option "leap3"): the same contract with [begin, end) counting planes.  Level 1 is computed on the interior cells of
+ * planes begin - 1 .. end (stored to d_out1 on [begin, end) only); the ring of level-1 cells around the interior, one cell wide,
+ * takes d_prev's halo values; the taps are applied in the single step's order (dz, dy, dx ascending).  The chunk length along z
+ * is option "fused_z_chunk" (0 = automatic); it moves no bit. */
 int lora_plan_step2_leapfrog(lora_plan *plan, const void *d_prev, const void *d_cur, void *d_out1, void *d_out2, double c,
                              void *stream);
 int lora_plan_step2_leapfrog_region(lora_plan *plan, const void *d_prev, const void *d_cur, void *d_out1, void *d_out2, double c,
@@ -434,7 +448,8 @@ int lora_plan_step_leapfrog_src_region(lora_plan *plan, const void *d_cur, void 
  * d_out2 = a2 (S(d_out1) + f) + c2 d_cur on the interior cells of rows [begin, end), with the rounding rule above at both
  * levels; the buffers are pairwise distinct.  Level-1 cells outside the interior take the value d_prev holds there; direct taps
  * in row-major order at both levels whatever option "lowrank_valu" says: a launch equals two single steps bit for bit on any
- * data.  Halo cells of d_out1 / d_out2 are never written, d_prev, d_cur and d_f never at all. */
+ * data.  Halo cells of d_out1 / d_out2 are never written, d_prev, d_cur and d_f never at all.  3D plans with option "leap3":
+ * as lora_plan_step2_leapfrog states it, in planes; d_f is read on interior cells alone, at both levels. */
 int lora_plan_step2_leapfrog_src(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1, void *d_out2,
                                  double a1, double c1, double a2, double c2, void *stream);
 int lora_plan_step2_leapfrog_src_region(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_f, void *d_out1,

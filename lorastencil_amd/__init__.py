@@ -39,6 +39,7 @@ from .ops import (  # noqa: F401
     run_host_leapfrog,
     run_host_until,
     separable_3x3x3,
+    set_default_leap3,
     set_default_source,
     stats_merge,
     svd_7x7,

@@ -162,6 +162,7 @@ SIGNATURES = {
     "lora_plan_set_boundary": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lora_set_default_boundary": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_normalize": (ctypes.c_int, [ctypes.c_int]),
+    "lora_set_default_leap3": (ctypes.c_int, [ctypes.c_int]),
     "lora_plan_set_source": (ctypes.c_int, [_vp, _vp]),
     "lora_set_default_source": (_vp, [_vp]),
     "lora_plan_set_option": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),

@@ -21,6 +21,8 @@
 //   --source=point:V   ... f = V on the interior centre cell dims / 2 and 0 elsewhere
 //   --leapfrog[=C]     time_size leapfrog steps u(t+1) = S(u(t)) + C u(t-1) from u(-1) = u(0), i.e. zero initial velocity
 //                      (lora_run_host_leapfrog; default C = -1, the wave equation); one GPU, fp64
+//   --leap3            (lorastencil_3d only, with --leapfrog or --chebyshev) the run takes two leapfrog steps per launch
+//                      (lora_set_default_leap3; plan option leap3); same results, same output
 //   --chebyshev=RHO    solve u = S(u) + f by the Chebyshev semi-iteration for a spectrum of S inside [-RHO, RHO], 0 <= RHO < 1
 //                      (lora_run_host_chebyshev): time_size steps, or with --until=TOL until the true residual
 //                      max |S(u) + f - u| <= TOL (time_size is the cap); f from --source= when given; one GPU, fp64
@@ -148,6 +150,7 @@ int main(int argc, char *argv[]) {
     double leapfrog_c = -1.0;
     bool chebyshev = false;
     double chebyshev_rho = 0.0;
+    bool leap3 = false;
     lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -205,6 +208,8 @@ int main(int argc, char *argv[]) {
             }
             leapfrog = true;
         }
+        else if (a == "--leap3" && kDim == 3)
+            leap3 = true;
         else if (a.rfind("--chebyshev=", 0) == 0) {
             const std::string v = a.substr(12);
             char *rest = nullptr;
@@ -273,6 +278,12 @@ int main(int argc, char *argv[]) {
         std::cerr << "--chebyshev runs on one GPU in fp64 against its own residual: not with --gpus, --grid, --check, --leapfrog or --dtype=bf16\n";
         return 1;
     }
+
+    if (leap3 && !leapfrog && !chebyshev) {
+        std::cerr << "--leap3 chooses the launches of a leapfrog run: only with --leapfrog or --chebyshev\n";
+        return 1;
+    }
+    if (leap3) lora_set_default_leap3(1);
 
     if (until && (gpus_given || grid[0] > 0 || check)) {
         std::cerr << "--until runs on one GPU against its own residual: not with --gpus, --grid or --check\n";

@@ -110,6 +110,7 @@ struct Plan : Resolved {
     int stream3_slots = 0;    // 3D plane-streaming kernel: input plane slots of the LDS ring (0 or kStream3Slots: the one ring there is)
     int lanes3 = -1;          // 3D fused launches through the register-resident kernels (kernels_3d_lanes.hip, fp64; kernels_3d_bf16_lanes.hip, bf16: four applications per launch): -1 by grid size, 0 never, 1 always (star / separable box taps, reference boundary)
     int fused_z_chunk = 0;    // 3D fused: output planes per workgroup (0 = auto: 32, shorter on small grids)
+    int leap3 = 0;            // 3D fp64: leapfrog runs take the two-step launch (kernels_3d_step2.hip); no effect outside 3D
     int spans3 = -1;          // 3D register-resident kernels: cut the (tile, plane) line into equal pieces per CU (1), equal chunks per tile (0), by region depth (-1)
     int torus = 1;            // periodic boundary: runs in fused launches on a ghost-extended grid (1), single sweeps behind a wrap each (0)
     int steps_per_launch_req = 0;  // 0 = auto, 1, 2 (2D / 3D), 3 / 4 (3D), 4 / 6 (2D), 2 .. 32 (1D)
@@ -252,25 +253,40 @@ inline bool source_fuses_two(const Plan &p) {
     return p.ndim == 2 && p.variant == LORA_VARIANT_DIRECT && !p.generic && p.boundary != LORA_BC_PERIODIC && p.steps_per_launch_req != 1;
 }
 
-// ---- leapfrog steps, prev <- S(cur) + c prev in place (kernels_step.hip: one step; kernels_2d_step2.hip: two, 2D) --------
-// Picked by the leapfrog entries of leapfrog.cpp and by nothing else.
+// ---- leapfrog steps, prev <- S(cur) + c prev in place (kernels_step.hip: one step; two per launch: kernels_2d_step2.hip in
+// 2D, kernels_3d_step2.hip in 3D).  Picked by the leapfrog entries of leapfrog.cpp and by nothing else.
 hipError_t launch_leapfrog(const Plan &p, const double *cur, double *prev, double c, int begin, int end, hipStream_t s);
-hipError_t launch_leapfrog2(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
-                            int end, hipStream_t s);
+hipError_t launch_leapfrog2_2d(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
+                               int end, hipStream_t s);
+hipError_t launch_leapfrog2_3d(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
+                               int end, hipStream_t s);
+inline hipError_t launch_leapfrog2(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
+                                   int end, hipStream_t s) {
+    return p.ndim == 3 ? launch_leapfrog2_3d(p, prev, cur, out1, out2, c, begin, end, s)
+                       : launch_leapfrog2_2d(p, prev, cur, out1, out2, c, begin, end, s);
+}
 // 0: no leapfrog kernel (bf16, the 2D matrix-pipe variant, a plan with a source); 1: single steps; 2: also the two-step launch
-// (2D, direct variant, even innermost extent).
+// (2D: direct variant, even innermost extent; 3D: even innermost extent and option leap3 on).
 inline int leapfrog_depth(const Plan &p) {
     if (p.dtype != LORA_F64 || p.source || (p.ndim == 2 && p.variant != LORA_VARIANT_DIRECT)) return 0;
+    if (p.ndim == 3) return p.leap3 && !p.generic ? 2 : 1;
     return p.ndim == 2 && !p.generic ? 2 : 1;
 }
 
-// ---- scaled leapfrog steps with a source, prev <- a (S(cur) + f) + c prev (kernels_step.hip: one step;
-// kernels_2d_step2.hip: two, 2D).  f is a call argument (nullptr = none), never the plan's source; the plans are those
-// of leapfrog_depth().  Picked by the *_leapfrog_src entries of leapfrog.cpp and by nothing else.
+// ---- scaled leapfrog steps with a source, prev <- a (S(cur) + f) + c prev (kernels_step.hip: one step; two per launch:
+// kernels_2d_step2.hip, kernels_3d_step2.hip).  f is a call argument (nullptr = none), never the plan's source; the plans are
+// those of leapfrog_depth().  Picked by the *_leapfrog_src entries of leapfrog.cpp and by nothing else.
 hipError_t launch_leapfrog_src(const Plan &p, const double *cur, double *prev, const double *f, double a, double c, int begin, int end,
                                hipStream_t s);
-hipError_t launch_leapfrog2_src(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
-                                double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s);
+hipError_t launch_leapfrog2_src_2d(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
+                                   double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s);
+hipError_t launch_leapfrog2_src_3d(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
+                                   double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s);
+inline hipError_t launch_leapfrog2_src(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
+                                       double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s) {
+    return p.ndim == 3 ? launch_leapfrog2_src_3d(p, prev, cur, f, out1, out2, a1, c1, a2, c2, begin, end, s)
+                       : launch_leapfrog2_src_2d(p, prev, cur, f, out1, out2, a1, c1, a2, c2, begin, end, s);
+}
 
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,

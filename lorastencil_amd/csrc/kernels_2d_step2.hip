@@ -1,9 +1,9 @@
 // kernels_2d_step2.hip -- TWO applications per launch with an update rule at both stores, 2D fp64: ONE kernel
 // body, stencil2d_step2_kernel<TAPSET, R1, EPI>, whose rule EPI (step_epilogue.h) is a template parameter:
 //     EPI_SOURCE        level 1 = S(in) + f,               out  = S(level 1) + f             launch_source2 (plans with a source)
-//     EPI_LEAP          out1 = S(cur) + c prev,            out2 = S(out1) + c cur            launch_leapfrog2
-//     EPI_LEAP_SCALED   out1 = a1 S(cur) + c1 prev,        out2 = a2 S(out1) + c2 cur        launch_leapfrog2_src, f == nullptr
-//     EPI_LEAP_SRC      out1 = a1 (S(cur) + f) + c1 prev,  out2 = a2 (S(out1) + f) + c2 cur  launch_leapfrog2_src
+//     EPI_LEAP          out1 = S(cur) + c prev,            out2 = S(out1) + c cur            launch_leapfrog2_2d
+//     EPI_LEAP_SCALED   out1 = a1 S(cur) + c1 prev,        out2 = a2 S(out1) + c2 cur        launch_leapfrog2_src_2d, f == nullptr
+//     EPI_LEAP_SRC      out1 = a1 (S(cur) + f) + c1 prev,  out2 = a2 (S(out1) + f) + c2 cur  launch_leapfrog2_src_2d
 //
 // The tile (that of stencil2d_fused2_kernel, kernels_2d_fused.hip):
 //   output tile        TH = 4 R1 - 6 rows x 122 columns          (61 lanes x 2 columns; j0 = 122 tx is even)
@@ -355,9 +355,9 @@ hipError_t launch_source2(const Plan &p, const double *in, double *out, int begi
     return launch_step2(EPI_SOURCE, p, a, begin, end, s);
 }
 
-// Two leapfrog steps.
-hipError_t launch_leapfrog2(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
-                            int end, hipStream_t s) {
+// Two leapfrog steps (2D plans; launch_leapfrog2 of engine.h dispatches).
+hipError_t launch_leapfrog2_2d(const Plan &p, const double *prev, const double *cur, double *out1, double *out2, double c, int begin,
+                               int end, hipStream_t s) {
     ArgsStep2 a = {};
     a.prev = prev;
     a.cur = cur;
@@ -367,9 +367,9 @@ hipError_t launch_leapfrog2(const Plan &p, const double *prev, const double *cur
     return launch_step2(EPI_LEAP, p, a, begin, end, s);
 }
 
-// Two scaled leapfrog steps; f == nullptr: no source.
-hipError_t launch_leapfrog2_src(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
-                                double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s) {
+// Two scaled leapfrog steps; f == nullptr: no source (2D plans; launch_leapfrog2_src of engine.h dispatches).
+hipError_t launch_leapfrog2_src_2d(const Plan &p, const double *prev, const double *cur, const double *f, double *out1, double *out2,
+                                   double a1, double c1, double a2, double c2, int begin, int end, hipStream_t s) {
     ArgsStep2 a = {};
     a.prev = prev;
     a.cur = cur;

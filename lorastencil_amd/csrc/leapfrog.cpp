@@ -1,5 +1,6 @@
 // leapfrog.cpp -- the leapfrog entries of the C ABI (include/lorastencil.h): u(t+1) = S(u(t)) + c u(t-1), the new level stored
-// over the oldest one.  One step in place (kernels_step.hip), two steps per launch in 2D (kernels_2d_step2.hip), the
+// over the oldest one.  One step in place (kernels_step.hip), two steps per launch in 2D (kernels_2d_step2.hip) and, behind option leap3, in 3D
+// (kernels_3d_step2.hip), the
 // run driver and the host-buffer operator.  `c` and the buffers are call arguments: nothing here changes what a plan resolves
 // to, and no run is cached in a graph.
 #include <hip/hip_runtime.h>
@@ -53,7 +54,7 @@ int plan_refused(const Plan &p, bool two) {
     if (p.dtype != LORA_F64) return unsupported("bf16 plans have no leapfrog kernels");
     if (p.source) return unsupported("a plan with a source has no leapfrog kernels: remove the source first");
     if (p.ndim == 2 && p.variant != LORA_VARIANT_DIRECT) return unsupported("the 2D matrix-pipe variant has no leapfrog kernels");
-    if (two && leapfrog_depth(p) < 2) return unsupported("two leapfrog steps per launch: 2D plans of the direct variant with an even innermost extent");
+    if (two && leapfrog_depth(p) < 2) return unsupported("two leapfrog steps per launch: 2D plans of the direct variant, 3D plans with option leap3 = 1, each with an even innermost extent");
     return LORA_OK;
 }
 

@@ -18,6 +18,7 @@ namespace lora {
 
 static thread_local int g_default_boundary = LORA_BC_REFERENCE;
 static thread_local int g_default_normalize = 0;
+static thread_local int g_default_leap3 = 0;
 
 int region_granularity(const Plan &p) { return p.ndim == 1 ? 2 : 1; }  // 2D tiles and 3D chunks may start on any row / plane
 
@@ -492,6 +493,8 @@ const Option kOptions[] = {
     {"steps_per_launch", &Plan::steps_per_launch_req, &Plan::steps_per_launch, DEPTH, 0, {}},
     flag("fused_pipeline", &Plan::fused_pipeline),
     range("fused_z_chunk", &Plan::fused_z_chunk, 0, 4096),
+    // 3D fp64 leapfrog: two steps per launch (lora_plan_leapfrog_depth reads 2); chooses no kernel of the plain sweeps
+    flag("leap3", &Plan::leap3),
     range("spans3", &Plan::spans3, -1, 2),
     flag("torus", &Plan::torus),
     read_only("tapset", &Plan::tapset),
@@ -582,6 +585,7 @@ int lora_plan_create(lora_plan **out, int shape, int dtype, const int *dims, con
     p.variant = LORA_VARIANT_DIRECT;
     p.generic = odd_inner;
     p.boundary = lora::g_default_boundary;
+    p.leap3 = lora::g_default_leap3;
     if (nd == 3) {
         // enough workgroups to fill 256 CUs a few times over, chunks as long as that allows
         const long tiles = (long) ((dims[2] + 127) / 128) * ((dims[1] + 15) / 16);
@@ -625,6 +629,12 @@ int lora_set_default_boundary(int boundary) {
 int lora_set_default_normalize(int on) {
     const int old = lora::g_default_normalize;
     lora::g_default_normalize = on ? 1 : 0;
+    return old;
+}
+
+int lora_set_default_leap3(int on) {
+    const int old = lora::g_default_leap3;
+    lora::g_default_leap3 = on ? 1 : 0;
     return old;
 }
 

@@ -275,6 +275,12 @@ def set_default_source(source):
     return old
 
 
+def set_default_leap3(on) -> int:
+    """Plan option "leap3" (3D fp64: two leapfrog steps per launch) of the plans created afterwards on this thread, the ones of
+    run_host_leapfrog and run_host_chebyshev included (lora_set_default_leap3).  Returns the previous value."""
+    return _lib.lib().lora_set_default_leap3(1 if on else 0)
+
+
 class _with_source:
     """set the thread's default source for one host-operator call, restore the previous one afterwards"""
 
