@@ -1,17 +1,14 @@
-// capi.cpp -- implementation of the C ABI in include/lorastencil.h: the launch dispatcher, the time-step driver and the
-// host-buffer operators that stand in for the reference's gpu_*() functions.  (What a plan is and resolves to: plan.cpp.)
+// capi.cpp -- implementation of the C ABI in include/lorastencil.h: the launch dispatcher, the time-step driver, the holder of
+// the grids a plan owns (lora::DeviceGrid) and the plain host-buffer operator that stands in for the reference's gpu_*()
+// functions (its skeleton: hostrun.cpp).  (What a plan is and resolves to: plan.cpp.)
 //
 // Reference behaviour followed (file:line under /root/reference/src/):
-//   driver: buf0 <- padded input, buf1 <- 0, `times` launches ping-ponging, result = buf[times % 2],
-//           timing = steady_clock around the launch loop + one device sync
+//   driver: buf0 <- padded input, buf1 <- 0, `times` launches ping-ponging, result = buf[times % 2]
 //           (1d/gpu_1r.cu:103-134, 2d/gpu.cu:392-421, :450-479, :525-554, 3d/gpu_star.cu:158-192,
 //            3d/gpu_box.cu:190-223)
-//   stdout: label / "Time = <ms>[ms]" / "GStencil/s = %f" (e.g. 2d/gpu.cu:549-553)
 // There is deliberately no CPU fallback: without a HIP device every compute entry point fails.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -113,38 +110,12 @@ int launch_apps(const Plan &p, const Apps &a, const void *d_in, void *d_out, hip
         err = p.stream3_active ? launch_3d_stream(p, 2, in, out, in, 0, b, e, s) : launch_3d_fused2(p, in, out, b, e, s);
     if (err != hipSuccess) {
         set_last_error(n == 1 ? "kernel launch" : "fused kernel launch", err);
-        if (p.source && lora_device_count() <= 0) {
-            g_last_error = "no HIP device visible";
-            return LORA_ENODEVICE;
-        }
-        return LORA_EHIP;
+        return p.source && lora_device_count() <= 0 ? no_device() : LORA_EHIP;
     }
     return LORA_OK;
 }
 
 static thread_local const double *g_default_source = nullptr;
-
-// The thread's default source uploaded beside the grid and set on the plan of a host-buffer operator (fp64); freed with it.
-struct HostSource {
-    void *d = nullptr;
-    ~HostSource() {
-        if (d) (void) hipFree(d);
-    }
-};
-static int upload_default_source(lora_plan *plan, size_t bytes, HostSource &hs) {
-    if (!g_default_source) return LORA_OK;
-    if (hipMalloc(&hs.d, bytes) != hipSuccess) {
-        (void) hipGetLastError();
-        hs.d = nullptr;
-        return LORA_ENOMEM;
-    }
-    const hipError_t e = hipMemcpy(hs.d, g_default_source, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_last_error("source upload", e);
-        return LORA_EHIP;
-    }
-    return lora_plan_set_source(plan, hs.d);
-}
 
 int default_source_refused(const char *who) {
     if (!g_default_source) return LORA_OK;
@@ -152,16 +123,54 @@ int default_source_refused(const char *who) {
     return LORA_EUNSUPPORTED;
 }
 
+// The thread's default source uploaded beside the grid and set on the plan of a host-buffer operator (fp64).
 int attach_default_source(lora_plan *plan, size_t bytes, void **d_source) {
-    HostSource hs;
-    const int rc = upload_default_source(plan, bytes, hs);
-    *d_source = hs.d;  // the caller frees it after the plan's last launch
-    hs.d = nullptr;
-    if (rc != LORA_OK && *d_source) {
-        (void) hipFree(*d_source);
+    if (!g_default_source) return LORA_OK;
+    if (hipMalloc(d_source, bytes) != hipSuccess) {
+        (void) hipGetLastError();
         *d_source = nullptr;
+        return LORA_ENOMEM;
     }
-    return rc;
+    const hipError_t e = hipMemcpy(*d_source, g_default_source, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_last_error("source upload", e);
+        return LORA_EHIP;
+    }
+    return lora_plan_set_source(plan, *d_source);
+}
+
+bool DeviceGrid::ready(size_t want) const {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void) hipGetLastError();
+        return false;
+    }
+    return ptr && bytes == want && device == dev;
+}
+
+bool DeviceGrid::ensure(size_t want, bool zero) {
+    if (ready(want)) return true;
+    release();
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipMalloc(&ptr, want) != hipSuccess) {
+        (void) hipGetLastError();
+        ptr = nullptr;
+        return false;
+    }
+    // zeroed: the cells no kernel ever writes (pads beyond the halo ring do not exist; the ring is copied per run)
+    if (zero && hipMemset(ptr, 0, want) != hipSuccess) {
+        (void) hipGetLastError();
+        release();
+        return false;
+    }
+    bytes = want;
+    device = dev;
+    return true;
+}
+
+void DeviceGrid::release() {
+    if (ptr) (void) hipFree(ptr);
+    *this = DeviceGrid();
 }
 
 }  // namespace lora
@@ -274,31 +283,11 @@ int lora_plan_stepn_region(lora_plan *plan, int napps, const void *d_in, void *d
 
 static void drop_graph(lora_plan *plan);
 
-// the scratch grid this plan would use on the current device is there already
-static bool scratch_ready(const lora_plan *plan) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    return plan->scratch && plan->scratch_bytes == lora_plan_padded_bytes(plan) && plan->scratch_device == dev;
-}
-
 static bool ensure_scratch(lora_plan *plan) {
     const size_t bytes = lora_plan_padded_bytes(plan);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    if (scratch_ready(plan)) return true;
+    if (plan->scratch.ready(bytes)) return true;
     drop_graph(plan);  // a captured run holds the old grid's address
-    if (plan->scratch) (void) hipFree(plan->scratch);
-    plan->scratch = nullptr;
-    if (hipMalloc(&plan->scratch, bytes) != hipSuccess) {
-        (void) hipGetLastError();
-        plan->scratch = nullptr;
-        return false;
-    }
-    // cells the kernels never write (pads beyond the halo ring do not exist; the ring itself is copied per run)
-    if (hipMemset(plan->scratch, 0, bytes) != hipSuccess) (void) hipGetLastError();
-    plan->scratch_bytes = bytes;
-    plan->scratch_device = dev;
-    return true;
+    return plan->scratch.ensure(bytes, true);
 }
 
 // 1D runs with the automatic launch depth fuse more applications per launch the longer the run is: 8 is the plan's
@@ -385,7 +374,8 @@ static Schedule run_schedule(const Plan &p, int times, int K, bool scratch_ok) {
 static Schedule plan_schedule(lora_plan *plan, int times, bool allocate) {
     const int K = run_depth(plan->p, times);
     Schedule sc = run_schedule(plan->p, times, K, true);
-    if (sc.scratch && !(allocate ? ensure_scratch(plan) : scratch_ready(plan))) sc = run_schedule(plan->p, times, K, false);
+    if (sc.scratch && !(allocate ? ensure_scratch(plan) : plan->scratch.ready(lora_plan_padded_bytes(plan))))
+        sc = run_schedule(plan->p, times, K, false);
     return sc;
 }
 
@@ -514,11 +504,7 @@ static const int *torus_pads(int nd) {
 static void torus_drop(lora_plan *plan) {
     if (plan->torus) lora_plan_destroy(plan->torus);
     plan->torus = nullptr;
-    for (void *&b : plan->torus_buf) {
-        if (b) (void) hipFree(b);
-        b = nullptr;
-    }
-    plan->torus_bytes = 0;
+    for (lora::DeviceGrid &b : plan->torus_buf) b.release();
     plan->torus_tried = false;
 }
 
@@ -554,22 +540,13 @@ static lora_plan *torus_prepare(lora_plan *plan) {
     if (ok && p.steps_per_launch_req > 1) (void) lora_plan_set_option(tp, "steps_per_launch", p.steps_per_launch_req);
     ok = ok && tp->p.steps_per_launch >= 2 && tp->p.steps_per_launch <= kmax;
     const size_t bytes = ok ? lora_plan_padded_bytes(tp) : 0;
-    for (int i = 0; ok && i < 2; ++i)
-        if (hipMalloc(&plan->torus_buf[i], bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            plan->torus_buf[i] = nullptr;
-            ok = false;
-        }
+    ok = ok && plan->torus_buf[0].ensure(bytes, false) && plan->torus_buf[1].ensure(bytes, false);
     if (!ok) {
         lora_plan_destroy(tp);
-        for (void *&b : plan->torus_buf) {
-            if (b) (void) hipFree(b);
-            b = nullptr;
-        }
+        for (lora::DeviceGrid &b : plan->torus_buf) b.release();
         return nullptr;
     }
     plan->torus = tp;
-    plan->torus_bytes = bytes;
     return tp;
 }
 
@@ -585,21 +562,16 @@ static int run_torus(lora_plan *plan, void *d_buf0, void *d_buf1, int times, hip
     int ring[3] = {0, 0, 0};
     for (int d = 0; d < nd; ++d) ring[d] = pad[d] + plan->torus_ghost[d];
     void *buf[2] = {d_buf0, d_buf1};
-    void *E[2] = {plan->torus_buf[0], plan->torus_buf[1]};
-    auto hip = [&](hipError_t e, const char *what) -> int {
-        if (e == hipSuccess) return LORA_OK;
-        lora::set_last_error(what, e);
-        return LORA_EHIP;
-    };
+    void *E[2] = {plan->torus_buf[0].ptr, plan->torus_buf[1].ptr};
     // level 0: the interior into the extended grid's middle, its images into everything around it
-    if (int rc = hip(lora::launch_copy_interior(p.dtype, nd, p.dims, E[0], ring, buf[0], pad, s), "torus: copy in")) return rc;
-    if (int rc = hip(lora::launch_ring_wrap(p.dtype, nd, p.dims, ring, E[0], s), "torus: wrap")) return rc;
+    if (int rc = lora::hip_status(lora::launch_copy_interior(p.dtype, nd, p.dims, E[0], ring, buf[0], pad, s), "torus: copy in")) return rc;
+    if (int rc = lora::hip_status(lora::launch_ring_wrap(p.dtype, nd, p.dims, ring, E[0], s), "torus: wrap")) return rc;
     int cur = 0, left = times;
     while (left > 0) {
         int d = std::min(left, K);
         while (!lora::has_depth(tp->p, d)) --d;  // the deepest launch the extended plan's kernels have
         if (int rc = lora::launch_apps(tp->p, {d, 0, tp->p.dims[0]}, E[cur], E[1 - cur], s)) return rc;
-        if (int rc2 = hip(lora::launch_ring_wrap(p.dtype, nd, p.dims, ring, E[1 - cur], s), "torus: wrap")) return rc2;
+        if (int rc2 = lora::hip_status(lora::launch_ring_wrap(p.dtype, nd, p.dims, ring, E[1 - cur], s), "torus: wrap")) return rc2;
         if (marks) {
             if (d == K)
                 ++marks->fused_launches;
@@ -616,8 +588,8 @@ static int run_torus(lora_plan *plan, void *d_buf0, void *d_buf1, int times, hip
         (void) hipEventRecord(marks->ev[2], s);
     }
     // the result: the extended grid's middle back into the caller's buffer, and that buffer's halo = its periodic images
-    if (int rc = hip(lora::launch_copy_interior(p.dtype, nd, p.dims, buf[times % 2], pad, E[cur], ring, s), "torus: copy out")) return rc;
-    const int rc = hip(lora::launch_halo(p, buf[times % 2], nullptr, lora::HALO_WRAP, s), "periodic halo");
+    if (int rc = lora::hip_status(lora::launch_copy_interior(p.dtype, nd, p.dims, buf[times % 2], pad, E[cur], ring, s), "torus: copy out")) return rc;
+    const int rc = lora::hip_status(lora::launch_halo(p, buf[times % 2], nullptr, lora::HALO_WRAP, s), "periodic halo");
     if (marks) (void) hipEventRecord(marks->ev[3], s);
     return rc;
 }
@@ -694,7 +666,7 @@ static int run_launches(lora_plan *plan, void *d_buf0, void *d_buf1, int times, 
         full += d == K;
         done += d;
     }
-    void *scratch = sc.scratch ? plan->scratch : nullptr;
+    void *scratch = sc.scratch ? plan->scratch.ptr : nullptr;
     if (n > 0) {
         if (int rc = lora::check_buffers(d_buf0, d_buf1)) return rc;
         if (!dirichlet)
@@ -848,39 +820,7 @@ int lora_plan_run_profiled(lora_plan *plan, void *d_buf0, void *d_buf1, int time
     return LORA_OK;
 }
 
-// ---- group A: host-buffer operators ------------------------------------------------------------------
-
-static const char *run_label(int shape) {
-    switch (shape) {
-        case LORA_1D1R:
-            return "LoRAStencil(1D 1d1r): ";  // 1d/gpu_1r.cu:127
-        case LORA_1D2R:
-            return "LoRAStencil(1D 1d2r): ";  // 1d/gpu_2r.cu:129
-        case LORA_STAR2D1R:
-            return "LoRAStencil(2D star_2d1r): ";  // 2d/gpu.cu:549
-        case LORA_STAR2D3R:
-            return "LoRAStencil(2D star_2d3r): ";  // 2d/gpu.cu:474
-        case LORA_BOX2D1R:
-        case LORA_BOX2D3R:
-            return "LoRAStencil(2D box_2d3r): ";  // 2d/gpu.cu:415 (one operator serves both box shapes)
-        case LORA_STAR3D1R:
-            return "LoRAStencil(3D star_3d1r): ";  // 3d/gpu_star.cu:185
-        case LORA_BOX3D1R:
-            return "LoRAStencil(3D box_3d1r): ";  // 3d/gpu_box.cu:216
-        default:
-            return "LoRAStencil(?): ";
-    }
-}
-
-namespace {
-struct DeviceBuffers {
-    void *b[2] = {nullptr, nullptr};
-    ~DeviceBuffers() {
-        for (void *p : b)
-            if (p) (void) hipFree(p);
-    }
-};
-}  // namespace
+// ---- group A: host-buffer operators (their skeleton: lora::HostRun, hostrun.cpp) -----------------------------------
 
 int lora_run_host(int shape, const double *in, double *out, const double *params, int times, const int *dims,
                   int quiet, lora_run_info *info) {
@@ -898,49 +838,27 @@ int lora_run_host_dtype(int shape, int dtype, const void *in, void *out, const d
     if (!in || !out || !dims || times < 0) return LORA_EINVAL;
     if (dtype == LORA_BF16)
         if (int rc = lora::default_source_refused("a bf16 run")) return rc;
-    if (lora_device_count() <= 0) {
-        g_last_error = "no HIP device visible";
-        return LORA_ENODEVICE;
-    }
-    lora_plan *plan = nullptr;
-    int rc = lora_plan_create(&plan, shape, dtype, dims, params);
+    lora::HostRun dev;
+    int rc = dev.open(shape, dtype, dims, params);
     if (rc != LORA_OK) return rc;
-    struct PlanGuard {
-        lora_plan *p;
-        ~PlanGuard() { lora_plan_destroy(p); }
-    } guard{plan};
-
-    using clock = std::chrono::steady_clock;
-    const size_t count = lora_padded_count(shape, dims);
-    const size_t esize = (dtype == LORA_BF16) ? 2 : sizeof(double);
-    const size_t bytes = count * esize;
-    DeviceBuffers dev;
-    lora::HostSource src;  // (declared before the plan's launches, freed after them)
-    const auto t_total0 = clock::now();
-    LORA_HIP_TRY(hipMalloc(&dev.b[0], bytes));
-    LORA_HIP_TRY(hipMalloc(&dev.b[1], bytes));
+    lora_plan *plan = dev.plan;
+    const size_t bytes = dev.bytes;
+    LORA_HIP_TRY(dev.alloc(2));
     LORA_HIP_TRY(hipMemcpy(dev.b[0], in, bytes, hipMemcpyHostToDevice));  // whole padded input, halo included
-    if (int src_rc = lora::upload_default_source(plan, bytes, src)) return src_rc;  // the thread's default source, beside the grid
+    if (int src_rc = lora::attach_default_source(plan, bytes, &dev.src)) return src_rc;  // the thread's default source, beside the grid
     // warm-up (the reference has none): one sweep into buf1, which is then cleared again
     if (times > 0) {
         rc = lora_plan_step(plan, dev.b[0], dev.b[1], nullptr);
         if (rc != LORA_OK) return rc;
     }
     LORA_HIP_TRY(hipMemset(dev.b[1], 0, bytes));
-    // a stream of our own: launch-bound runs are replayed from a hipGraph, which the legacy default stream cannot capture
-    struct StreamGuard {
-        hipStream_t s = nullptr;
-        ~StreamGuard() {
-            if (s) (void) hipStreamDestroy(s);
-        }
-    } sg;
-    LORA_HIP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    LORA_HIP_TRY(dev.stream());
     LORA_HIP_TRY(hipDeviceSynchronize());
     if (times >= 16 && bytes <= (64u << 20)) {
         // build (capture + instantiate) the graph outside the timed region, like the reference's setup work
-        rc = lora_plan_run(plan, dev.b[0], dev.b[1], times, sg.s);
+        rc = lora_plan_run(plan, dev.b[0], dev.b[1], times, dev.s);
         if (rc != LORA_OK) return rc;
-        LORA_HIP_TRY(hipStreamSynchronize(sg.s));
+        LORA_HIP_TRY(hipStreamSynchronize(dev.s));
         LORA_HIP_TRY(hipMemcpy(dev.b[0], in, bytes, hipMemcpyHostToDevice));
         LORA_HIP_TRY(hipMemset(dev.b[1], 0, bytes));
     }
@@ -949,41 +867,16 @@ int lora_run_host_dtype(int shape, int dtype, const void *in, void *out, const d
     (void) lora_plan_prepare_run(plan, times);
     LORA_HIP_TRY(hipDeviceSynchronize());
 
-    const auto t0 = clock::now();
-    rc = lora_plan_run(plan, dev.b[0], dev.b[1], times, sg.s);
+    dev.tic();
+    rc = lora_plan_run(plan, dev.b[0], dev.b[1], times, dev.s);
     if (rc != LORA_OK) return rc;
-    LORA_HIP_TRY(hipStreamSynchronize(sg.s));
-    const auto t1 = clock::now();
+    LORA_HIP_TRY(hipStreamSynchronize(dev.s));
+    dev.toc();
 
     // 1D copies all but the last element (1d/gpu_1r.cu:134)
-    const size_t copy_bytes = (plan->p.ndim == 1) ? bytes - esize : bytes;
+    const size_t copy_bytes = (plan->p.ndim == 1) ? bytes - dev.esize : bytes;
     LORA_HIP_TRY(hipMemcpy(out, dev.b[times % 2], copy_bytes, hipMemcpyDeviceToHost));
-    const auto t_total1 = clock::now();
-
-    double points = 1.0;
-    for (int d = 0; d < plan->p.ndim; ++d) points *= dims[d];
-    const long long us = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
-    const double secs = us / 1e6;
-    const int F = lora_shape_gstencil_factor(shape);
-    lora_run_info ri;
-    ri.sweep_seconds = std::chrono::duration<double>(t1 - t0).count();
-    ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
-    ri.gstencils = points * times / ri.sweep_seconds / 1e9;
-    ri.gstencils_refconv = ri.gstencils * F;
-    ri.hbm_gbs = points * times * (plan->p.source ? 3.0 : 2.0) * esize / ri.sweep_seconds / 1e9;  // a source is one more read
-    ri.variant = plan->p.variant;
-    ri.steps_per_launch = plan->p.steps_per_launch;
-    lora::g_last_info = ri;
-    if (info) *info = ri;
-    if (!quiet) {
-        // byte-compatible with the reference's three lines (2d/gpu.cu:549-553)
-        std::printf("%s\n", run_label(shape));
-        std::printf("Time = %lld[ms]\n",
-                    (long long) std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count());
-        std::printf("GStencil/s = %f\n", points * times * F / secs / 1e9);
-        std::fflush(stdout);
-    }
-    return LORA_OK;
+    return dev.finish(times, plan->p.source ? 3.0 : 2.0, plan->p.steps_per_launch, quiet, info);  // a source is one more read
 }
 
 int lora_last_run_info(lora_run_info *info) {
@@ -1024,15 +917,9 @@ int lora_gpu_star_3d1r(const double *in, double *out, const double *params, int 
 }  // extern "C"
 
 namespace lora {
-const char *run_label(int shape) { return ::run_label(shape); }
-
 void release_run_state(lora_plan *plan) {
     drop_graph(plan);
-    if (plan->scratch) (void) hipFree(plan->scratch);
-    plan->scratch = nullptr;
     torus_drop(plan);
-    release_leapfrog_state(plan);
-    if (plan->reduce_buf) (void) hipFree(plan->reduce_buf);
-    plan->reduce_buf = nullptr;
+    for (DeviceGrid *g : {&plan->scratch, &plan->records, &plan->leap[0], &plan->leap[1], &plan->cheb_probe}) g->release();
 }
 }  // namespace lora

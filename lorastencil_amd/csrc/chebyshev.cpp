@@ -1,12 +1,11 @@
 // chebyshev.cpp -- the Chebyshev semi-iteration on top of the scaled leapfrog step with a source (leapfrog.cpp:
 // lora_plan_run_leapfrog_src):   u(k+1) = w(k+1) (S(u(k)) + f) + (1 - w(k+1)) u(k-1)
 // solves u = S(u) + f in O(N) steps on an N-wide grid where Jacobi (lora_plan_run_until with a source) needs O(N^2).
-// The coefficient schedule (host only), the run-until driver with a true-residual probe, and the host-buffer operator.
+// The coefficient schedule (host only), the run-until driver with a true-residual probe (its grid: lora_plan::cheb_probe), and
+// the host-buffer operator (its skeleton: hostrun.cpp).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <vector>
 
 #include "engine.h"
@@ -29,41 +28,6 @@ struct Omega {
 };
 
 bool bad_rho(double rho) { return !(rho >= 0.0 && rho < 1.0); }  // (a NaN fails both)
-
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
-int unsupported(const char *text) {
-    set_last_error_text(text);
-    return LORA_EUNSUPPORTED;
-}
-
-bool ensure_probe(lora_plan *plan) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void) hipGetLastError();
-        return false;
-    }
-    const size_t bytes = lora_plan_padded_bytes(plan);
-    if (plan->cheb_probe && plan->cheb_bytes == bytes && plan->cheb_device == dev) return true;
-    if (plan->cheb_probe) (void) hipFree(plan->cheb_probe);
-    plan->cheb_probe = nullptr;
-    // (only interior cells of it are ever read, each after the probe's sweep wrote it)
-    if (hipMalloc(&plan->cheb_probe, bytes) != hipSuccess || hipMemset(plan->cheb_probe, 0, bytes) != hipSuccess) {
-        (void) hipGetLastError();
-        if (plan->cheb_probe) (void) hipFree(plan->cheb_probe);
-        plan->cheb_probe = nullptr;
-        return false;
-    }
-    plan->cheb_bytes = bytes;
-    plan->cheb_device = dev;
-    return true;
-}
-
-bool bad_until(const lora_until *u) {
-    if (u->check_every < 2 || u->check_every % 2 || u->max_times < 0) return true;
-    if (u->norm != LORA_NORM_MAX && u->norm != LORA_NORM_RMS) return true;
-    return !(u->tol >= 0.0) || !(u->rtol >= 0.0);
-}
 
 }  // namespace
 }  // namespace lora
@@ -101,8 +65,9 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
     // probe's; sum_sq -- the RMS norm's -- is summed in another order there, so that norm keeps the two passes and their grid
     const bool fused = u->norm == LORA_NORM_MAX && lora::has_fused_residual(p);
     if (!fused) {
-        if (!lora::ensure_probe(plan)) return LORA_ENOMEM;
-        if (plan->cheb_probe == d_prev || plan->cheb_probe == d_cur || plan->cheb_probe == d_f) return LORA_EINVAL;
+        // (only interior cells of it are ever read, each after the probe's sweep wrote it)
+        if (!plan->cheb_probe.ensure(lora_plan_padded_bytes(plan), true)) return LORA_ENOMEM;
+        if (plan->cheb_probe.ptr == d_prev || plan->cheb_probe.ptr == d_cur || plan->cheb_probe.ptr == d_f) return LORA_EINVAL;
     }
     (void) lora_plan_prepare_leapfrog(plan, u->check_every);
 
@@ -125,19 +90,10 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
         if (fused) {
             if (int rc = lora::residual_whole(plan, d_cur, d_f, &r->last, s)) return rc;
         } else {
-            if (int rc = lora::launch_apps(probe, {1, 0, p.dims[0]}, d_cur, plan->cheb_probe, s)) return rc;
-            if (int rc = lora::diff_whole(plan, plan->cheb_probe, d_cur, &r->last, s)) return rc;
+            if (int rc = lora::launch_apps(probe, {1, 0, p.dims[0]}, d_cur, plan->cheb_probe.ptr, s)) return rc;
+            if (int rc = lora::diff_whole(plan, plan->cheb_probe.ptr, d_cur, &r->last, s)) return rc;
         }
-        r->checks += 1;
-        r->residual = u->norm == LORA_NORM_RMS ? std::sqrt(r->last.sum_sq / (double) r->last.count) : r->last.max_abs;
-        if (r->last.nonfinite > 0) {
-            r->diverged = 1;
-            break;
-        }
-        if (r->residual <= u->tol + u->rtol * r->last.a_abs_max) {
-            r->converged = 1;
-            break;
-        }
+        if (lora::until_decide(u, r)) break;
     }
     return LORA_OK;
 }
@@ -147,55 +103,29 @@ int lora_run_host_chebyshev(int shape, const double *in, const double *source, d
     if (!in || !out || !dims || lora::bad_rho(rho)) return LORA_EINVAL;
     if (u ? (!r || lora::bad_until(u)) : times < 0) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("a Chebyshev run (its source is an argument)")) return rc;
-    if (lora_device_count() <= 0) {
-        lora::set_last_error_text("no HIP device visible");
-        return LORA_ENODEVICE;
-    }
-    lora_plan *plan = nullptr;
-    int rc = lora_plan_create(&plan, shape, LORA_F64, dims, params);
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
     if (rc != LORA_OK) return rc;
-    struct Guard {
-        lora_plan *p;
-        void *b[3] = {nullptr, nullptr, nullptr};
-        hipStream_t s = nullptr;
-        ~Guard() {
-            if (s) (void) hipStreamDestroy(s);
-            for (void *x : b)
-                if (x) (void) hipFree(x);
-            lora_plan_destroy(p);
-        }
-    } g{plan};
-    auto hip = [&](hipError_t e, const char *what) -> int {
-        if (e == hipSuccess) return LORA_OK;
-        lora::set_last_error(what, e);
-        return LORA_EHIP;
-    };
-    using clock = std::chrono::steady_clock;
-    const size_t bytes = lora_plan_padded_bytes(plan);
-    const auto t_total0 = clock::now();
-    for (int i = 0; i < (source ? 3 : 2); ++i)
-        if (hipMalloc(&g.b[i], bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            g.b[i] = nullptr;
-            return LORA_ENOMEM;
-        }
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(source ? 3 : 2) != hipSuccess) return LORA_ENOMEM;
     void *d_prev = g.b[0], *d_cur = g.b[1], *d_f = g.b[2];
-    if ((rc = hip(hipMemcpy(d_cur, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if ((rc = lora::hip_status(hipMemcpy(d_cur, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     if (source)
-        if ((rc = hip(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the scratch grids, and one warm-up step (it writes d_prev, which is uploaded after it)
     const int cap = u ? u->max_times : times;
     if ((rc = lora_plan_prepare_leapfrog(plan, u ? u->check_every : times))) return rc;
-    if ((rc = hip(hipMemset(d_prev, 0, bytes), "warm-up"))) return rc;
+    if ((rc = lora::hip_status(hipMemset(d_prev, 0, bytes), "warm-up"))) return rc;
     if (cap > 0)
         if ((rc = lora_plan_step_leapfrog_src(plan, d_cur, d_prev, d_f, 1.0, 0.0, nullptr))) return rc;
-    if ((rc = hip(hipDeviceSynchronize(), "warm-up"))) return rc;
-    if ((rc = hip(hipMemcpy(d_prev, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;  // both levels start as `in`
-    if ((rc = hip(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking), "stream"))) return rc;
-    if ((rc = hip(hipDeviceSynchronize(), "upload"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "warm-up"))) return rc;
+    if ((rc = lora::hip_status(hipMemcpy(d_prev, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;  // both levels start as `in`
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
 
     int done = times;
-    const auto t0 = clock::now();
+    g.tic();
     if (u) {
         if ((rc = lora_plan_run_chebyshev_until(plan, d_prev, d_cur, d_f, rho, u, r, g.s))) return rc;
         done = r->times_done;
@@ -205,32 +135,10 @@ int lora_run_host_chebyshev(int shape, const double *in, const double *source, d
         if ((rc = lora_plan_run_leapfrog_src(plan, d_prev, d_cur, d_f, a.data(), c.data(), (int) a.size(), times, g.s))) return rc;
         if (r) *r = {times, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}};
     }
-    if ((rc = hip(hipStreamSynchronize(g.s), "run"))) return rc;
-    const auto t1 = clock::now();
-    if ((rc = hip(hipMemcpy(out, done % 2 ? d_prev : d_cur, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
-    const auto t_total1 = clock::now();
-
-    double points = 1.0;
-    for (int d = 0; d < plan->p.ndim; ++d) points *= dims[d];
-    const int F = lora_shape_gstencil_factor(shape);
-    lora_run_info ri;
-    ri.sweep_seconds = std::chrono::duration<double>(t1 - t0).count();  // the steps and, with `u`, their probes
-    ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
-    ri.gstencils = points * done / ri.sweep_seconds / 1e9;
-    ri.gstencils_refconv = ri.gstencils * F;
-    ri.hbm_gbs = points * done * (source ? 4.0 : 3.0) * sizeof(double) / ri.sweep_seconds / 1e9;  // cur, prev (and f) read, prev written
-    ri.variant = plan->p.variant;
-    ri.steps_per_launch = lora::leapfrog_depth(plan->p);
-    lora::set_last_run_info(ri);
-    if (info) *info = ri;
-    if (!quiet) {
-        const double secs = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() / 1e6;
-        std::printf("%s\n", lora::run_label(shape));
-        std::printf("Time = %lld[ms]\n", (long long) std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count());
-        std::printf("GStencil/s = %f\n", points * done * F / secs / 1e9);
-        std::fflush(stdout);
-    }
-    return LORA_OK;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();  // the steps and, with `u`, their probes
+    if ((rc = lora::hip_status(hipMemcpy(out, done % 2 ? d_prev : d_cur, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    return g.finish(done, source ? 4.0 : 3.0, lora::leapfrog_depth(plan->p), quiet, info);  // cur, prev (and f) read, prev written
 }
 
 }  // extern "C"

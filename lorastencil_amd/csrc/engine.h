@@ -314,15 +314,69 @@ int region_granularity(const Plan &p);
 void set_last_error(const char *what, hipError_t e);
 void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
-void release_leapfrog_state(lora_plan *plan);      // leapfrog.cpp: the two scratch grids of lora_plan_run_leapfrog[_src], the probe grid of lora_plan_run_chebyshev_until
-void release_run_state(lora_plan *plan);            // capi.cpp: what runs cached in the plan (graph, scratch grid, torus, reduction records)
+void release_run_state(lora_plan *plan);            // capi.cpp: the one place that releases what a plan owns on a device (graph, torus, every DeviceGrid)
 int admit_reduction(const void *a, const void *b, hipStream_t s);  // reduce.cpp: what every reduction entry checks before it touches the device
 int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_residual_src over the whole interior, unchecked (blocks)
 int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_diff over the whole interior, unchecked (blocks)
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
-int attach_default_source(lora_plan *plan, size_t bytes, void **d_source);  // capi.cpp: upload the thread's default source (if any) and set it on the plan; *d_source is the caller's to hipFree
-const char *run_label(int shape);                  // the operator's first stdout line (e.g. 2d/gpu.cu:549)
+int attach_default_source(lora_plan *plan, size_t bytes, void **d_source);  // capi.cpp: upload the thread's default source (if any) and set it on the plan; *d_source is the caller's to hipFree, whatever the status
+const char *run_label(int shape);                  // hostrun.cpp: the operator's first stdout line (e.g. 2d/gpu.cu:549)
+
+// ---- what the entries of capi.cpp, leapfrog.cpp, chebyshev.cpp and reduce.cpp refuse and report alike ----------------------
+inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+inline int unsupported(const char *text) {
+    set_last_error_text(text);
+    return LORA_EUNSUPPORTED;
+}
+inline int hip_status(hipError_t e, const char *what) {  // LORA_OK, or LORA_EHIP and the error as the thread's text
+    if (e == hipSuccess) return LORA_OK;
+    set_last_error(what, e);
+    return LORA_EHIP;
+}
+inline int no_device() {
+    set_last_error_text("no HIP device visible");
+    return LORA_ENODEVICE;
+}
+// reduce.cpp: a lora_until's schedule (check_every, max_times) / any of its fields is out of range
+bool bad_until_schedule(const lora_until *u);
+bool bad_until(const lora_until *u);
+// reduce.cpp: one check of an until-loop, its probe in r->last: counts it, takes the norm, marks diverged or else converged;
+// whether the loop stops
+bool until_decide(const lora_until *u, lora_until_result *r);
+
+// ---- a device grid a plan owns (capi.cpp): allocated on first need, kept while size and device match, freed by
+// release_run_state ----------------------------------------------------------------------------------------------------------
+struct DeviceGrid {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    int device = -1;
+    bool ready(size_t want) const;        // a grid of `want` bytes on the current device is there (no allocation)
+    bool ensure(size_t want, bool zero);  // ... or is now, in place of what was held; false: no grid (the holder is empty)
+    void release();
+};
+
+// ---- what the four host-buffer operators share (hostrun.cpp): the device check, the plan, N padded grids, a stream of the
+// operator's own, the two clocks, the run info and the reference's three stdout lines.  The operator keeps its checks, uploads,
+// warm-up, prepare call, the timed call between tic() and toc(), and its download.
+struct HostRun {
+    lora_plan *plan = nullptr;
+    void *b[3] = {nullptr, nullptr, nullptr};  // alloc(): padded grids
+    void *src = nullptr;                       // the thread's default source on the device (attach_default_source)
+    hipStream_t s = nullptr;
+    size_t esize = 0, bytes = 0;               // of a cell, of a padded grid
+    ~HostRun();
+    int open(int shape, int dtype, const int *dims, const double *params);  // LORA_ENODEVICE, or what plan creation says
+    hipError_t alloc(int n);  // starts the total clock, then n grids; a failure leaves no sticky error
+    hipError_t stream();      // non-blocking: launch-bound runs are replayed from a hipGraph, which the legacy default stream cannot capture
+    void tic();
+    void toc();
+    // after the download: `steps` steps that each moved `grids_moved` grids; LORA_OK
+    int finish(int steps, double grids_moved, int steps_per_launch, int quiet, lora_run_info *info);
+    int shape = 0;
+    double points = 1.0;              // interior points
+    long long ticks[3] = {0, 0, 0};  // steady_clock: alloc(), tic(), toc()
+};
 
 }  // namespace lora
 
@@ -334,29 +388,17 @@ struct lora_plan {
     int graph_times = -1;
     unsigned graph_epoch = 0;  // value of p.epoch the graph was captured at
     bool capturing = false;    // lora_plan_run is capturing its launches: no allocations meanwhile
-    // one more padded grid, allocated on first need (lora_plan_run with an odd number of fused launches)
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    int scratch_device = -1;
-    // the periodic option's fused runs (run_torus): a plan of the grid extended by a ghost zone on every side, its two
-    // buffers, the ghost widths; rebuilt when the plan's taps / options change
+    // the periodic option's fused runs (run_torus): a plan of the grid extended by a ghost zone on every side and the ghost
+    // widths; rebuilt, with its two buffers below, when the plan's taps / options or the device change
     lora_plan *torus = nullptr;
-    void *torus_buf[2] = {nullptr, nullptr};
-    size_t torus_bytes = 0;
     int torus_device = -1;
     int torus_ghost[3] = {0, 0, 0};
     unsigned torus_epoch = 0;
     bool torus_tried = false;  // at torus_epoch: the answer was already "no" (grid too small, no fused kernel, no memory)
-    // the reductions' records (reduce.cpp): one per workgroup and the folded one, allocated on first need
-    void *reduce_buf = nullptr;
-    int reduce_device = -1;
-    // lora_plan_run_leapfrog's two scratch grids (leapfrog.cpp), allocated on first need
-    void *leap_scratch[2] = {nullptr, nullptr};
-    size_t leap_bytes = 0;
-    int leap_device = -1;
-    // lora_plan_run_chebyshev_until's probe grid (chebyshev.cpp): S(u) + f of the newest level, allocated on first need of the
-    // two-pass probe (the RMS norm, plans without the fused residual kernel)
-    void *cheb_probe = nullptr;
-    size_t cheb_bytes = 0;
-    int cheb_device = -1;
+    // Grids allocated on first need, each keyed on its own size and device and used by its driver alone:
+    lora::DeviceGrid scratch;       // lora_plan_run: one more padded grid for an odd number of fused launches (a cached graph holds its address)
+    lora::DeviceGrid torus_buf[2];  // run_torus: the extended grid's two buffers (keyed by the torus fields above)
+    lora::DeviceGrid records;       // reduce.cpp: the reductions' records, one per workgroup and the folded one (not zeroed)
+    lora::DeviceGrid leap[2];       // lora_plan_run_leapfrog[_src]: the two scratch grids, both or neither
+    lora::DeviceGrid cheb_probe;    // lora_plan_run_chebyshev_until: S(u) + f of the newest level, for the two-pass probe (the RMS norm, plans without the fused residual kernel)
 };

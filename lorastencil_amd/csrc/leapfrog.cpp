@@ -1,52 +1,20 @@
 // leapfrog.cpp -- the leapfrog entries of the C ABI (include/lorastencil.h): u(t+1) = S(u(t)) + c u(t-1), the new level stored
-// over the oldest one.  One step in place (kernels_step.hip), two steps per launch in 2D (kernels_2d_step2.hip) and, behind option leap3, in 3D
-// (kernels_3d_step2.hip), the
-// run driver and the host-buffer operator.  `c` and the buffers are call arguments: nothing here changes what a plan resolves
-// to, and no run is cached in a graph.
+// over the oldest one, and their forms with a source and a scale, a (S(u) + f) + c u-.  One step in place
+// (kernels_step.hip), two steps per launch in 2D (kernels_2d_step2.hip) and, behind option leap3, in 3D (kernels_3d_step2.hip),
+// the one run driver both rules go through (run_steps) and the host-buffer operator (its skeleton: hostrun.cpp).  The
+// coefficients and the buffers are call arguments: nothing here changes what a plan resolves to, and no run is cached in a graph.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 
 #include "engine.h"
 
 namespace lora {
-
 namespace {
-
-// the two scratch grids alone (the probe grid of a Chebyshev run in progress stays)
-void release_scratch(lora_plan *plan) {
-    for (void *&b : plan->leap_scratch) {
-        if (b) (void) hipFree(b);
-        b = nullptr;
-    }
-    plan->leap_bytes = 0;
-    plan->leap_device = -1;
-}
-
-}  // namespace
-
-void release_leapfrog_state(lora_plan *plan) {
-    release_scratch(plan);
-    if (plan->cheb_probe) (void) hipFree(plan->cheb_probe);
-    plan->cheb_probe = nullptr;
-    plan->cheb_bytes = 0;
-    plan->cheb_device = -1;
-}
-
-namespace {
-
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 bool bad_range(const Plan &p, int begin, int end) {
     return begin < 0 || end > p.dims[0] || begin > end || begin % region_granularity(p) != 0;
-}
-
-int unsupported(const char *text) {
-    set_last_error_text(text);
-    return LORA_EUNSUPPORTED;
 }
 
 // LORA_EUNSUPPORTED for the plans that have no leapfrog kernel (`two`: no two-step kernel)
@@ -61,11 +29,7 @@ int plan_refused(const Plan &p, bool two) {
 // a launch error as a status: loud about a missing device, as the source path is
 int failed(const char *what, hipError_t e) {
     set_last_error(what, e);
-    if (lora_device_count() <= 0) {
-        set_last_error_text("no HIP device visible");
-        return LORA_ENODEVICE;
-    }
-    return LORA_EHIP;
+    return lora_device_count() <= 0 ? no_device() : LORA_EHIP;
 }
 
 int step1(const Plan &p, const void *d_cur, void *d_prev, double c, int begin, int end, hipStream_t s) {
@@ -101,41 +65,65 @@ bool any_equal(const void *const *b, int n) {
     return false;
 }
 
-bool scratch_ready(const lora_plan *plan) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void) hipGetLastError();
-        return false;
-    }
-    return plan->leap_scratch[0] && plan->leap_scratch[1] && plan->leap_bytes == lora_plan_padded_bytes(plan) && plan->leap_device == dev;
-}
-
+// the two scratch grids, both or neither
 bool ensure_scratch(lora_plan *plan) {
-    if (scratch_ready(plan)) return true;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void) hipGetLastError();
-        return false;
-    }
-    release_scratch(plan);
     const size_t bytes = lora_plan_padded_bytes(plan);
-    for (void *&b : plan->leap_scratch) {
-        // (pads beyond the halo ring do not exist; the ring is copied per run, the interior written before it is read)
-        if (hipMalloc(&b, bytes) != hipSuccess || hipMemset(b, 0, bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            release_scratch(plan);
-            return false;
-        }
-    }
-    plan->leap_bytes = bytes;
-    plan->leap_device = dev;
-    return true;
+    // (the ring of each is copied per run, its interior written before it is read)
+    if (plan->leap[0].ensure(bytes, true) && plan->leap[1].ensure(bytes, true)) return true;
+    for (DeviceGrid &g : plan->leap) g.release();
+    return false;
 }
 
 // Whether a run of `times` steps takes two-step launches at all: plans of depth 2, a boundary that never writes a halo, the
 // scratch grids allowed, at least one pair of launches.
 bool run_fuses(const Plan &p, int times) {
     return leapfrog_depth(p) == 2 && p.boundary != LORA_BC_PERIODIC && p.use_scratch != 0 && times >= 4;
+}
+
+// The run driver of both rules: `times` steps from (d_prev, d_cur), step i as step1(cur, prev, i) in place or, two at a time,
+// step2(prev, cur, out1, out2, i) for steps i and i + 1.  d_f: the source the steps read (nullptr = none).
+template <class Step1, class Step2>
+int run_steps(lora_plan *plan, void *d_prev, void *d_cur, const void *d_f, int times, void *stream, Step1 step1, Step2 step2) {
+    const Plan &p = plan->p;
+    void *lv[2] = {d_prev, d_cur};  // lv[1] holds the newest level, lv[0] the one before it
+
+    if (p.boundary == LORA_BC_PERIODIC) {
+        // the newest level always carries its periodic images; the older one's halo is never read
+        auto wrap = [&](void *buf) -> int {
+            const int rc = lora_plan_halo(plan, buf, nullptr, LORA_HALO_WRAP, stream);
+            return rc == LORA_EHIP && lora_device_count() <= 0 ? no_device() : rc;
+        };
+        if (int rc = wrap(lv[1])) return rc;
+        for (int i = 0; i < times; ++i) {
+            if (int rc = step1(lv[1], lv[0], i)) return rc;
+            if (int rc = wrap(lv[0])) return rc;
+            std::swap(lv[0], lv[1]);
+        }
+        return LORA_OK;
+    }
+
+    // Pairs of two-step launches through the plan's scratch grids: (prev, cur) -> (s0, s1) -> (prev, cur), steps 4k .. 4k + 3.
+    // s0 takes levels that live in d_prev under the in-place driver and s1 levels that live in d_cur, so they carry those
+    // buffers' halos; four steps later every level is where single steps leave it.
+    int done = 0;
+    if (run_fuses(p, times) && ensure_scratch(plan)) {
+        void *s0 = plan->leap[0].ptr, *s1 = plan->leap[1].ptr;
+        const void *all[5] = {d_prev, d_cur, d_f, s0, s1};
+        if (!any_equal(all, 5)) {
+            if (int rc = lora_plan_halo(plan, s0, d_prev, LORA_HALO_COPY, stream)) return rc;
+            if (int rc = lora_plan_halo(plan, s1, d_cur, LORA_HALO_COPY, stream)) return rc;
+            for (int i = 0; i + 4 <= times; i += 4) {
+                if (int rc = step2(d_prev, d_cur, s0, s1, i)) return rc;
+                if (int rc = step2(s0, s1, d_prev, d_cur, i + 2)) return rc;
+            }
+            done = times / 4 * 4;
+        }
+    }
+    for (int i = done; i < times; ++i) {
+        if (int rc = step1(lv[1], lv[0], i)) return rc;
+        std::swap(lv[0], lv[1]);
+    }
+    return LORA_OK;
 }
 
 }  // namespace
@@ -197,48 +185,10 @@ int lora_plan_run_leapfrog(lora_plan *plan, void *d_prev, void *d_cur, double c,
     if (times == 0) return LORA_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int m = p.dims[0];
-    void *lv[2] = {d_prev, d_cur};  // lv[1] holds the newest level, lv[0] the one before it
-
-    if (p.boundary == LORA_BC_PERIODIC) {
-        // the newest level always carries its periodic images; the older one's halo is never read
-        auto wrap = [&](void *buf) -> int {
-            const int rc = lora_plan_halo(plan, buf, nullptr, LORA_HALO_WRAP, stream);
-            if (rc == LORA_EHIP && lora_device_count() <= 0) {
-                lora::set_last_error_text("no HIP device visible");
-                return LORA_ENODEVICE;
-            }
-            return rc;
-        };
-        if (int rc = wrap(lv[1])) return rc;
-        for (int i = 0; i < times; ++i) {
-            if (int rc = lora::step1(p, lv[1], lv[0], c, 0, m, s)) return rc;
-            if (int rc = wrap(lv[0])) return rc;
-            std::swap(lv[0], lv[1]);
-        }
-        return LORA_OK;
-    }
-
-    // Pairs of two-step launches through the plan's scratch grids: (prev, cur) -> (s0, s1) -> (prev, cur).  s0 takes levels
-    // that live in d_prev under the in-place driver and s1 levels that live in d_cur, so they carry those buffers' halos; four
-    // steps later every level is where single steps leave it.
-    int done = 0;
-    if (lora::run_fuses(p, times) && lora::ensure_scratch(plan)) {
-        void *s0 = plan->leap_scratch[0], *s1 = plan->leap_scratch[1];
-        if (s0 != d_prev && s0 != d_cur && s1 != d_prev && s1 != d_cur) {
-            if (int rc = lora_plan_halo(plan, s0, d_prev, LORA_HALO_COPY, stream)) return rc;
-            if (int rc = lora_plan_halo(plan, s1, d_cur, LORA_HALO_COPY, stream)) return rc;
-            for (int k = 0; k < times / 4; ++k) {
-                if (int rc = lora::step2(p, d_prev, d_cur, s0, s1, c, 0, m, s)) return rc;
-                if (int rc = lora::step2(p, s0, s1, d_prev, d_cur, c, 0, m, s)) return rc;
-            }
-            done = times / 4 * 4;
-        }
-    }
-    for (int i = done; i < times; ++i) {
-        if (int rc = lora::step1(p, lv[1], lv[0], c, 0, m, s)) return rc;
-        std::swap(lv[0], lv[1]);
-    }
-    return LORA_OK;
+    return lora::run_steps(
+        plan, d_prev, d_cur, nullptr, times, stream,
+        [&](const void *cur, void *prev, int) { return lora::step1(p, cur, prev, c, 0, m, s); },
+        [&](const void *prev, const void *cur, void *o1, void *o2, int) { return lora::step2(p, prev, cur, o1, o2, c, 0, m, s); });
 }
 
 // ---- a (S(u) + f) + c u-: the same entries with a source and a scale as call arguments ------------------------
@@ -294,126 +244,42 @@ int lora_plan_run_leapfrog_src(lora_plan *plan, void *d_prev, void *d_cur, const
     const int m = p.dims[0];
     auto A = [&](int i) { return a[std::min(i, ncoef - 1)]; };
     auto C = [&](int i) { return c[std::min(i, ncoef - 1)]; };
-    void *lv[2] = {d_prev, d_cur};  // lv[1] holds the newest level, lv[0] the one before it
-
-    if (p.boundary == LORA_BC_PERIODIC) {
-        // as lora_plan_run_leapfrog: the newest level always carries its periodic images; the older one's halo is never read
-        auto wrap = [&](void *buf) -> int {
-            const int rc = lora_plan_halo(plan, buf, nullptr, LORA_HALO_WRAP, stream);
-            if (rc == LORA_EHIP && lora_device_count() <= 0) {
-                lora::set_last_error_text("no HIP device visible");
-                return LORA_ENODEVICE;
-            }
-            return rc;
-        };
-        if (int rc = wrap(lv[1])) return rc;
-        for (int i = 0; i < times; ++i) {
-            if (int rc = lora::step1_src(p, lv[1], lv[0], d_f, A(i), C(i), 0, m, s)) return rc;
-            if (int rc = wrap(lv[0])) return rc;
-            std::swap(lv[0], lv[1]);
-        }
-        return LORA_OK;
-    }
-
-    // lora_plan_run_leapfrog's schedule and scratch grids: (prev, cur) -> (s0, s1) -> (prev, cur), steps 4k .. 4k + 3
-    int done = 0;
-    if (lora::run_fuses(p, times) && lora::ensure_scratch(plan)) {
-        void *s0 = plan->leap_scratch[0], *s1 = plan->leap_scratch[1];
-        const void *all[5] = {d_prev, d_cur, d_f, s0, s1};
-        if (!lora::any_equal(all, 5)) {
-            if (int rc = lora_plan_halo(plan, s0, d_prev, LORA_HALO_COPY, stream)) return rc;
-            if (int rc = lora_plan_halo(plan, s1, d_cur, LORA_HALO_COPY, stream)) return rc;
-            for (int k = 0; k < times / 4; ++k) {
-                const int i = 4 * k;
-                if (int rc = lora::step2_src(p, d_prev, d_cur, d_f, s0, s1, A(i), C(i), A(i + 1), C(i + 1), 0, m, s)) return rc;
-                if (int rc = lora::step2_src(p, s0, s1, d_f, d_prev, d_cur, A(i + 2), C(i + 2), A(i + 3), C(i + 3), 0, m, s)) return rc;
-            }
-            done = times / 4 * 4;
-        }
-    }
-    for (int i = done; i < times; ++i) {
-        if (int rc = lora::step1_src(p, lv[1], lv[0], d_f, A(i), C(i), 0, m, s)) return rc;
-        std::swap(lv[0], lv[1]);
-    }
-    return LORA_OK;
+    return lora::run_steps(
+        plan, d_prev, d_cur, d_f, times, stream,
+        [&](const void *cur, void *prev, int i) { return lora::step1_src(p, cur, prev, d_f, A(i), C(i), 0, m, s); },
+        [&](const void *prev, const void *cur, void *o1, void *o2, int i) {
+            return lora::step2_src(p, prev, cur, d_f, o1, o2, A(i), C(i), A(i + 1), C(i + 1), 0, m, s);
+        });
 }
 
 int lora_run_host_leapfrog(int shape, const double *in_cur, const double *in_prev, double *out, const double *params, double c,
                            int times, const int *dims, int quiet, lora_run_info *info) {
     if (!in_cur || !in_prev || !out || !dims || times < 0 || !std::isfinite(c)) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("a leapfrog run")) return rc;
-    if (lora_device_count() <= 0) {
-        lora::set_last_error_text("no HIP device visible");
-        return LORA_ENODEVICE;
-    }
-    lora_plan *plan = nullptr;
-    int rc = lora_plan_create(&plan, shape, LORA_F64, dims, params);
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
     if (rc != LORA_OK) return rc;
-    struct Guard {
-        lora_plan *p;
-        void *b[2] = {nullptr, nullptr};
-        hipStream_t s = nullptr;
-        ~Guard() {
-            if (s) (void) hipStreamDestroy(s);
-            for (void *x : b)
-                if (x) (void) hipFree(x);
-            lora_plan_destroy(p);
-        }
-    } g{plan};
-    auto hip = [&](hipError_t e, const char *what) -> int {
-        if (e == hipSuccess) return LORA_OK;
-        lora::set_last_error(what, e);
-        return LORA_EHIP;
-    };
-    using clock = std::chrono::steady_clock;
-    const size_t bytes = lora_plan_padded_bytes(plan);
-    const auto t_total0 = clock::now();
-    for (void *&x : g.b)
-        if (hipMalloc(&x, bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            x = nullptr;
-            return LORA_ENOMEM;
-        }
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(2) != hipSuccess) return LORA_ENOMEM;
     void *d_prev = g.b[0], *d_cur = g.b[1];
-    if ((rc = hip(hipMemcpy(d_cur, in_cur, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if ((rc = lora::hip_status(hipMemcpy(d_cur, in_cur, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the scratch grids, and one warm-up step (it writes d_prev, which is uploaded after it)
     if ((rc = lora_plan_prepare_leapfrog(plan, times))) return rc;
-    if ((rc = hip(hipMemset(d_prev, 0, bytes), "warm-up"))) return rc;
+    if ((rc = lora::hip_status(hipMemset(d_prev, 0, bytes), "warm-up"))) return rc;
     if (times > 0)
         if ((rc = lora_plan_step_leapfrog(plan, d_cur, d_prev, c, nullptr))) return rc;
-    if ((rc = hip(hipDeviceSynchronize(), "warm-up"))) return rc;
-    if ((rc = hip(hipMemcpy(d_prev, in_prev, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
-    if ((rc = hip(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking), "stream"))) return rc;
-    if ((rc = hip(hipDeviceSynchronize(), "upload"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "warm-up"))) return rc;
+    if ((rc = lora::hip_status(hipMemcpy(d_prev, in_prev, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
 
-    const auto t0 = clock::now();
+    g.tic();
     if ((rc = lora_plan_run_leapfrog(plan, d_prev, d_cur, c, times, g.s))) return rc;
-    if ((rc = hip(hipStreamSynchronize(g.s), "run"))) return rc;
-    const auto t1 = clock::now();
-    if ((rc = hip(hipMemcpy(out, times % 2 ? d_prev : d_cur, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
-    const auto t_total1 = clock::now();
-
-    double points = 1.0;
-    for (int d = 0; d < plan->p.ndim; ++d) points *= dims[d];
-    const int F = lora_shape_gstencil_factor(shape);
-    lora_run_info ri;
-    ri.sweep_seconds = std::chrono::duration<double>(t1 - t0).count();
-    ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
-    ri.gstencils = points * times / ri.sweep_seconds / 1e9;
-    ri.gstencils_refconv = ri.gstencils * F;
-    ri.hbm_gbs = points * times * 3.0 * sizeof(double) / ri.sweep_seconds / 1e9;  // cur and prev read, prev written
-    ri.variant = plan->p.variant;
-    ri.steps_per_launch = lora::leapfrog_depth(plan->p);
-    lora::set_last_run_info(ri);
-    if (info) *info = ri;
-    if (!quiet) {
-        const double secs = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() / 1e6;
-        std::printf("%s\n", lora::run_label(shape));
-        std::printf("Time = %lld[ms]\n", (long long) std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count());
-        std::printf("GStencil/s = %f\n", points * times * F / secs / 1e9);
-        std::fflush(stdout);
-    }
-    return LORA_OK;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();
+    if ((rc = lora::hip_status(hipMemcpy(out, times % 2 ? d_prev : d_cur, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    return g.finish(times, 3.0, lora::leapfrog_depth(plan->p), quiet, info);  // cur and prev read, prev written
 }
 
 }  // extern "C"

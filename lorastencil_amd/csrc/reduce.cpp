@@ -1,10 +1,10 @@
-// reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip) and what is built on them: lora_plan_stats,
-// lora_plan_diff, lora_plan_residual and lora_plan_residual_src (kernels_residual.hip), lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until and its group-A form.
+// reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip; their records: lora_plan::records) and what is
+// built on them: lora_plan_stats, lora_plan_diff, lora_plan_residual and lora_plan_residual_src (kernels_residual.hip),
+// lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until, what it shares with the Chebyshev one (bad_until,
+// until_decide) and its group-A form (its skeleton: hostrun.cpp).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 
 #include "engine.h"
 #include "residual_tiles.h"
@@ -68,23 +68,12 @@ bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a,
 
 namespace {
 
-// the plan's records on the current device (freed by release_run_state)
+// the plan's records on the current device
 int ensure_records(lora_plan *plan, ReduceRecord **out) {
     int dev = 0;
     LORA_HIP_TRY(hipGetDevice(&dev));
-    if (plan->reduce_buf && plan->reduce_device != dev) {
-        (void) hipFree(plan->reduce_buf);
-        plan->reduce_buf = nullptr;
-    }
-    if (!plan->reduce_buf) {
-        if (hipMalloc(&plan->reduce_buf, sizeof(ReduceRecord) * (kReduceMaxGroups + 1)) != hipSuccess) {
-            (void) hipGetLastError();
-            plan->reduce_buf = nullptr;
-            return LORA_ENOMEM;
-        }
-        plan->reduce_device = dev;
-    }
-    *out = static_cast<ReduceRecord *>(plan->reduce_buf);
+    if (!plan->records.ensure(sizeof(ReduceRecord) * (kReduceMaxGroups + 1), false)) return LORA_ENOMEM;
+    *out = static_cast<ReduceRecord *>(plan->records.ptr);
     return LORA_OK;
 }
 
@@ -98,10 +87,7 @@ int resolve_range(const Plan &p, int &begin, int &end) {
 // what every reduction entry checks before it touches the device
 int admit(const void *a, const void *b, hipStream_t s) {
     if (int rc = check_buffers(a, b)) return rc;
-    if (lora_device_count() <= 0) {
-        set_last_error_text("no HIP device visible");
-        return LORA_ENODEVICE;
-    }
+    if (lora_device_count() <= 0) return no_device();
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) {
         (void) hipGetLastError();
@@ -181,6 +167,22 @@ int no_residual_kernel() {
 }
 
 }  // namespace
+
+bool bad_until_schedule(const lora_until *u) { return u->check_every < 2 || u->check_every % 2 || u->max_times < 0; }
+bool bad_until(const lora_until *u) {
+    if (bad_until_schedule(u) || (u->norm != LORA_NORM_MAX && u->norm != LORA_NORM_RMS)) return true;
+    return !(u->tol >= 0.0) || !(u->rtol >= 0.0);  // (a NaN fails both)
+}
+
+bool until_decide(const lora_until *u, lora_until_result *r) {
+    r->checks += 1;
+    r->residual = u->norm == LORA_NORM_RMS ? std::sqrt(r->last.sum_sq / (double) r->last.count) : r->last.max_abs;
+    if (r->last.nonfinite > 0)
+        r->diverged = 1;
+    else if (r->residual <= u->tol + u->rtol * r->last.a_abs_max)
+        r->converged = 1;
+    return r->diverged || r->converged;
+}
 
 int admit_reduction(const void *a, const void *b, hipStream_t s) { return admit(a, b, s); }
 int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s) {
@@ -306,10 +308,7 @@ void lora_grid_stats_merge(lora_grid_stats *into, const lora_grid_stats *part) {
 }
 
 int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_until *u, lora_until_result *r, void *stream) {
-    if (!plan || !d_buf0 || !d_buf1 || !u || !r || d_buf0 == d_buf1) return LORA_EINVAL;
-    if (u->check_every < 2 || u->check_every % 2 || u->max_times < 0) return LORA_EINVAL;
-    if (u->norm != LORA_NORM_MAX && u->norm != LORA_NORM_RMS) return LORA_EINVAL;
-    if (!(u->tol >= 0.0) || !(u->rtol >= 0.0)) return LORA_EINVAL;  // (a NaN fails both)
+    if (!plan || !d_buf0 || !d_buf1 || !u || !r || d_buf0 == d_buf1 || lora::bad_until(u)) return LORA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = lora::admit(d_buf0, d_buf1, s)) return rc;
     const Plan &p = plan->p;
@@ -331,94 +330,38 @@ int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_
             if (int rc = lora_plan_step(plan, d_buf0, d_buf1, stream)) return rc;
             if (int rc = lora::diff_range(plan, d_buf1, d_buf0, 0, p.dims[0], &r->last, s)) return rc;
         }
-        r->checks += 1;
-        r->residual = u->norm == LORA_NORM_RMS ? std::sqrt(r->last.sum_sq / (double) r->last.count) : r->last.max_abs;
-        if (r->last.nonfinite > 0) {
-            r->diverged = 1;
-            break;
-        }
-        if (r->residual <= u->tol + u->rtol * r->last.a_abs_max) {
-            r->converged = 1;
-            break;
-        }
+        if (lora::until_decide(u, r)) break;
     }
     return LORA_OK;
 }
 
 int lora_run_host_until(int shape, int dtype, const void *in, void *out, const double *params, const int *dims, const lora_until *u,
                         lora_until_result *r, int quiet, lora_run_info *info) {
-    if (!in || !out || !dims || !u || !r) return LORA_EINVAL;
-    if (u->check_every < 2 || u->check_every % 2 || u->max_times < 0) return LORA_EINVAL;
-    if (lora_device_count() <= 0) {
-        lora::set_last_error_text("no HIP device visible");
-        return LORA_ENODEVICE;
-    }
-    lora_plan *plan = nullptr;
-    int rc = lora_plan_create(&plan, shape, dtype, dims, params);
+    if (!in || !out || !dims || !u || !r || lora::bad_until_schedule(u)) return LORA_EINVAL;  // (the rest of `u`: lora_plan_run_until)
+    lora::HostRun g;
+    int rc = g.open(shape, dtype, dims, params);
     if (rc != LORA_OK) return rc;
     if (dtype == LORA_BF16)
-        if (int src_rc = lora::default_source_refused("a bf16 run")) {
-            lora_plan_destroy(plan);
-            return src_rc;
-        }
-    struct Guard {
-        lora_plan *p;
-        void *b[2] = {nullptr, nullptr};
-        hipStream_t s = nullptr;
-        void *src = nullptr;
-        ~Guard() {
-            if (src) (void) hipFree(src);
-            for (void *x : b)
-                if (x) (void) hipFree(x);
-            if (s) (void) hipStreamDestroy(s);
-            lora_plan_destroy(p);
-        }
-    } g{plan};
-
-    using clock = std::chrono::steady_clock;
-    const size_t esize = dtype == LORA_BF16 ? 2 : sizeof(double);
-    const size_t bytes = lora_padded_count(shape, dims) * esize;
-    const auto t_total0 = clock::now();
-    LORA_HIP_TRY(hipMalloc(&g.b[0], bytes));
-    LORA_HIP_TRY(hipMalloc(&g.b[1], bytes));
+        if (int src_rc = lora::default_source_refused("a bf16 run")) return src_rc;
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    LORA_HIP_TRY(g.alloc(2));
     LORA_HIP_TRY(hipMemcpy(g.b[0], in, bytes, hipMemcpyHostToDevice));  // whole padded input, halo included
     LORA_HIP_TRY(hipMemset(g.b[1], 0, bytes));
     if (int src_rc = lora::attach_default_source(plan, bytes, &g.src)) return src_rc;  // the thread's default source, beside the grid
-    LORA_HIP_TRY(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
+    LORA_HIP_TRY(g.stream());
     (void) lora_plan_prepare_run(plan, u->check_every);
     LORA_HIP_TRY(hipDeviceSynchronize());
 
-    const auto t0 = clock::now();
+    g.tic();
     rc = lora_plan_run_until(plan, g.b[0], g.b[1], u, r, g.s);
     if (rc != LORA_OK) return rc;
     LORA_HIP_TRY(hipStreamSynchronize(g.s));
-    const auto t1 = clock::now();
+    g.toc();  // the sweeps and their checks
 
     // 1D copies all but the last element (1d/gpu_1r.cu:134); the level is in buffer 0 (times_done is even)
-    LORA_HIP_TRY(hipMemcpy(out, g.b[0], plan->p.ndim == 1 ? bytes - esize : bytes, hipMemcpyDeviceToHost));
-    const auto t_total1 = clock::now();
-
-    double points = 1.0;
-    for (int d = 0; d < plan->p.ndim; ++d) points *= dims[d];
-    const int times = r->times_done, F = lora_shape_gstencil_factor(shape);
-    lora_run_info ri;
-    ri.sweep_seconds = std::chrono::duration<double>(t1 - t0).count();  // the sweeps and their checks
-    ri.total_seconds = std::chrono::duration<double>(t_total1 - t_total0).count();
-    ri.gstencils = points * times / ri.sweep_seconds / 1e9;
-    ri.gstencils_refconv = ri.gstencils * F;
-    ri.hbm_gbs = points * times * (plan->p.source ? 3.0 : 2.0) * esize / ri.sweep_seconds / 1e9;  // a source is one more read
-    ri.variant = plan->p.variant;
-    ri.steps_per_launch = plan->p.steps_per_launch;
-    lora::set_last_run_info(ri);
-    if (info) *info = ri;
-    if (!quiet) {
-        const double secs = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() / 1e6;
-        std::printf("%s\n", lora::run_label(shape));
-        std::printf("Time = %lld[ms]\n", (long long) std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count());
-        std::printf("GStencil/s = %f\n", points * times * F / secs / 1e9);
-        std::fflush(stdout);
-    }
-    return LORA_OK;
+    LORA_HIP_TRY(hipMemcpy(out, g.b[0], plan->p.ndim == 1 ? bytes - g.esize : bytes, hipMemcpyDeviceToHost));
+    return g.finish(r->times_done, plan->p.source ? 3.0 : 2.0, plan->p.steps_per_launch, quiet, info);  // a source is one more read
 }
 
 }  // extern "C"
