@@ -173,6 +173,15 @@ int lora_last_run_info(lora_run_info *info);
  *    A plan fixes shape, interior dims, weights and kernel variant; it owns no grid memory.
  *    Buffers are PADDED device arrays laid out like the host arrays of group A; `stream` is a
  *    hipStream_t passed as void* (NULL = the null stream).  Calls are asynchronous.
+ *    Stream ordering: everything a call enqueues -- kernels, halo copies, resets and wraps, the copies in and out of the
+ *    extended periodic grid, a graph launch, record read-backs -- is ordered on `stream` and on no other stream, the null
+ *    stream included; a non-blocking stream with work pending on other streams is served as well as an idle device.  The
+ *    grids a plan allocates on first need (scratch grid, leapfrog grids, probe grid, records, extended periodic grids) are
+ *    allocated inside the call (a hipMalloc, on the host) and are NOT initialised by it: the call writes every cell of them
+ *    on `stream` before it reads it, so first-need allocation waits for no stream and leaves no work on any other one.
+ *    The lora_plan_prepare_* calls only move that hipMalloc out of a timed region.  The entries that return a result to
+ *    the host (stats, diff, residual, residual_src, the until-drivers) wait for `stream`, not for the device.
+ *    (tests/test_gpu_stream_order.py; DESIGN section 7, "Stream ordering".)
  *    Alignment: every buffer given to a launch or a run must be 16-byte aligned (LORA_EUNSUPPORTED otherwise) and need
  *    not be more -- a sub-array of a bigger allocation will do.  No kernel reads or writes global memory in pieces wider
  *    than 16 bytes, and each piece sits at a multiple of its width from the buffer's base (of 8 bytes on the paths that
@@ -672,6 +681,7 @@ int lora_slab_store(lora_slab *slab, void *host_global_padded);
 /* which = 0 / 1: the two local device buffers; anything else: the one holding the current time level */
 void *lora_slab_buffer(lora_slab *slab, int which);
 void *lora_slab_stream(lora_slab *slab); /* the hipStream_t its sweeps run on */
+void *lora_slab_comm_stream(lora_slab *slab); /* the hipStream_t its ghost-zone exchanges run on */
 lora_plan *lora_slab_plan(lora_slab *slab);
 /* Several slabs of ONE decomposition driven by this host thread (one process, N devices): launches and exchanges are
  * interleaved across the slabs, every exchange inside one group. */
@@ -729,6 +739,7 @@ int lora_block_sync(lora_block *block);
 int lora_block_store(lora_block *block, void *host_global_padded);
 void *lora_block_buffer(lora_block *block, int which);
 void *lora_block_stream(lora_block *block);
+void *lora_block_comm_stream(lora_block *block); /* the hipStream_t its ghost-zone exchanges run on */
 lora_plan *lora_block_plan(lora_block *block);
 /* Group A's generic operator on a grid[0] x grid[1] grid of blocks, one per device of this node (RCCL from
  * ncclCommInitAll; LORA_SLAB_LOOPBACK=1: all blocks on device 0 with the loopback exchange).  What the CLIs' --grid=AxB runs. */

@@ -181,6 +181,7 @@ SIGNATURES = {
     "lora_slab_store": (ctypes.c_int, [_vp, _vp]),
     "lora_slab_buffer": (_vp, [_vp, ctypes.c_int]),
     "lora_slab_stream": (_vp, [_vp]),
+    "lora_slab_comm_stream": (_vp, [_vp]),
     "lora_slab_plan": (_vp, [_vp]),
     "lora_slab_run_many": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int]),
     "lora_slab_refresh_ghosts_many": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int]),
@@ -194,6 +195,7 @@ SIGNATURES = {
     "lora_block_store": (ctypes.c_int, [_vp, _vp]),
     "lora_block_buffer": (_vp, [_vp, ctypes.c_int]),
     "lora_block_stream": (_vp, [_vp]),
+    "lora_block_comm_stream": (_vp, [_vp]),
     "lora_block_plan": (_vp, [_vp]),
     "lora_run_host_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                             ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp]),

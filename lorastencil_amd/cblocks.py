@@ -48,6 +48,12 @@ class Block:
         _lib.check(_lib.lib().lora_block_info(self._h, ctypes.byref(i)), "lora_block_info")
         return i
 
+    def stream(self) -> int:
+        return int(_lib.lib().lora_block_stream(self._h) or 0)  # the hipStream_t the block's sweeps run on
+
+    def comm_stream(self) -> int:
+        return int(_lib.lib().lora_block_comm_stream(self._h) or 0)  # ... and the one its exchanges run on
+
     def load(self, a: np.ndarray) -> None:
         a = np.ascontiguousarray(a)
         _lib.check(_lib.lib().lora_block_load(self._h, a.ctypes.data_as(ctypes.c_void_p)), "lora_block_load")
@@ -87,6 +93,12 @@ class BlockGrid:
 
     def info(self, r: int = 0):
         return self.blocks[r].info()
+
+    def stream(self, r: int = 0) -> int:
+        return self.blocks[r].stream()
+
+    def comm_stream(self, r: int = 0) -> int:
+        return self.blocks[r].comm_stream()
 
     def load(self, a) -> None:
         for b in self.blocks:

@@ -82,6 +82,12 @@ class SlabSet:
         check(_lib.lib().lora_slab_info(self._h[i], ctypes.byref(si)), "lora_slab_info")
         return si
 
+    def stream(self, i: int = 0) -> int:
+        return int(_lib.lib().lora_slab_stream(self._h[i]) or 0)  # the hipStream_t slab i's sweeps run on
+
+    def comm_stream(self, i: int = 0) -> int:
+        return int(_lib.lib().lora_slab_comm_stream(self._h[i]) or 0)  # ... and the one its exchanges run on
+
     def load(self, global_padded: np.ndarray):
         a = np.ascontiguousarray(global_padded)
         for h in self._h:

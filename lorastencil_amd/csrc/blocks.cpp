@@ -476,6 +476,7 @@ void *lora_block_buffer(lora_block *s, int which) {
     return which == 0 || which == 1 ? s->buf[which] : s->buf[s->cur];
 }
 void *lora_block_stream(lora_block *s) { return s ? s->cs : nullptr; }
+void *lora_block_comm_stream(lora_block *s) { return s ? s->ms : nullptr; }
 lora_plan *lora_block_plan(lora_block *s) { return s ? s->plan : nullptr; }
 
 // buffer 0 <- this block's cells of the padded GLOBAL host array (ghost cells and pads included), buffer 1 <- 0

@@ -148,19 +148,13 @@ bool DeviceGrid::ready(size_t want) const {
     return ptr && bytes == want && device == dev;
 }
 
-bool DeviceGrid::ensure(size_t want, bool zero) {
+bool DeviceGrid::ensure(size_t want) {
     if (ready(want)) return true;
     release();
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipMalloc(&ptr, want) != hipSuccess) {
         (void) hipGetLastError();
         ptr = nullptr;
-        return false;
-    }
-    // zeroed: the cells no kernel ever writes (pads beyond the halo ring do not exist; the ring is copied per run)
-    if (zero && hipMemset(ptr, 0, want) != hipSuccess) {
-        (void) hipGetLastError();
-        release();
         return false;
     }
     bytes = want;
@@ -287,7 +281,9 @@ static bool ensure_scratch(lora_plan *plan) {
     const size_t bytes = lora_plan_padded_bytes(plan);
     if (plan->scratch.ready(bytes)) return true;
     drop_graph(plan);  // a captured run holds the old grid's address
-    return plan->scratch.ensure(bytes, true);
+    // (not zeroed: every run copies buffer 0's ring into it -- there are no pads beyond the ring -- and a launch writes its whole
+    // interior, both on the run's stream, before the next launch reads it)
+    return plan->scratch.ensure(bytes);
 }
 
 // 1D runs with the automatic launch depth fuse more applications per launch the longer the run is: 8 is the plan's
@@ -540,7 +536,7 @@ static lora_plan *torus_prepare(lora_plan *plan) {
     if (ok && p.steps_per_launch_req > 1) (void) lora_plan_set_option(tp, "steps_per_launch", p.steps_per_launch_req);
     ok = ok && tp->p.steps_per_launch >= 2 && tp->p.steps_per_launch <= kmax;
     const size_t bytes = ok ? lora_plan_padded_bytes(tp) : 0;
-    ok = ok && plan->torus_buf[0].ensure(bytes, false) && plan->torus_buf[1].ensure(bytes, false);
+    ok = ok && plan->torus_buf[0].ensure(bytes) && plan->torus_buf[1].ensure(bytes);
     if (!ok) {
         lora_plan_destroy(tp);
         for (lora::DeviceGrid &b : plan->torus_buf) b.release();
@@ -719,7 +715,7 @@ static void drop_graph(lora_plan *plan) {
 }
 
 // Everything lora_plan_run(times) would allocate on first need, now: the scratch grid of a schedule with an odd number of
-// fused launches (a hipMalloc + hipMemset of one more padded grid -- usually a millisecond or two, but on a fresh device
+// fused launches (a hipMalloc of one more padded grid -- usually a millisecond or two, but on a fresh device
 // it has taken 60 ms, INSIDE whatever region the caller was timing: the "four times slower" runs of DESIGN section 7), the
 // extended grid's plan and buffers of a periodic run.  Idempotent; lora_plan_run works without it.
 int lora_plan_prepare_run(lora_plan *plan, int times) {
@@ -756,8 +752,8 @@ int lora_plan_run(lora_plan *plan, void *d_buf0, void *d_buf1, int times, void *
           plan->graph_times == times && plan->graph_epoch == p.epoch)) {
         drop_graph(plan);
         if (int rc = lora::check_buffers(d_buf0, d_buf1)) return rc;
-        // a scratch grid, if this run's schedule wants one, is allocated BEFORE the capture (hipMalloc and the null-stream
-        // memset do not belong inside one); while capturing, run_launches only uses a grid that is already there
+        // a scratch grid, if this run's schedule wants one, is allocated BEFORE the capture (hipMalloc does not belong inside
+        // one); while capturing, run_launches only uses a grid that is already there
         (void) plan_schedule(plan, times, true);
         if (p.boundary == LORA_BC_PERIODIC && times >= 2) (void) torus_prepare(plan);  // (likewise: the extended grid's buffers)
         hipGraph_t graph = nullptr;

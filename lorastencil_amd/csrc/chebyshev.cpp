@@ -65,8 +65,9 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
     // probe's; sum_sq -- the RMS norm's -- is summed in another order there, so that norm keeps the two passes and their grid
     const bool fused = u->norm == LORA_NORM_MAX && lora::has_fused_residual(p);
     if (!fused) {
-        // (only interior cells of it are ever read, each after the probe's sweep wrote it)
-        if (!plan->cheb_probe.ensure(lora_plan_padded_bytes(plan), true)) return LORA_ENOMEM;
+        // (not zeroed: the difference loads whole 16-byte pieces, but selects the halo cells of a piece away before any arithmetic
+        // -- kernels_reduce.hip -- and every interior cell is read after the probe's sweep wrote it, on the same stream)
+        if (!plan->cheb_probe.ensure(lora_plan_padded_bytes(plan))) return LORA_ENOMEM;
         if (plan->cheb_probe.ptr == d_prev || plan->cheb_probe.ptr == d_cur || plan->cheb_probe.ptr == d_f) return LORA_EINVAL;
     }
     (void) lora_plan_prepare_leapfrog(plan, u->check_every);

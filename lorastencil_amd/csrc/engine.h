@@ -352,7 +352,11 @@ struct DeviceGrid {
     size_t bytes = 0;
     int device = -1;
     bool ready(size_t want) const;        // a grid of `want` bytes on the current device is there (no allocation)
-    bool ensure(size_t want, bool zero);  // ... or is now, in place of what was held; false: no grid (the holder is empty)
+    // ... or is now, in place of what was held; false: no grid (the holder is empty).  A fresh grid is NOT initialised: no
+    // stream is known here, and a hipMemset on the null stream returns before it has run and orders nothing against the
+    // caller's non-blocking stream ("Stream ordering").  Every driver writes each cell of its grid, on its caller's
+    // stream, before anything reads it.
+    bool ensure(size_t want);
     void release();
 };
 

@@ -68,8 +68,8 @@ bool any_equal(const void *const *b, int n) {
 // the two scratch grids, both or neither
 bool ensure_scratch(lora_plan *plan) {
     const size_t bytes = lora_plan_padded_bytes(plan);
-    // (the ring of each is copied per run, its interior written before it is read)
-    if (plan->leap[0].ensure(bytes, true) && plan->leap[1].ensure(bytes, true)) return true;
+    // (not zeroed: the ring of each is copied per run, its interior written before it is read, all on the run's stream)
+    if (plan->leap[0].ensure(bytes) && plan->leap[1].ensure(bytes)) return true;
     for (DeviceGrid &g : plan->leap) g.release();
     return false;
 }

@@ -72,7 +72,7 @@ namespace {
 int ensure_records(lora_plan *plan, ReduceRecord **out) {
     int dev = 0;
     LORA_HIP_TRY(hipGetDevice(&dev));
-    if (!plan->records.ensure(sizeof(ReduceRecord) * (kReduceMaxGroups + 1), false)) return LORA_ENOMEM;
+    if (!plan->records.ensure(sizeof(ReduceRecord) * (kReduceMaxGroups + 1))) return LORA_ENOMEM;
     *out = static_cast<ReduceRecord *>(plan->records.ptr);
     return LORA_OK;
 }

@@ -634,6 +634,7 @@ void *lora_slab_buffer(lora_slab *s, int which) {
     return which == 0 || which == 1 ? s->buf[which] : s->buf[s->cur];
 }
 void *lora_slab_stream(lora_slab *s) { return s ? s->cs : nullptr; }
+void *lora_slab_comm_stream(lora_slab *s) { return s ? s->ms : nullptr; }
 lora_plan *lora_slab_plan(lora_slab *s) { return s ? s->plan : nullptr; }
 
 static int reset_state(lora_slab *s) {
