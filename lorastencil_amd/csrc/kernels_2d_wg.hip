@@ -26,6 +26,12 @@
 //     fits 128 VGPRs = four waves per SIMD (two 8-wave workgroups per CU) where six levels in one wave would need 190.
 //   * Stage 0 issues the loads (global -> LDS, one 1 KiB piece per wave and row, D rows ahead), the last stage the stores:
 //     no wave has both in its vmcnt, so "row r has landed" is exactly vmcnt(D - 1) and stores are never waited for.
+//   * What a lane reads back from a level row it mostly wrote itself: pieces 0 of the window of level l are the pair the
+//     same lane published as level l - 1 one step earlier.  Where both levels belong to one wave (all but the first level
+//     of a stage) that pair stays in two registers per level and the window is three 16-byte LDS reads, not four
+//     (K = 6: 70 instead of 84 per wave and 7 steps).  In interior steps of the nested-profile form the window of the
+//     level below is fetched between the profile phase of a level (after which its own window is dead) and its fourteen
+//     scatter multiply-adds, and waited for ahead of the level's ds_write: no more registers than before (116).
 //   * The launch is ONE round: strips x chunks = the workgroups that are resident at once (2 per CU), every chunk as
 //     long as that allows (16384^2: 35 strips x 14 chunks of 1171 rows, 7 K - 1 = 41 recomputed steps each = 3.5 %).
 //   * Halo semantics (as kernels_2d_stream.hip): cells of an intermediate level outside the interior are 0 at
@@ -165,29 +171,45 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
 #pragma unroll
             for (int k = 0; k < 7; ++k) pa[j][k] = pb[j][k] = 0.0;
         const double *const winp = lds + 2 * t;  // + constant offsets: every window and row-buffer access of this lane
-        // EDGE: per intermediate level of this wave, which of the lane's two columns are interior columns
-        // (as all-ones / zero masks)
-        unsigned cmask0[KL], cmask1[KL];
+        // The pair this lane published as level LB + j one step ago, j < KL - 1: pieces 0 of the window of level LB + j + 1,
+        // which the same lane evaluates -- kept in registers, so that level's window is three LDS reads, not four.  (EDGE
+        // steps: the blended pair, as written.)  The first level of a stage reads another wave's row: four pieces, as does
+        // level 1 from the ring.  A chunk starts with the zeros the row buffers start with.
+        constexpr int NC = KL > 1 ? KL - 1 : 1;
+        d2 own[NC];
 #pragma unroll
-        for (int j = 0; j < KL; ++j) {
-            const int c0 = j0 - 3 * K + 3 * (LB + j + 1) + 2 * t;
-            cmask0[j] = (unsigned) c0 < (unsigned) a.n ? ~0u : 0u;
-            cmask1[j] = (unsigned) (c0 + 1) < (unsigned) a.n ? ~0u : 0u;
-            asm volatile("" : "+v"(cmask0[j]), "+v"(cmask1[j]));
-        }
-        // Stage 0, EDGE: per even level 2 e + 2 (of ANY stage) the byte offset of this lane's cell in a padded row when the
+        for (int j = 0; j < NC; ++j) own[j] = (d2){0.0, 0.0};
+        // EDGE-only state, set up by edge_state() ahead of each EDGE range of groups and dead in between: the interior
+        // groups carry none of it in registers.
+        // cmask*: per intermediate level of this wave, which of the lane's two columns are interior columns (as all-ones /
+        // zero masks).
+        // Stage 0: per even level 2 e + 2 (of ANY stage) the byte offset of this lane's cell in a padded row when the
         // lane needs the source's value there (0x80000000 = beyond the descriptor's range: no memory request) --
         // `hcol` in rows of the interior (rim columns only), `hall` in rows outside it (every lane)
+        unsigned cmask0[KL], cmask1[KL];
         constexpr int NH = wg_halo_levels(K, DIRI);  // levels with halo values: level DIRI ? e + 1 : 2 e + 2 is number e
         unsigned hcol[NH > 0 ? NH : 1], hall[NH > 0 ? NH : 1];
-        if (FIRST) {
+        auto edge_state = [&]() {
+            // an opaque copy of the lane's column: two calls share no subexpression that could stay live between them
+            int te = t;
+            asm volatile("" : "+v"(te));
 #pragma unroll
-            for (int e = 0; e < NH; ++e) {
-                const int c0 = j0 - 3 * K + 3 * (DIRI ? e + 1 : 2 * e + 2) + 2 * t;
-                hall[e] = 8u * (unsigned) min(max(c0 + 4, 0), a.n + 6);
-                hcol[e] = ((unsigned) c0 < (unsigned) a.n && (unsigned) (c0 + 1) < (unsigned) a.n) ? 0x80000000u : hall[e];
+            for (int j = 0; j < KL; ++j) {
+                const int c0 = j0 - 3 * K + 3 * (LB + j + 1) + 2 * te;
+                cmask0[j] = (unsigned) c0 < (unsigned) a.n ? ~0u : 0u;
+                cmask1[j] = (unsigned) (c0 + 1) < (unsigned) a.n ? ~0u : 0u;
+                asm volatile("" : "+v"(cmask0[j]), "+v"(cmask1[j]));
             }
-        }
+            if (FIRST) {
+#pragma unroll
+                for (int e = 0; e < NH; ++e) {
+                    const int c0 = j0 - 3 * K + 3 * (DIRI ? e + 1 : 2 * e + 2) + 2 * te;
+                    hall[e] = 8u * (unsigned) min(max(c0 + 4, 0), a.n + 6);
+                    hcol[e] = ((unsigned) c0 < (unsigned) a.n && (unsigned) (c0 + 1) < (unsigned) a.n) ? 0x80000000u : hall[e];
+                    asm volatile("" : "+v"(hcol[e]), "+v"(hall[e]));
+                }
+            }
+        };
         double *const hb = lds + NS * kRowW + (K - 1) * 2 * kBufW;  // hb + (e * 2 + copy) * kRowW: halo values of level 2 e + 2
 
         auto step = [&](const int r, auto phase_tag, auto edge_tag) {
@@ -205,20 +227,34 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             const int cur = par * kBufW, prev = kBufW - cur;  // this step's / the previous step's copy of a level row
+            // the window of this wave's level number jj (global level LB + jj + 1): the pair the lane holds + three pieces, or
+            // four pieces of another wave's row / of the ring
+            auto window = [&](const int jj, double (&w)[8]) {
+                const int lw = LB + jj + 1;
+                const double *const src = lw == 1 ? winp + (r & (NS - 1)) * kRowW : winp + NS * kRowW + (lw - 2) * 2 * kBufW + prev;
+                const bool own_pair = jj >= 1;  // the level below is this wave's: its pair is in `own`
+                if (own_pair) {
+                    w[0] = own[jj >= 1 ? jj - 1 : 0].x;
+                    w[1] = own[jj >= 1 ? jj - 1 : 0].y;
+                }
+#pragma unroll
+                for (int q = own_pair ? 1 : 0; q < 4; ++q) {
+                    const d2 w2 = *reinterpret_cast<const d2 *>(src + 2 * q);
+                    w[2 * q] = w2.x;
+                    w[2 * q + 1] = w2.y;
+                }
+            };
+            // Interior steps of the nested-profile form fetch the window of the level below between the two phases of a level
+            // (rows_2d.h).  Not the EDGE steps: they are where the registers run out; not the other forms:
+            // their windows stay live through the whole level.
+            constexpr bool kEarly = !EDGE && EVAL == EVAL_NEST;
+            double win[8];
 #pragma unroll
             for (int j = KL - 1; j >= 0; --j) {
                 const int l = LB + j + 1;                    // global level (a constant after unrolling)
                 const int row = i0 - 3 * K - 4 * l + 1 + r;  // the row this level completes now
-                const bool from_ring = l == 1;               // level 1 reads the input row
                 const bool to_global = l == K;               // level K is the output
-                const double *const src = from_ring ? winp + (r & (NS - 1)) * kRowW : winp + NS * kRowW + (l - 2) * 2 * kBufW + prev;
-                double win[8];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const d2 w2 = *reinterpret_cast<const d2 *>(src + 2 * q);
-                    win[2 * q] = w2.x;
-                    win[2 * q + 1] = w2.y;
-                }
+                if (!kEarly || j == KL - 1) window(j, win);  // (kEarly: the level above fetched it)
                 // EDGE: what this lane's cells are forced to when they lie outside the interior
                 d2 h = {0.0, 0.0};
                 if (EDGE && !to_global && ((l & 1) == 0 || DIRI))
@@ -227,7 +263,24 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
                 // first multiply-add and not a register carried around the loop
                 pa[j][(P + 6) % 7] = 0.0;
                 pb[j][(P + 6) % 7] = 0.0;
-                apply_row<EVAL, 7, P>(6, win, pa[j], pb[j], W, F);
+                if constexpr (kEarly) {
+                    // the profiles use the window up; the pieces of the next level's window travel while this level's
+                    // fourteen scatter multiply-adds issue
+                    double t0[4], t1[4];
+                    nest_profiles(win, t0, t1, F);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j > 0) window(j - 1, win);
+                    __builtin_amdgcn_sched_barrier(0);
+                    nest_scatter<7, P>(6, t0, t1, pa[j], pb[j], F);
+                    // a use of the fetched pieces AHEAD of this level's ds_write: the wait for them lands here and is a plain
+                    // lgkmcnt(0) over reads alone -- behind the write the compiler's count would wait for the write as well
+                    if (j > 0) {
+                        if (j - 1 == 0) asm volatile("" ::"v"(win[0]), "v"(win[1]));
+                        asm volatile("" ::"v"(win[2]), "v"(win[3]), "v"(win[4]), "v"(win[5]), "v"(win[6]), "v"(win[7]));
+                    }
+                } else {
+                    apply_row<EVAL, 7, P>(6, win, pa[j], pb[j], W, F);
+                }
                 d2 v;
                 v.x = pa[j][P];
                 v.y = pb[j][P];
@@ -252,6 +305,9 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
                         v = __builtin_bit_cast(d2, o);
                     }
                     *reinterpret_cast<d2 *>(const_cast<double *>(winp) + NS * kRowW + (l - 1) * 2 * kBufW + cur) = v;
+                    // what level l + 1 of this wave reads in the next step (it ran before this level in this step, on the
+                    // pair of the step before)
+                    if (j < KL - 1) own[j < KL - 1 ? j : 0] = v;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -331,6 +387,7 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
             }
             g = idle;
         }
+        edge_state();
         for (; g < g1; ++g) {
             slice();
             group(7 * g, std::true_type{});
@@ -339,6 +396,10 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
             slice();
             group(7 * g, std::false_type{});
         }
+        // again: pure functions of the arguments and the lane, cheaper than ten registers through the loop above.  (Not at one
+        // level per wave: registers are no concern there, and the scalars the second call keeps alive cost two
+        // instantiations of the two-application launch their eighth wave per SIMD.)
+        if constexpr (KL > 1) edge_state();
         for (; g < groups; ++g) {
             slice();
             group(7 * g, std::true_type{});

@@ -31,6 +31,33 @@ struct LowRankTaps {
     double rc;       // LR_DIAMOND: +rc on the four axis tips, -rc on the four (+-2, +-2) corners
 };
 
+// EVAL_NEST in its two phases, for callers that put work of their own between them (kernels_2d_wg.hip fetches the next
+// level's window there): the four profiles of a row for column 0 / column 1 -- after which the window is dead -- and the
+// scatter of the profiles to the output rows.  apply_row<EVAL_NEST> is the one behind the other.
+__device__ __forceinline__ void nest_profiles(const double (&win)[8], double (&t0)[4], double (&t1)[4], const LowRankTaps &F) {
+    t0[0] = win[3];
+    t1[0] = win[4];
+#pragma unroll
+    for (int k = 1; k <= 3; ++k) {
+        t0[k] = fma(F.v[0][k], t0[k - 1], win[3 - k] + win[3 + k]);
+        t1[k] = fma(F.v[0][k], t1[k - 1], win[4 - k] + win[4 + k]);
+    }
+}
+
+template <int R, int ROT>
+__device__ __forceinline__ void nest_scatter(const int j, const double (&t0)[4], const double (&t1)[4], double (&acc0)[R],
+                                             double (&acc1)[R], const LowRankTaps &F) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int dy = j - r;
+        if (dy >= 0 && dy < 7) {
+            const int k = dy <= 3 ? dy : 6 - dy;
+            acc0[(r + ROT) % R] = fma(F.u[0][k], t0[k], acc0[(r + ROT) % R]);
+            acc1[(r + ROT) % R] = fma(F.u[0][k], t1[k], acc1[(r + ROT) % R]);
+        }
+    }
+}
+
 // ROT rotates the accumulator index: logical output row r lives in acc[(r + ROT) % R] (rotating register files of the
 // row-streaming kernel; 0 = the plain tile kernels).
 template <int EVAL, int R, int ROT = 0>
@@ -53,22 +80,8 @@ __device__ __forceinline__ void apply_row(const int j, const double (&win)[8], d
         }
     } else if constexpr (EVAL == EVAL_NEST) {
         double t0[4], t1[4];  // the four profiles of this row for column 0 / column 1
-        t0[0] = win[3];
-        t1[0] = win[4];
-#pragma unroll
-        for (int k = 1; k <= 3; ++k) {
-            t0[k] = fma(F.v[0][k], t0[k - 1], win[3 - k] + win[3 + k]);
-            t1[k] = fma(F.v[0][k], t1[k - 1], win[4 - k] + win[4 + k]);
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int dy = j - r;
-            if (dy >= 0 && dy < 7) {
-                const int k = dy <= 3 ? dy : 6 - dy;
-                acc0[(r + ROT) % R] = fma(F.u[0][k], t0[k], acc0[(r + ROT) % R]);
-                acc1[(r + ROT) % R] = fma(F.u[0][k], t1[k], acc1[(r + ROT) % R]);
-            }
-        }
+        nest_profiles(win, t0, t1, F);
+        nest_scatter<R, ROT>(j, t0, t1, acc0, acc1, F);
     } else if constexpr (EVAL == EVAL_LR_PYRAMID_SYM || EVAL == EVAL_LR_PYRAMID_SYM_GAP) {
         constexpr bool GAP = EVAL == EVAL_LR_PYRAMID_SYM_GAP;
         // s[k] = win[k] + win[6 - k] for column 0, win[k + 1] + win[7 - k] for column 1 (k = 0..2); centre taps as they are
