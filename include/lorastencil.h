@@ -165,6 +165,16 @@ int lora_run_host_leapfrog(int shape, const double *in_cur, const double *in_pre
 int lora_run_host_chebyshev(int shape, const double *in, const double *source, double *out, const double *params, double rho,
                             int times, const struct lora_until *u, struct lora_until_result *r, const int *dims, int quiet,
                             lora_run_info *info);
+/* Conjugate gradients for u = S(u) + f on host arrays (fp64; see lora_plan_run_cg_until in group B): uploads the padded host
+ * array `in` (the start iterate, its halo the boundary values) and `source` (a padded host array of f, or NULL: none) outside
+ * the timed region, runs lora_plan_run_cg_until and copies the iterate (the whole padded array) to `out`.  `u` and `r` must
+ * not be NULL.  Prints the operator's three lines unless `quiet`; fills lora_run_info with hbm_gbs counting 11 x 8 bytes per
+ * point and iteration and steps_per_launch = 1; the timed region holds the start-up, the iterations and their probes.
+ * LORA_EUNSUPPORTED for the plans lora_plan_run_cg_until refuses and while the thread has a default source
+ * (lora_set_default_source): the source is an argument here. */
+struct lora_cg_result;
+int lora_run_host_cg(int shape, const double *in, const double *source, double *out, const double *params, const struct lora_until *u,
+                     struct lora_cg_result *r, const int *dims, int quiet, lora_run_info *info);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -600,6 +610,86 @@ int lora_plan_run_until(lora_plan *plan, void *d_buf0, void *d_buf1, const lora_
  * with a source plus one difference. */
 int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, const void *d_f, double rho, const lora_until *u,
                                   lora_until_result *r, void *stream);
+
+/* ---- conjugate gradients for u = S(u) + f (NEW).  The operator is A = I - S, S the plan's raw single sweep; a
+ * grid the operator is applied to carries a ZERO halo, so the boundary is homogeneous on the correction and the caller's
+ * boundary values enter the first residual only.  Needs no spectral estimate, and its coefficients give the extreme eigenvalues
+ * of A -- a rho for lora_plan_run_chebyshev_until.  fp64.
+ *   Which plans (read-only option "cg": 1 or 0): fp64 plans whose option "fused_residual" reads 1 and that carry no source.
+ *   Every other plan -- bf16, the 2D matrix-pipe variant, an odd innermost extent in 2D / 3D, a plan on which
+ *   lora_plan_set_source was called -- answers LORA_EUNSUPPORTED; lora_plan_dot alone takes every plan, as lora_plan_diff does.
+ *   The three entries with a record BLOCK like the reductions and use their range rules (0, 0: the whole interior; begin == end
+ *   otherwise: the empty record {0, 0, 0, 0}; begin obeys lora_plan_region_granularity).  Status, in this order: LORA_EINVAL for
+ *   a null pointer, a bad range or begin, or two buffers of different roles that are equal (d_a == d_b of lora_plan_dot is
+ *   allowed); LORA_EUNSUPPORTED for a misaligned buffer, then for a plan without the kernels; then the reductions' codes (a
+ *   capturing stream, LORA_ENODEVICE).  The same call returns the same bits every time, whatever the plan's tuning options:
+ *   the launch geometry follows from extents, tap set and region alone, lanes, waves and workgroups fold in fixed orders, and
+ *   there are no atomics.  Every arithmetic operation named below is its own fp64 rounding, fl(); nothing is contracted.  The
+ *   buffer contract above holds: pieces of at most 16 bytes, nothing outside [base, base + lora_plan_padded_bytes). */
+typedef struct lora_grid_dot {
+    double dot, sum_abs;        /* sum of a b and of |a b| over the cells whose product is finite */
+    long long count, nonfinite; /* cells of the region; cells whose product is not finite        */
+} lora_grid_dot;
+/* *out = the lora_grid_dot of two grids over the interior cells of [begin, end), cut like lora_plan_diff; halo cells of a
+ * 16-byte piece are selected away before any arithmetic, so no halo value -- a NaN included -- reaches a result. */
+int lora_plan_dot(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_dot *out, void *stream);
+/* q = A p in one pass: on every interior cell of [begin, end) d_q = fl(d_p - acc), where acc has the bits
+ * lora_plan_step_region(plan, d_p, spare, begin, end) stores, and *out = the lora_grid_dot of a = d_p, b = d_q over those
+ * cells.  d_p is read once (halo included: the stencil needs it), d_q is written once on interior cells only -- its halo is
+ * neither read nor written.  Tiled like lora_plan_residual (csrc/residual_tiles.h). */
+int lora_plan_apply_dot(lora_plan *plan, const void *d_p, void *d_q, int begin, int end, lora_grid_dot *out, void *stream);
+/* On every interior cell of [begin, end): d_x = fl(d_x + fl(alpha d_p)), d_r = fl(d_r - fl(alpha d_q)); *out_rr = the
+ * lora_grid_dot of a = b = the new d_r.  Four reads, two writes, interior cells only (16-byte pieces; 8 bytes for the odd tail
+ * point in 1D): no halo cell of any of the four grids is loaded or stored. */
+int lora_plan_cg_update(lora_plan *plan, void *d_x, void *d_r, const void *d_p, const void *d_q, double alpha, int begin, int end,
+                        lora_grid_dot *out_rr, void *stream);
+/* On every interior cell of [begin, end): d_p = fl(d_r + fl(beta d_p)); the halo of d_p is not touched.  ASYNCHRONOUS: enqueues
+ * one launch on `stream` like lora_plan_step_region and takes a capturing stream; status codes otherwise as above. */
+int lora_plan_cg_direction(lora_plan *plan, void *d_p, const void *d_r, double beta, int begin, int end, void *stream);
+/* Solve u = S(u) + f by conjugate gradients until the TRUE residual is small.  d_x holds the start iterate, the caller's
+ * boundary values in its halo; d_f may be NULL.  `u` obeys lora_plan_run_until's rules unchanged.  Three grids r, p, q the plan
+ * owns (allocated on first need or by lora_plan_prepare_cg, never memset, freed with the plan) and a device-resident scalar
+ * state {rr, pq, alpha, beta, iteration, breakdown} with a history of max_times alphas and betas carry the run.
+ *   Start-up:  r = fl(fl(S(x) + f) - x) on the interior -- the plan's single sweep with f as its source (without f: r =
+ *   fl(S(x) - x), no zero is added), then one subtraction -- p = r with a zeroed halo (once per run, on `stream`), rr = the dot
+ *   of lora_plan_dot(r, r).
+ *   Each round enqueues check_every iterations with NO host wait between them; iteration k is
+ *     pq = lora_plan_apply_dot(p, q).dot;  alpha = rr / pq;  rr' = lora_plan_cg_update(x, r, p, q, alpha).dot;
+ *     beta = rr' / rr;  lora_plan_cg_direction(p, r, beta);  rr = rr'
+ *   over the whole interior, alpha and beta divided in IEEE fp64 on the device by one lane behind each fold and read from the
+ *   state by the next launch.  Then the round probes the true residual exactly as lora_plan_run_chebyshev_until does -- `last`
+ *   = the lora_grid_diff of a = S(d_x) + f against b = d_x: ONE lora_plan_residual_src(d_x, d_f) under LORA_NORM_MAX, else the
+ *   source sweep into q and lora_plan_diff -- and reads the state back in the same wait.  Stop rule and fields of `until` are
+ *   lora_plan_run_until's, times_done = the device's iteration count.
+ *   Breakdown: if pq is not finite or pq <= 0 (A is not positive definite on p), or rr or any product is not finite, the
+ *   one-lane update sets a sticky flag; every later launch of the run that finds it set returns before it loads or stores
+ *   anything, so d_x stays the last good iterate.  The run stops at its next probe with breakdown = 1 and diverged = 1 --
+ *   unless that probe meets the stop rule: a residual that vanished exactly (p = 0, pq = 0) is convergence, converged = 1
+ *   with breakdown = 1.  A non-finite probe gives diverged = 1.
+ *   BIT CONTRACT: d_x after k iterations is bit for bit what the caller gets by looping the four public entries above as
+ *   written, alpha and beta divided in host fp64 -- the driver launches the same kernels at the same geometry.
+ *   No halo cell of d_x is ever written, d_f is never written, everything is ordered on `stream` alone.
+ *   On return lambda_min / lambda_max are the extreme eigenvalues of the run's Lanczos tridiagonal (lora_cg_spectrum over the
+ *   times_done coefficients) -- Ritz values, inside the spectrum of A and closing in on its ends -- and rho_estimate =
+ *   max(|1 - lambda_min|, |1 - lambda_max|), the spectral radius of S to hand to lora_plan_run_chebyshev_until; all three NaN
+ *   when times_done == 0.
+ *   LORA_EINVAL for a null plan, d_x, u or r, a bad `u`, d_f == d_x, or a caller's buffer that is one of the plan's grids;
+ *   LORA_EUNSUPPORTED for a misaligned buffer, a plan whose option "cg" reads 0, and taps that are not point-symmetric (w[t] ==
+ *   w[ntaps - 1 - t] exactly, decided on the host: without it A is not symmetric); then the reductions' codes.  BLOCKS. */
+typedef struct lora_cg_result {
+    lora_until_result until;
+    double lambda_min, lambda_max, rho_estimate;
+    int breakdown;
+} lora_cg_result;
+int lora_plan_run_cg_until(lora_plan *plan, void *d_x, const void *d_f, const lora_until *u, lora_cg_result *r, void *stream);
+/* Allocate now what lora_plan_run_cg_until(..., u->max_times = max_times) would allocate on first need: the three grids and
+ * the scalar state with its history.  LORA_EINVAL for max_times < 0, LORA_EUNSUPPORTED for a plan whose option "cg" reads 0. */
+int lora_plan_prepare_cg(lora_plan *plan, int max_times);
+/* Host only: the extreme eigenvalues of the n x n Lanczos tridiagonal of a CG run's coefficients,
+ *   T[k][k] = 1 / alpha[k] + beta[k-1] / alpha[k-1] (the second term absent for k = 0),  T[k][k+1] = sqrt(beta[k]) / alpha[k],
+ * by bisection on the Sturm count, to a few ulps of the largest.  beta[n-1] is not read (beta may be NULL for n == 1).
+ * LORA_EINVAL for n < 1, a null pointer, an alpha that is not positive and finite, a beta that is negative or not finite. */
+int lora_cg_spectrum(const double *alpha, const double *beta, int n, double *lambda_min, double *lambda_max);
 void lora_plan_destroy(lora_plan *plan);
 
 /* ========================================================================================

@@ -12,12 +12,15 @@ from . import _lib
 from .ops import (  # noqa: F401
     EMPTY_STATS,
     SHAPES,
+    CgResult,
     GlibcRand,
     GridDiff,
+    GridDot,
     GridStats,
     LoraError,
     Plan,
     UntilResult,
+    cg_spectrum,
     chebyshev_coeffs,
     default_params,
     device_count,
@@ -35,6 +38,7 @@ from .ops import (  # noqa: F401
     padded_shape,
     reference_input,
     run_host,
+    run_host_cg,
     run_host_chebyshev,
     run_host_leapfrog,
     run_host_until,

@@ -84,6 +84,16 @@ class UntilResult(ctypes.Structure):
                 ("residual", ctypes.c_double), ("last", GridDiff)]
 
 
+class GridDot(ctypes.Structure):
+    """lora_grid_dot: sum of the finite products of two grids of one plan over a region."""
+    _fields_ = [("dot", ctypes.c_double), ("sum_abs", ctypes.c_double), ("count", ctypes.c_longlong), ("nonfinite", ctypes.c_longlong)]
+
+
+class CgResult(ctypes.Structure):
+    _fields_ = [("until", UntilResult), ("lambda_min", ctypes.c_double), ("lambda_max", ctypes.c_double),
+                ("rho_estimate", ctypes.c_double), ("breakdown", ctypes.c_int)]
+
+
 NORM_MAX, NORM_RMS = 0, 1
 
 _comm_begin_t = ctypes.CFUNCTYPE(ctypes.c_int, _vp)
@@ -247,6 +257,15 @@ SIGNATURES = {
                                                      _vp]),
     "lora_run_host_chebyshev": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.POINTER(Until),
                                                ctypes.POINTER(UntilResult), _ip, ctypes.c_int, ctypes.POINTER(RunInfo)]),
+    "lora_plan_dot": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDot), _vp]),
+    "lora_plan_apply_dot": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDot), _vp]),
+    "lora_plan_cg_update": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDot), _vp]),
+    "lora_plan_cg_direction": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp]),
+    "lora_plan_run_cg_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Until), ctypes.POINTER(CgResult), _vp]),
+    "lora_plan_prepare_cg": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lora_cg_spectrum": (ctypes.c_int, [_dp, _dp, ctypes.c_int, _dp, _dp]),
+    "lora_run_host_cg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Until), ctypes.POINTER(CgResult), _ip, ctypes.c_int,
+                                        ctypes.POINTER(RunInfo)]),
     "lora_run_host_leapfrog": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int,
                                               ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),

@@ -1,0 +1,315 @@
+// cg.cpp -- conjugate gradients for u = S(u) + f on A = I - S (kernels: kernels_cg.hip, the dot reduction:
+// kernels_reduce.hip / reduce.cpp).  The public entries of the three kernels, the run-until driver with a true-residual probe
+// (its grids: lora_plan::cg, its device-resident scalars: lora_plan::cg_state), the spectrum of a run's Lanczos tridiagonal
+// (host only), and the host-buffer operator (its skeleton: hostrun.cpp).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "engine.h"
+#include "residual_tiles.h"
+
+namespace lora {
+namespace {
+
+int no_cg_kernels(const Plan &p) {
+    return unsupported(p.source ? "a plan with a source has no conjugate-gradient kernels: the source of a CG run is a call argument"
+                                : "this plan has no conjugate-gradient kernels (bf16, the 2D matrix-pipe variant, or an odd innermost extent)");
+}
+
+// A = I - S is symmetric when the taps are point-symmetric
+bool taps_symmetric(const Plan &p) {
+    for (int t = 0; t < p.ntaps; ++t)
+        if (p.w[t] != p.w[p.ntaps - 1 - t]) return false;
+    return true;
+}
+
+// The launches of the three kernels over [begin, end) (a proper range) -- the ONE place both the public entries and the driver
+// go through, so that both run the same kernels at the same geometry.  Records: the plan's.
+struct CgLaunch {
+    const Plan &p;
+    ReduceRecord *records;
+    hipStream_t s;
+    ResidualTiles rt;
+    ReduceArgs a;
+    int kind = 0, groups = 0;
+    long long count = 0;
+    CgLaunch(const Plan &plan, ReduceRecord *rec, hipStream_t stream) : p(plan), records(rec), s(stream) {}
+    bool setup(int begin, int end) { return residual_tiles_setup(rt, p, begin, end) && interior_geometry(p, begin, end, a, kind, groups, count); }
+    int apply_dot(const void *d_p, void *d_q, CgState *st, int cap) const {
+        if (int rc = hip_status(launch_apply_dot(p, rt, static_cast<const double *>(d_p), static_cast<double *>(d_q), st, records, s), "apply_dot launch")) return rc;
+        return hip_status(launch_cg_fold(records, rt.groups, st, st ? CG_FOLD_APPLY : CG_FOLD_PLAIN, cap, s), "fold launch");
+    }
+    int update(void *d_x, void *d_r, const void *d_p, const void *d_q, double alpha, CgState *st, int cap) const {
+        if (int rc = hip_status(launch_cg_pointwise(CG_OP_UPDATE, a, kind, groups, static_cast<double *>(d_x), static_cast<double *>(d_r),
+                                                    static_cast<const double *>(d_p), static_cast<const double *>(d_q), alpha, st, records, s),
+                                "cg_update launch"))
+            return rc;
+        return hip_status(launch_cg_fold(records, groups, st, st ? CG_FOLD_UPDATE : CG_FOLD_PLAIN, cap, s), "fold launch");
+    }
+    int direction(void *d_p, const void *d_r, double beta, const CgState *st) const {
+        return hip_status(launch_cg_pointwise(CG_OP_DIRECTION, a, kind, groups, static_cast<double *>(d_p), nullptr, static_cast<const double *>(d_r),
+                                              nullptr, beta, st, records, s),
+                          "cg_direction launch");
+    }
+    int start(void *d_r, void *d_p, const void *d_x) const {  // r = r - x, p = r
+        return hip_status(launch_cg_pointwise(CG_OP_START, a, kind, groups, static_cast<double *>(d_r), static_cast<double *>(d_p),
+                                              static_cast<const double *>(d_x), nullptr, 0.0, nullptr, records, s),
+                          "cg_start launch");
+    }
+    int result(lora_grid_dot *out) const {  // blocks
+        ReduceRecord rec;
+        if (int rc = folded_record(records, rec, s)) return rc;
+        *out = {rec.f[0], rec.f[1], count, rec.i[0]};
+        return LORA_OK;
+    }
+};
+
+size_t state_bytes(int cap) { return sizeof(CgState) + 2 * sizeof(double) * (size_t) cap; }
+
+// the three grids and the state with room for `max_times` coefficients (an earlier, larger history is kept)
+int ensure_cg(lora_plan *plan, int max_times) {
+    const size_t bytes = lora_plan_padded_bytes(plan);
+    for (DeviceGrid &g : plan->cg)
+        if (!g.ensure(bytes)) return LORA_ENOMEM;
+    const int cap = max_times > 1 ? max_times : 1;
+    if (plan->cg_cap >= cap && plan->cg_state.ready(state_bytes(plan->cg_cap))) return LORA_OK;
+    if (!plan->cg_state.ensure(state_bytes(cap))) return LORA_ENOMEM;
+    plan->cg_cap = cap;
+    return LORA_OK;
+}
+
+// eigenvalues of the tridiagonal (d, e2 = squared off-diagonals) below x: the Sturm count
+int sturm_count(const std::vector<double> &d, const std::vector<double> &e2, double x, double tiny) {
+    int below = 0;
+    double q = 1.0;
+    for (size_t k = 0; k < d.size(); ++k) {
+        q = d[k] - x - (k ? e2[k - 1] / q : 0.0);
+        if (q == 0.0) q = -tiny;
+        below += q < 0.0;
+    }
+    return below;
+}
+
+// the smallest x in [lo, hi] with at least `want` eigenvalues below it, to the last bit the midpoint still moves
+double bisect(const std::vector<double> &d, const std::vector<double> &e2, double lo, double hi, int want, double tiny) {
+    for (;;) {
+        const double mid = lo + (hi - lo) / 2;
+        if (!(mid > lo && mid < hi)) return mid;
+        if (sturm_count(d, e2, mid, tiny) >= want)
+            hi = mid;
+        else
+            lo = mid;
+    }
+}
+
+const double kNaN = std::numeric_limits<double>::quiet_NaN();
+
+}  // namespace
+}  // namespace lora
+
+using lora::CgLaunch;
+using lora::Plan;
+
+extern "C" {
+
+int lora_plan_apply_dot(lora_plan *plan, const void *d_p, void *d_q, int begin, int end, lora_grid_dot *out, void *stream) {
+    if (!plan || !d_p || !d_q || !out) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::reduction_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p) || d_p == d_q) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_p, d_q)) return rc;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_p, d_q, s)) return rc;
+    *out = {0.0, 0.0, 0, 0};
+    if (!some) return LORA_OK;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(begin, end)) return LORA_EINVAL;
+    if (int rc = L.apply_dot(d_p, d_q, nullptr, 0)) return rc;
+    return L.result(out);
+}
+
+int lora_plan_cg_update(lora_plan *plan, void *d_x, void *d_r, const void *d_p, const void *d_q, double alpha, int begin, int end,
+                        lora_grid_dot *out_rr, void *stream) {
+    if (!plan || !d_x || !d_r || !d_p || !d_q || !out_rr) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::reduction_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p)) return LORA_EINVAL;
+    if (d_x == d_r || d_x == d_p || d_x == d_q || d_r == d_p || d_r == d_q || d_p == d_q) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_x, d_r)) return rc;
+    if (int rc = lora::check_buffers(d_p, d_q)) return rc;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_x, d_r, s)) return rc;
+    *out_rr = {0.0, 0.0, 0, 0};
+    if (!some) return LORA_OK;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(begin, end)) return LORA_EINVAL;
+    if (int rc = L.update(d_x, d_r, d_p, d_q, alpha, nullptr, 0)) return rc;
+    return L.result(out_rr);
+}
+
+int lora_plan_cg_direction(lora_plan *plan, void *d_p, const void *d_r, double beta, int begin, int end, void *stream) {
+    if (!plan || !d_p || !d_r) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::reduction_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p) || d_p == d_r) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_p, d_r)) return rc;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    if (lora_device_count() <= 0) return lora::no_device();
+    if (!some) return LORA_OK;
+    CgLaunch L(p, nullptr, static_cast<hipStream_t>(stream));
+    if (!L.setup(begin, end)) return LORA_EINVAL;
+    return L.direction(d_p, d_r, beta, nullptr);
+}
+
+int lora_plan_prepare_cg(lora_plan *plan, int max_times) {
+    if (!plan || max_times < 0) return LORA_EINVAL;
+    if (!lora::has_cg(plan->p)) return lora::no_cg_kernels(plan->p);
+    if (lora_device_count() <= 0) return lora::no_device();
+    return lora::ensure_cg(plan, max_times);
+}
+
+int lora_plan_run_cg_until(lora_plan *plan, void *d_x, const void *d_f, const lora_until *u, lora_cg_result *r, void *stream) {
+    if (!plan || !d_x || !u || !r || lora::bad_until(u) || d_f == d_x) return LORA_EINVAL;
+    if (lora::misaligned(d_x) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    const Plan &p = plan->p;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    if (!lora::taps_symmetric(p))
+        return lora::unsupported("conjugate gradients need point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_x, d_x, s)) return rc;
+    *r = {{0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}}, lora::kNaN, lora::kNaN, lora::kNaN, 0};
+    if (u->max_times < u->check_every) return LORA_OK;
+    if (int rc = lora::ensure_cg(plan, u->max_times)) return rc;
+    void *d_r = plan->cg[0].ptr, *d_p = plan->cg[1].ptr, *d_q = plan->cg[2].ptr;
+    for (const void *own : {d_r, d_p, d_q, plan->cg_state.ptr})
+        if (own == d_x || own == d_f) return LORA_EINVAL;
+    lora::CgState *st = static_cast<lora::CgState *>(plan->cg_state.ptr);
+    const int cap = plan->cg_cap;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
+
+    // the sweep of the start-up and of the two-pass probe: the plan's own single sweep with f as its source -- a copy of the
+    // plan's resolved state, as in lora_plan_run_chebyshev_until
+    Plan with_f = p;
+    with_f.source = d_f;
+    const lora::Apps whole = {1, 0, p.dims[0]};
+    // r = fl(fl(S(x) + f) - x), p = r with a zero halo, rr = r.r -- nothing read before this run wrote it, on this stream
+    if (int rc = lora::launch_apps(with_f, whole, d_x, d_r, s)) return rc;
+    if (int rc = lora::hip_status(lora::launch_halo(p, d_p, nullptr, lora::HALO_ZERO, s), "halo launch")) return rc;
+    if (int rc = L.start(d_r, d_p, d_x)) return rc;
+    if (int rc = lora::hip_status(lora::launch_reduce_dot(L.a, L.kind, L.groups, d_r, d_r, records, s), "reduction kernel launch")) return rc;
+    if (int rc = lora::hip_status(lora::launch_cg_fold(records, L.groups, st, lora::CG_FOLD_START, cap, s), "fold launch")) return rc;
+
+    // under the max norm every deciding field of the fused residual is bit for bit the two-pass probe's (see there)
+    const bool fused = u->norm == LORA_NORM_MAX;
+    lora::CgState now = {};
+    lora_until_result &ur = r->until;
+    while (ur.times_done + u->check_every <= u->max_times) {
+        for (int i = 0; i < u->check_every; ++i) {
+            if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
+            if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
+            if (int rc = L.direction(d_p, d_r, 0.0, st)) return rc;
+        }
+        // the scalars come back in the probe's wait
+        if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
+        if (fused) {
+            if (int rc = lora::residual_whole(plan, d_x, d_f, &ur.last, s)) return rc;
+        } else {
+            if (int rc = lora::launch_apps(with_f, whole, d_x, d_q, s)) return rc;
+            if (int rc = lora::diff_whole(plan, d_q, d_x, &ur.last, s)) return rc;
+        }
+        ur.times_done = (int) now.iteration;
+        bool stop = lora::until_decide(u, &ur);
+        if (now.breakdown) {
+            r->breakdown = 1;
+            if (!ur.converged) ur.diverged = 1;
+            stop = true;
+        }
+        if (stop) break;
+    }
+    const int n = ur.times_done;
+    if (n > 0) {
+        std::vector<double> hist(2 * (size_t) n);
+        const double *d_hist = reinterpret_cast<const double *>(st + 1);
+        if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * n, hipMemcpyDeviceToHost, s), "history download")) return rc;
+        if (int rc = lora::hip_status(hipMemcpyAsync(hist.data() + n, d_hist + cap, sizeof(double) * n, hipMemcpyDeviceToHost, s), "history download"))
+            return rc;
+        if (int rc = lora::hip_status(hipStreamSynchronize(s), "history download")) return rc;
+        if (lora_cg_spectrum(hist.data(), hist.data() + n, n, &r->lambda_min, &r->lambda_max) == LORA_OK)
+            r->rho_estimate = std::fmax(std::fabs(1.0 - r->lambda_min), std::fabs(1.0 - r->lambda_max));
+    }
+    return LORA_OK;
+}
+
+int lora_cg_spectrum(const double *alpha, const double *beta, int n, double *lambda_min, double *lambda_max) {
+    if (n < 1 || !alpha || !lambda_min || !lambda_max || (n > 1 && !beta)) return LORA_EINVAL;
+    for (int k = 0; k < n; ++k)
+        if (!(alpha[k] > 0.0) || !std::isfinite(alpha[k])) return LORA_EINVAL;
+    for (int k = 0; k + 1 < n; ++k)
+        if (!(beta[k] >= 0.0) || !std::isfinite(beta[k])) return LORA_EINVAL;
+    std::vector<double> d(n), e2(n > 1 ? n - 1 : 0);
+    for (int k = 0; k < n; ++k) {
+        d[k] = 1.0 / alpha[k] + (k ? beta[k - 1] / alpha[k - 1] : 0.0);
+        if (k + 1 < n) {
+            const double e = std::sqrt(beta[k]) / alpha[k];
+            e2[k] = e * e;
+        }
+    }
+    // Gershgorin: every eigenvalue lies in [lo, hi]
+    double lo = HUGE_VAL, hi = -HUGE_VAL;
+    for (int k = 0; k < n; ++k) {
+        const double rad = (k ? std::sqrt(e2[k - 1]) : 0.0) + (k + 1 < n ? std::sqrt(e2[k]) : 0.0);
+        lo = std::fmin(lo, d[k] - rad);
+        hi = std::fmax(hi, d[k] + rad);
+    }
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return LORA_EINVAL;  // (a coefficient so small that 1 / alpha overflowed)
+    const double scale = std::fmax(std::fabs(lo), std::fabs(hi));
+    const double tiny = scale * std::numeric_limits<double>::epsilon() * std::numeric_limits<double>::epsilon();
+    const double pad = scale * 4 * std::numeric_limits<double>::epsilon();
+    *lambda_min = lora::bisect(d, e2, lo - pad, hi + pad, 1, tiny);
+    *lambda_max = lora::bisect(d, e2, lo - pad, hi + pad, n, tiny);
+    return LORA_OK;
+}
+
+int lora_run_host_cg(int shape, const double *in, const double *source, double *out, const double *params, const lora_until *u,
+                     lora_cg_result *r, const int *dims, int quiet, lora_run_info *info) {
+    if (!in || !out || !dims || !u || !r || lora::bad_until(u)) return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("a conjugate-gradient run (its source is an argument)")) return rc;
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
+    if (rc != LORA_OK) return rc;
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
+    void *d_x = g.b[0], *d_f = g.b[1];
+    if ((rc = lora::hip_status(hipMemcpy(d_x, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if (source)
+        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    // set-up outside the timed region: the plan's grids and state, and one warm-up application into the plan's own q
+    if ((rc = lora_plan_prepare_cg(plan, u->max_times))) return rc;
+    lora_grid_dot warm;
+    if ((rc = lora_plan_apply_dot(plan, d_x, plan->cg[2].ptr, 0, 0, &warm, nullptr))) return rc;
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
+
+    g.tic();
+    if ((rc = lora_plan_run_cg_until(plan, d_x, d_f, u, r, g.s))) return rc;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();  // the start-up, the iterations and their probes
+    if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    // per iteration: p read, q written; x, r, p, q read, x, r written; r, p read, p written
+    return g.finish(r->until.times_done, 11.0, 1, quiet, info);
+}
+
+}  // extern "C"

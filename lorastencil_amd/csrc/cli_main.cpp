@@ -26,6 +26,8 @@
 //   --chebyshev=RHO    solve u = S(u) + f by the Chebyshev semi-iteration for a spectrum of S inside [-RHO, RHO], 0 <= RHO < 1
 //                      (lora_run_host_chebyshev): time_size steps, or with --until=TOL until the true residual
 //                      max |S(u) + f - u| <= TOL (time_size is the cap); f from --source= when given; one GPU, fp64
+//   --cg               solve u = S(u) + f by conjugate gradients (lora_run_host_cg): needs --until=TOL, time_size is the cap;
+//                      f from --source= when given; needs no RHO and prints the one its coefficients give; one GPU, fp64
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -151,6 +153,7 @@ int main(int argc, char *argv[]) {
     bool chebyshev = false;
     double chebyshev_rho = 0.0;
     bool leap3 = false;
+    bool cg = false;
     lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -210,6 +213,8 @@ int main(int argc, char *argv[]) {
         }
         else if (a == "--leap3" && kDim == 3)
             leap3 = true;
+        else if (a == "--cg")
+            cg = true;
         else if (a.rfind("--chebyshev=", 0) == 0) {
             const std::string v = a.substr(12);
             char *rest = nullptr;
@@ -279,6 +284,15 @@ int main(int argc, char *argv[]) {
         return 1;
     }
 
+    if (cg && (chebyshev || leapfrog || gpus_given || grid[0] > 0 || check || bf16)) {
+        std::cerr << "--cg runs on one GPU in fp64 against its own residual: not with --chebyshev, --leapfrog, --gpus, --grid, --check or --dtype=bf16\n";
+        return 1;
+    }
+    if (cg && !until) {
+        std::cerr << "--cg solves until the residual is small: it needs --until=TOL (time_size is the cap)\n";
+        return 1;
+    }
+
     if (leap3 && !leapfrog && !chebyshev) {
         std::cerr << "--leap3 chooses the launches of a leapfrog run: only with --leapfrog or --chebyshev\n";
         return 1;
@@ -341,7 +355,7 @@ int main(int argc, char *argv[]) {
             for (int i = 0; i < dims[0]; ++i)
                 for (int j = 0; j < (kDim > 1 ? dims[1] : 1); ++j)
                     for (int k = 0; k < (kDim > 2 ? dims[2] : 1); ++k) at(i, j, k) = source_value;
-        if (!chebyshev) lora_set_default_source(source.data());  // (a Chebyshev run takes its source as an argument)
+        if (!chebyshev && !cg) lora_set_default_source(source.data());  // (a Chebyshev or CG run takes its source as an argument)
     }
 
     if (check && (custom_bc || normalize)) {
@@ -357,7 +371,17 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     lora_until_result reached = {};
-    if (leapfrog) {
+    lora_cg_result solved = {};
+    if (cg) {
+        // the input is the start iterate, its halo the boundary values; time_size is the cap; the operator prints the reference's three lines
+        how.max_times = times;
+        const int rc = lora_run_host_cg(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, &how, &solved, dims, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+        reached = solved.until;
+    } else if (leapfrog) {
         // prev = cur: zero initial velocity; the operator prints the reference's three lines itself
         const int rc = lora_run_host_leapfrog(shape, matrix.data(), matrix.data(), output.data(), params, leapfrog_c, times, dims, 0, nullptr);
         if (rc != LORA_OK) {
@@ -442,7 +466,10 @@ int main(int argc, char *argv[]) {
     }
 
     if (extra && chebyshev) std::printf("Chebyshev: u(k+1) = w(k+1) (S(u(k)) + f) + (1 - w(k+1)) u(k-1), rho = %g, steps = %d\n", chebyshev_rho, reached.times_done);
-    if (extra && until && chebyshev)
+    if (extra && cg)
+        std::printf("Conjugate gradients on I - S: iterations = %d%s, rho_estimate = %.17g (lambda in [%g, %g])\n", reached.times_done,
+                    solved.breakdown ? ", broke down" : "", solved.rho_estimate, solved.lambda_min, solved.lambda_max);
+    if (extra && until && (chebyshev || cg))
         std::printf("Until: times_done = %d, %s, residual = %g (max |S(u) + f - u|, tol %g, checked every %d steps)\n", reached.times_done,
                     reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
                     how.check_every);
@@ -453,7 +480,7 @@ int main(int argc, char *argv[]) {
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
     if (extra && source_kind)
-        std::printf(chebyshev ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
+        std::printf(chebyshev || cg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {
         lora_run_info ri;
         if (lora_last_run_info(&ri) == LORA_OK && ri.sweep_seconds > 0) {

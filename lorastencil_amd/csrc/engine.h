@@ -229,6 +229,9 @@ hipError_t launch_reduce_stats(const ReduceArgs &a, int kind, int groups, const 
 hipError_t launch_reduce_diff(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
                               hipStream_t s);
 hipError_t launch_reduce_fold_cells(int groups, ReduceRecord *partial, hipStream_t s);
+// sum of a * b: records {dot, sum |a b|, max |a| | nonfinite} over the cells whose product is finite (lora_plan_dot)
+hipError_t launch_reduce_dot(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
+                             hipStream_t s);
 
 // ---- one sweep's change, reduced in the sweep (kernels_residual.hip; tile geometry: residual_tiles.h) -----------------
 struct ResidualTiles;
@@ -240,6 +243,31 @@ inline bool has_fused_residual(const Plan &p) {
 // The records of `d = a - in` over the tiles of `rt`, one per workgroup into partial[0 .. rt.groups), and the fold:
 // a = sweep(in), or with `f` (fp64 plans only; nullptr = none) a = fl(sweep(in) + f), f read at the reduced cells alone.
 hipError_t launch_residual(const Plan &p, const ResidualTiles &rt, const void *in, const double *f, ReduceRecord *partial, hipStream_t s);
+
+// ---- conjugate gradients on A = I - S (kernels_cg.hip; host side: cg.cpp) ---------------------------------------
+// Whether the plan has the CG kernels: fp64 plans with the fused residual kernel (so: no source, an even innermost extent in
+// 2D / 3D, the 2D direct variant).  Read-only option "cg".
+inline bool has_cg(const Plan &p) { return p.dtype == LORA_F64 && has_fused_residual(p); }
+// The scalars of a run, resident on the device; behind them in the same allocation the run's history: `cap` alphas, `cap` betas.
+struct CgState {
+    double rr, pq, alpha, beta, r_abs_max;  // r.r of the current residual, p.q of the last apply, rr / pq, rr' / rr, max |r|
+    long long iteration, breakdown;         // iterations applied; sticky: pq or rr not finite, pq <= 0, a non-finite product
+};
+enum CgOp { CG_OP_UPDATE = 0, CG_OP_DIRECTION = 1, CG_OP_START = 2 };
+// what the fold does with the scalars: nothing; rr = the record lora_plan_dot's fold left, the rest reset; pq and alpha; rr, beta,
+// the history and the iteration count
+enum CgFold { CG_FOLD_PLAIN = 0, CG_FOLD_START = 1, CG_FOLD_APPLY = 2, CG_FOLD_UPDATE = 3 };
+// q = fl(p - sweep(p)) on the interior cells of the tiles of `rt` and the records of dot(p, q), one per workgroup (no fold)
+hipError_t launch_apply_dot(const Plan &p, const ResidualTiles &rt, const double *d_p, double *d_q, const CgState *st, ReduceRecord *partial,
+                            hipStream_t s);
+// the pointwise kernels over the pieces of an interior box (reduce_geometry; kind must be KIND_F64X2):
+//   CG_OP_UPDATE     g0 = x, g1 = r, g2 = p, g3 = q: x += coef p, r -= coef q, the records of dot(r, r) (no fold)
+//   CG_OP_DIRECTION  g0 = p, g2 = r:                 p = r + coef p
+//   CG_OP_START      g0 = r, g1 = p, g2 = x:         r = r - x, p = r
+// With a state, coef is its alpha (UPDATE) / beta (DIRECTION) and a set breakdown flag makes the launch a no-op.
+hipError_t launch_cg_pointwise(int op, const ReduceArgs &a, int kind, int groups, double *g0, double *g1, const double *g2, const double *g3,
+                               double coef, const CgState *st, ReduceRecord *partial, hipStream_t s);
+hipError_t launch_cg_fold(ReduceRecord *partial, int groups, CgState *st, int phase, int cap, hipStream_t s);
 
 // ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_step2.hip: two, 2D) -------
 // Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
@@ -316,7 +344,11 @@ void set_last_error_text(const char *text);
 void set_last_run_info(const lora_run_info &info);  // what lora_last_run_info returns on this thread
 void release_run_state(lora_plan *plan);            // capi.cpp: the one place that releases what a plan owns on a device (graph, torus, every DeviceGrid)
 int admit_reduction(const void *a, const void *b, hipStream_t s);  // reduce.cpp: what every reduction entry checks before it touches the device
-int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_residual_src over the whole interior, unchecked (blocks)
+int reduction_range(const Plan &p, int &begin, int &end);  // reduce.cpp: the reductions' range rule: 1 = the whole interior (0, 0) or a proper range, 0 = an empty one, LORA_EINVAL = a bad one
+int reduction_records(lora_plan *plan, ReduceRecord **out);  // reduce.cpp: the plan's records on the current device
+bool interior_geometry(const Plan &p, int begin, int end, ReduceArgs &a, int &kind, int &groups, long long &count);  // reduce.cpp: reduce_geometry of the interior box of [begin, end) and its number of cells
+int folded_record(const ReduceRecord *records, ReduceRecord &rec, hipStream_t s);  // reduce.cpp: the folded record back on the host (blocks)
+int residual_whole(lora_plan *plan,const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_residual_src over the whole interior, unchecked (blocks)
 int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_diff over the whole interior, unchecked (blocks)
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
@@ -405,4 +437,7 @@ struct lora_plan {
     lora::DeviceGrid records;       // reduce.cpp: the reductions' records, one per workgroup and the folded one (not zeroed)
     lora::DeviceGrid leap[2];       // lora_plan_run_leapfrog[_src]: the two scratch grids, both or neither
     lora::DeviceGrid cheb_probe;    // lora_plan_run_chebyshev_until: S(u) + f of the newest level, for the two-pass probe (the RMS norm, plans without the fused residual kernel)
+    lora::DeviceGrid cg[3];         // lora_plan_run_cg_until: r, p, q -- all three or none
+    lora::DeviceGrid cg_state;      // ... its CgState and, behind it, the history of cg_cap alphas and cg_cap betas
+    int cg_cap = 0;
 };

@@ -1,5 +1,6 @@
-// kernels_reduce.hip -- reductions over the interior of padded arrays: the statistics of one grid and the difference of two
-// (lora_plan_stats / lora_plan_diff; host side: reduce.cpp).  Bandwidth-bound: a launch reads every cell of its box once.
+// kernels_reduce.hip -- reductions over the interior of padded arrays: the statistics of one grid, the difference of two and
+// their inner product (lora_plan_stats / lora_plan_diff / lora_plan_dot; host side: reduce.cpp).  Bandwidth-bound: a launch
+// reads every cell of its box once.
 //
 // Layout.  The box (lo / hi per dimension, padded coordinates) is a list of rows; a row is cut into PIECES, the naturally
 // aligned units one lane loads at once:
@@ -68,21 +69,6 @@ struct PieceOf<KIND_BF16X8> {
     __device__ static __forceinline__ double get_or_zero(const Raw &r, int j, bool keep) {  // (the select on 32 bits)
         const unsigned int w = r[j >> 1];
         return (double) __uint_as_float(keep ? ((j & 1) ? (w & 0xffff0000u) : (w << 16)) : 0u);
-    }
-};
-
-// Where a lane is on the line of pieces: the piece within its row, the row within its plane, and the cell offset.
-struct Cursor {
-    int q, i1;
-    long off;
-    __device__ __forceinline__ void advance(const ReduceArgs &a) {
-        q += a.dq;
-        const bool c = q >= a.ppr;
-        q -= c ? a.ppr : 0;
-        i1 += a.d1 + (c ? 1 : 0);
-        const bool c1 = i1 >= a.e1;
-        i1 -= c1 ? a.e1 : 0;
-        off += a.step_off + (c ? a.row_carry : 0) + (c1 ? a.plane_carry : 0);
     }
 };
 
@@ -177,6 +163,24 @@ __device__ __forceinline__ void reduce_piece(DiffAcc &acc, const ReduceArgs &a, 
     acc.idx = take ? (long long) c.off : acc.idx;
 }
 
+// A piece of two grids as products a * b (lora_plan_dot).  Halo cells count as a = b = 0.  The sum of the magnitudes tells
+// whether every product was finite (and no sum overflowed); else the piece is done again cell by cell.
+template <int KIND>
+__device__ __forceinline__ void reduce_piece(DotAcc &acc, const ReduceArgs &a, const Cursor &c, const typename PieceOf<KIND>::Raw &ra,
+                                             const typename PieceOf<KIND>::Raw &rb) {
+    typedef PieceOf<KIND> P;
+    const unsigned first = (unsigned) ((a.q0 + c.q) * P::cells - a.col_lo), width = (unsigned) (a.col_hi - a.col_lo);
+    double x[P::cells], y[P::cells];
+    bool valid[P::cells];
+#pragma unroll
+    for (int j = 0; j < P::cells; ++j) {
+        valid[j] = first + j < width;
+        x[j] = P::get_or_zero(ra, j, valid[j]);
+        y[j] = P::get_or_zero(rb, j, valid[j]);
+    }
+    acc.cells<P::cells>(x, y, valid);
+}
+
 // (four workgroups per CU, so that the kReduceMaxGroups of a big launch are all resident: 128 registers per lane at most)
 template <typename ACC, int KIND, bool DIFF>
 __global__ __launch_bounds__(kThreads, 4) void reduce_kernel(const void *__restrict__ pa, const void *__restrict__ pb, const ReduceArgs a,
@@ -252,6 +256,7 @@ __device__ __forceinline__ void resolve_cell(DiffAcc &acc, const ReduceArgs &a, 
     acc.idx += found;
 }
 __device__ __forceinline__ void resolve(StatsAcc &, const ReduceArgs &, int, const void *, const void *) {}
+__device__ __forceinline__ void resolve(DotAcc &, const ReduceArgs &, int, const void *, const void *) {}
 __device__ __forceinline__ void resolve(DiffAcc &acc, const ReduceArgs &a, int kind, const void *pa, const void *pb) {
     if (kind == KIND_F64X2)
         resolve_cell<KIND_F64X2>(acc, a, pa, pb);
@@ -303,6 +308,12 @@ hipError_t launch_reduce_stats(const ReduceArgs &a, int kind, int groups, const 
 hipError_t launch_reduce_diff(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
                               hipStream_t s) {
     return launch<DiffAcc, true>(a, kind, groups, buf_a, buf_b, partial, s);
+}
+
+// sum of a * b over the box (lora_plan_dot; a == b allowed: the grid is then loaded twice)
+hipError_t launch_reduce_dot(const ReduceArgs &a, int kind, int groups, const void *buf_a, const void *buf_b, ReduceRecord *partial,
+                             hipStream_t s) {
+    return launch<DotAcc, true>(a, kind, groups, buf_a, buf_b, partial, s);
 }
 
 // the fold alone, over difference records that carry cell indices (kernels_residual.hip)

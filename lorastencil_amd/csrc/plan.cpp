@@ -503,6 +503,8 @@ const Option kOptions[] = {
     read_only("boundary", &Plan::boundary),
     // whether lora_plan_residual has a kernel for this plan (no part of the kernel signature or of the resolved state)
     {"fused_residual", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_fused_residual(q) ? 1 : 0; }},
+    // whether the plan has the conjugate-gradient kernels (lora_plan_apply_dot, lora_plan_cg_update, lora_plan_cg_direction)
+    {"cg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_cg(q) ? 1 : 0; }},
     // whether the plan carries a source (lora_plan_set_source)
     {"source", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return q.source ? 1 : 0; }},
 };

@@ -1,5 +1,5 @@
 // reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip; their records: lora_plan::records) and what is
-// built on them: lora_plan_stats, lora_plan_diff, lora_plan_residual and lora_plan_residual_src (kernels_residual.hip),
+// built on them: lora_plan_stats, lora_plan_diff, lora_plan_dot, lora_plan_residual and lora_plan_residual_src (kernels_residual.hip),
 // lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until, what it shares with the Chebyshev one (bad_until,
 // until_decide) and its group-A form (its skeleton: hostrun.cpp).
 #include <hip/hip_runtime.h>
@@ -66,6 +66,26 @@ bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a,
     return true;
 }
 
+// the interior box of the outermost range [begin, end): its launch geometry and its number of cells
+bool interior_geometry(const Plan &p, int begin, int end, ReduceArgs &a, int &kind, int &groups, long long &count) {
+    const int *hw = halo_widths(p.ndim);
+    int lo[3], hi[3];
+    count = 1;
+    for (int d = 0; d < p.ndim; ++d) {
+        lo[d] = hw[d] + (d == 0 ? begin : 0);
+        hi[d] = hw[d] + (d == 0 ? end : p.dims[d]);
+        count *= hi[d] - lo[d];
+    }
+    return reduce_geometry(p, lo, hi, a, kind, groups);
+}
+
+// the folded record back on the host (blocks)
+int folded_record(const ReduceRecord *records, ReduceRecord &rec, hipStream_t s) {
+    LORA_HIP_TRY(hipMemcpyAsync(&rec, records + kReduceMaxGroups, sizeof rec, hipMemcpyDeviceToHost, s));
+    LORA_HIP_TRY(hipStreamSynchronize(s));
+    return LORA_OK;
+}
+
 namespace {
 
 // the plan's records on the current device
@@ -103,18 +123,9 @@ int admit(const void *a, const void *b, hipStream_t s) {
 // launches over the outermost range [begin, end) and the folded record back on the host (blocks)
 int reduce_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, ReduceRecord &rec, long long &count,
                  hipStream_t s) {
-    const Plan &p = plan->p;
-    const int *hw = halo_widths(p.ndim);
-    int lo[3], hi[3];
-    count = 1;
-    for (int d = 0; d < p.ndim; ++d) {
-        lo[d] = hw[d] + (d == 0 ? begin : 0);
-        hi[d] = hw[d] + (d == 0 ? end : p.dims[d]);
-        count *= hi[d] - lo[d];
-    }
     ReduceArgs a;
     int kind = 0, groups = 0;
-    if (!reduce_geometry(p, lo, hi, a, kind, groups)) return LORA_EINVAL;
+    if (!interior_geometry(plan->p, begin, end, a, kind, groups, count)) return LORA_EINVAL;
     ReduceRecord *records = nullptr;
     if (int rc = ensure_records(plan, &records)) return rc;
     const hipError_t e = d_b ? launch_reduce_diff(a, kind, groups, d_a, d_b, records, s) : launch_reduce_stats(a, kind, groups, d_a, records, s);
@@ -122,8 +133,25 @@ int reduce_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, i
         set_last_error("reduction kernel launch", e);
         return LORA_EHIP;
     }
-    LORA_HIP_TRY(hipMemcpyAsync(&rec, records + kReduceMaxGroups, sizeof rec, hipMemcpyDeviceToHost, s));
-    LORA_HIP_TRY(hipStreamSynchronize(s));
+    return folded_record(records, rec, s);
+}
+
+// sum of a * b over [begin, end) (a proper range): the folded record (blocks)
+int dot_range(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_dot *out, hipStream_t s) {
+    ReduceArgs a;
+    int kind = 0, groups = 0;
+    long long count = 0;
+    if (!interior_geometry(plan->p, begin, end, a, kind, groups, count)) return LORA_EINVAL;
+    ReduceRecord *records = nullptr;
+    if (int rc = ensure_records(plan, &records)) return rc;
+    const hipError_t e = launch_reduce_dot(a, kind, groups, d_a, d_b, records, s);
+    if (e != hipSuccess) {
+        set_last_error("reduction kernel launch", e);
+        return LORA_EHIP;
+    }
+    ReduceRecord rec;
+    if (int rc = folded_record(records, rec, s)) return rc;
+    *out = {rec.f[0], rec.f[1], count, rec.i[0]};
     return LORA_OK;
 }
 
@@ -185,6 +213,8 @@ bool until_decide(const lora_until *u, lora_until_result *r) {
 }
 
 int admit_reduction(const void *a, const void *b, hipStream_t s) { return admit(a, b, s); }
+int reduction_range(const Plan &p, int &begin, int &end) { return resolve_range(p, begin, end); }
+int reduction_records(lora_plan *plan, ReduceRecord **out) { return ensure_records(plan, out); }
 int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s) {
     return residual_range(plan, d_in, d_f, 0, plan->p.dims[0], out, s);
 }
@@ -227,6 +257,17 @@ int lora_plan_diff(lora_plan *plan, const void *d_a, const void *d_b, int begin,
     *out = {0.0, 0.0, 0.0, -1, 0, 0};
     if (!some) return LORA_OK;
     return lora::diff_range(plan, d_a, d_b, begin, end, out, s);
+}
+
+int lora_plan_dot(lora_plan *plan, const void *d_a, const void *d_b, int begin, int end, lora_grid_dot *out, void *stream) {
+    if (!plan || !d_a || !d_b || !out) return LORA_EINVAL;
+    const int some = lora::resolve_range(plan->p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(plan->p)) return LORA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit(d_a, d_b, s)) return rc;
+    *out = {0.0, 0.0, 0, 0};
+    if (!some) return LORA_OK;
+    return lora::dot_range(plan, d_a, d_b, begin, end, out, s);
 }
 
 int lora_plan_residual(lora_plan *plan, const void *d_in, int begin, int end, lora_grid_diff *out, void *stream) {

@@ -1,5 +1,6 @@
-// reduce_device.h -- device pieces the reductions share (kernels_reduce.hip, kernels_residual.hip): the state of a
-// difference reduction, its merge rule, and the fixed orders in which lanes and waves are folded.
+// reduce_device.h -- device pieces the reductions share (kernels_reduce.hip, kernels_residual.hip, kernels_cg.hip): the states
+// of a difference and of a product reduction, their merge rules, the walk over a box's pieces, and the fixed orders in which
+// lanes and waves are folded.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +47,79 @@ struct DiffAcc {
         r.f[3] = 0.0;
         r.i[0] = idx;
         r.i[1] = nf;
+    }
+};
+
+// The state of a product reduction (lora_plan_dot, the fused reductions of kernels_cg.hip): sum of the finite products a * b,
+// sum of their magnitudes, the largest |a| among them, and how many products were not finite.
+struct DotAcc {
+    double dot, sabs, amax;
+    long long nf;
+    __device__ __forceinline__ void init() {
+        dot = sabs = amax = 0.0;
+        nf = 0;
+    }
+    // N cells a lane holds at once (a piece, or its cells of one row); cells that are not `valid` must come in as a = b = 0.
+    // Every product is its own rounding.  One finite test of the magnitudes' sum, the exact cell-by-cell path only when it fails.
+    template <int N>
+    __device__ __forceinline__ void cells(const double (&a)[N], const double (&b)[N], const bool (&valid)[N]) {
+#pragma clang fp contract(off)
+        double pr[N], s = 0.0, sa = 0.0, am = 0.0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            pr[j] = a[j] * b[j];
+            s += pr[j];
+            sa += fabs(pr[j]);
+            am = fmax(am, fabs(a[j]));
+        }
+        if (!finite64(sa)) {  // some product is not finite (or the sum overflowed): cell by cell
+            s = sa = am = 0.0;
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const bool ok = valid[j] && finite64(pr[j]);
+                nf += (valid[j] && !ok) ? 1 : 0;
+                s += ok ? pr[j] : 0.0;
+                sa += ok ? fabs(pr[j]) : 0.0;
+                am = (ok && fabs(a[j]) > am) ? fabs(a[j]) : am;
+            }
+        }
+        dot += s;
+        sabs += sa;
+        amax = am > amax ? am : amax;
+    }
+    __device__ __forceinline__ void merge(double odot, double osabs, double oamax, long long onf) {
+        dot += odot;
+        sabs += osabs;
+        amax = oamax > amax ? oamax : amax;
+        nf += onf;
+    }
+    __device__ __forceinline__ void merge_lane(int m) {  // with the state of lane ^ m
+        merge(__shfl_xor(dot, m), __shfl_xor(sabs, m), __shfl_xor(amax, m), __shfl_xor(nf, m));
+    }
+    __device__ __forceinline__ void merge_record(const ReduceRecord &r) { merge(r.f[0], r.f[1], r.f[2], r.i[0]); }
+    __device__ __forceinline__ void to(ReduceRecord &r) const {
+        r.f[0] = dot;
+        r.f[1] = sabs;
+        r.f[2] = amax;
+        r.f[3] = 0.0;
+        r.i[0] = nf;
+        r.i[1] = 0;
+    }
+};
+
+// Where a lane is on the line of pieces of a box (reduce.cpp: reduce_geometry): the piece within its row, the row within its
+// plane, and the cell offset; one stride of the lanes further by the step's precomputed digits with carries.
+struct Cursor {
+    int q, i1;
+    long off;
+    __device__ __forceinline__ void advance(const ReduceArgs &a) {
+        q += a.dq;
+        const bool c = q >= a.ppr;
+        q -= c ? a.ppr : 0;
+        i1 += a.d1 + (c ? 1 : 0);
+        const bool c1 = i1 >= a.e1;
+        i1 -= c1 ? a.e1 : 0;
+        off += a.step_off + (c ? a.row_carry : 0) + (c1 ? a.plane_carry : 0);
     }
 };
 

@@ -231,6 +231,25 @@ class UntilResult(NamedTuple):
     last: GridDiff
 
 
+class GridDot(NamedTuple):
+    """Sum of the products a * b over a region (lora_grid_dot): ``dot`` and ``sum_abs`` = sum |a b| over the cells whose product
+    is finite, ``nonfinite`` the number of the others."""
+    dot: float
+    sum_abs: float
+    count: int
+    nonfinite: int
+
+
+class CgResult(NamedTuple):
+    """What ``run_cg_until`` returns (lora_cg_result): the until-result, the extreme Ritz values of A = I - S from the run's
+    coefficients, the spectral radius of S they imply (NaN when no iteration ran), and whether CG broke down."""
+    until: UntilResult
+    lambda_min: float
+    lambda_max: float
+    rho_estimate: float
+    breakdown: bool
+
+
 NORMS = {"max": _lib.NORM_MAX, "rms": _lib.NORM_RMS}
 
 
@@ -240,6 +259,10 @@ def _tuple_of(cls, c):
 
 def _until_result(r) -> UntilResult:
     return UntilResult(r.times_done, r.checks, bool(r.converged), bool(r.diverged), r.residual, _tuple_of(GridDiff, r.last))
+
+
+def _cg_result(r) -> CgResult:
+    return CgResult(_until_result(r.until), r.lambda_min, r.lambda_max, r.rho_estimate, bool(r.breakdown))
 
 
 def _until_arg(tol, rtol, norm, check_every, max_times):
@@ -413,6 +436,43 @@ def run_host_chebyshev(shape, in_: np.ndarray, rho: float, times: int = 0, sourc
                                              ctypes.byref(r), _dims_arg(dims), int(quiet), ctypes.byref(info)),
           f"lora_run_host_chebyshev({SHAPE_NAMES.get(sid, sid)})")
     return out, _until_result(r), info
+
+
+def cg_spectrum(alpha, beta):
+    """(lambda_min, lambda_max) of the Lanczos tridiagonal of a CG run's coefficients (lora_cg_spectrum; host only):
+    T[k, k] = 1 / alpha[k] + beta[k-1] / alpha[k-1], T[k, k+1] = sqrt(beta[k]) / alpha[k]; beta[-1] is not read."""
+    a = np.ascontiguousarray(np.atleast_1d(alpha), dtype=np.float64)
+    b = np.ascontiguousarray(np.atleast_1d(beta), dtype=np.float64)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("alpha and beta must be 1D arrays of one length")
+    lo, hi = ctypes.c_double(), ctypes.c_double()
+    check(_lib.lib().lora_cg_spectrum(_p(a), _p(b), int(a.size), ctypes.byref(lo), ctypes.byref(hi)), "lora_cg_spectrum")
+    return lo.value, hi.value
+
+
+def run_host_cg(shape, in_: np.ndarray, tol: float, source=None, rtol: float = 0.0, norm="max", check_every: int = 20,
+                max_times: int = 2000, params=None, quiet: bool = True):
+    """Conjugate gradients for u = S(u) + f from the padded float64 host array ``in_`` (the start iterate, its halo the boundary
+    values), ``source`` a padded host array of f or None (lora_run_host_cg): until the true residual is <= tol + rtol *
+    max|S(u) + f|, checked every ``check_every`` iterations, ``max_times`` at most.  Returns (the iterate as a padded array,
+    CgResult, RunInfo)."""
+    sid = shape_id(shape)
+    in_ = np.ascontiguousarray(in_, dtype=np.float64)
+    h = halo(sid)
+    if in_.ndim != len(h):
+        raise ValueError("in_ must be a padded array of the shape's rank")
+    src = None
+    if source is not None:
+        src = np.ascontiguousarray(source, dtype=np.float64)
+        if src.shape != in_.shape:
+            raise ValueError("source must be a padded array of in_'s size")
+    dims = [in_.shape[i] - 2 * h[i] for i in range(in_.ndim)]
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    u, r, info = _until_arg(tol, rtol, norm, check_every, max_times), _lib.CgResult(), RunInfo()
+    check(_lib.lib().lora_run_host_cg(sid, _p(in_), None if src is None else _p(src), _p(out), pp, ctypes.byref(u), ctypes.byref(r),
+                                      _dims_arg(dims), int(quiet), ctypes.byref(info)), f"lora_run_host_cg({SHAPE_NAMES.get(sid, sid)})")
+    return out, _cg_result(r), info
 
 
 def _operator(cname: str, nd: int):
@@ -689,6 +749,51 @@ class Plan:
         check(_lib.lib().lora_plan_run_chebyshev_until(self._h, _ptr(d_prev), _ptr(d_cur), _optr(d_f), float(rho), ctypes.byref(u),
                                                        ctypes.byref(r), _stream(stream)), "lora_plan_run_chebyshev_until")
         return _until_result(r)
+
+    # -- conjugate gradients on A = I - S (fp64 plans whose option "cg" reads 1; ``dot`` alone takes every plan)
+    def dot(self, d_a, d_b, begin: int = 0, end: int = 0, stream=None) -> GridDot:
+        """Sum of a * b over the interior of the outermost range [begin, end) (lora_plan_dot); ``d_a is d_b`` is allowed."""
+        out = _lib.GridDot()
+        check(_lib.lib().lora_plan_dot(self._h, _ptr(d_a), _ptr(d_b), int(begin), int(end), ctypes.byref(out), _stream(stream)),
+              "lora_plan_dot")
+        return _tuple_of(GridDot, out)
+
+    def apply_dot(self, d_p, d_q, begin: int = 0, end: int = 0, stream=None) -> GridDot:
+        """q = p - S(p) on the interior cells of [begin, end), each cell ``step_region``'s bits subtracted in one more rounding,
+        and the dot of p and q from the same launch (lora_plan_apply_dot).  The halo of ``d_q`` is not touched."""
+        out = _lib.GridDot()
+        check(_lib.lib().lora_plan_apply_dot(self._h, _ptr(d_p), _ptr(d_q), int(begin), int(end), ctypes.byref(out), _stream(stream)),
+              "lora_plan_apply_dot")
+        return _tuple_of(GridDot, out)
+
+    def cg_update(self, d_x, d_r, d_p, d_q, alpha: float, begin: int = 0, end: int = 0, stream=None) -> GridDot:
+        """x = x + alpha p, r = r - alpha q on the interior cells of [begin, end), every operation its own rounding; returns the
+        dot of the new r with itself (lora_plan_cg_update)."""
+        out = _lib.GridDot()
+        check(_lib.lib().lora_plan_cg_update(self._h, _ptr(d_x), _ptr(d_r), _ptr(d_p), _ptr(d_q), float(alpha), int(begin), int(end),
+                                             ctypes.byref(out), _stream(stream)), "lora_plan_cg_update")
+        return _tuple_of(GridDot, out)
+
+    def cg_direction(self, d_p, d_r, beta: float, begin: int = 0, end: int = 0, stream=None):
+        """p = r + beta p on the interior cells of [begin, end) (lora_plan_cg_direction); asynchronous."""
+        check(_lib.lib().lora_plan_cg_direction(self._h, _ptr(d_p), _ptr(d_r), float(beta), int(begin), int(end), _stream(stream)),
+              "lora_plan_cg_direction")
+
+    def prepare_cg(self, max_times: int):
+        """Allocate now what ``run_cg_until(..., max_times=max_times)`` would allocate on first need (three grids, the state)."""
+        check(_lib.lib().lora_plan_prepare_cg(self._h, int(max_times)), "lora_plan_prepare_cg")
+        return self
+
+    def run_cg_until(self, d_x, d_f, tol: float, rtol: float = 0.0, norm="max", check_every: int = 20, max_times: int = 2000,
+                     stream=None) -> CgResult:
+        """Conjugate gradients for u = S(u) + f in rounds of ``check_every`` iterations until the TRUE residual max|S(u) + f - u|
+        is <= tol + rtol * max|S(u) + f| (lora_plan_run_cg_until).  ``d_x``: the start iterate with the boundary values in its
+        halo, then the solution; ``d_f``: a padded device grid or None.  Needs point-symmetric taps.  ``rho_estimate`` of the
+        result is a spectral radius for ``run_chebyshev_until``."""
+        u, r = _until_arg(tol, rtol, norm, check_every, max_times), _lib.CgResult()
+        check(_lib.lib().lora_plan_run_cg_until(self._h, _ptr(d_x), _optr(d_f), ctypes.byref(u), ctypes.byref(r), _stream(stream)),
+              "lora_plan_run_cg_until")
+        return _cg_result(r)
 
     # -- reductions on the device (these block until the result is on the host)
     def stats(self, d_buf, begin: int = 0, end: int = 0, stream=None) -> GridStats:
