@@ -175,6 +175,18 @@ int lora_run_host_chebyshev(int shape, const double *in, const double *source, d
 struct lora_cg_result;
 int lora_run_host_cg(int shape, const double *in, const double *source, double *out, const double *params, const struct lora_until *u,
                      struct lora_cg_result *r, const int *dims, int quiet, lora_run_info *info);
+/* Implicit time steps of du/dt = S(u) + f - u on host arrays (fp64; see lora_plan_run_theta in group B): uploads the padded
+ * host array `in` (level 0, its halo the boundary values) and `source` (a padded host array of f, or NULL: none) outside the
+ * timed region, runs lora_plan_run_theta over `steps` steps and copies the last level (the whole padded array) to `out`.
+ * `result` must not be NULL.  Prints the operator's three lines unless `quiet`, counting STEPS; fills lora_run_info with
+ * steps_per_launch = 1 and hbm_gbs counting, per point and step, 3 x 8 bytes for the step's start (4 x 8 with a source) and
+ * 11 x 8 for each of its iterations on average; the timed region holds every step and the steady-state probe.  Argument rules
+ * and LORA_EUNSUPPORTED as lora_plan_run_theta, and LORA_EUNSUPPORTED while the thread has a default source
+ * (lora_set_default_source): the source is an argument here. */
+struct lora_theta_result;
+int lora_run_host_theta(int shape, const double *in, const double *source, double *out, const double *params, double theta, double tau,
+                        int steps, int max_iters, double rtol, const int *dims, int quiet, lora_run_info *info,
+                        struct lora_theta_result *result);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -690,6 +702,69 @@ int lora_plan_prepare_cg(lora_plan *plan, int max_times);
  * by bisection on the Sturm count, to a few ulps of the largest.  beta[n-1] is not read (beta may be NULL for n == 1).
  * LORA_EINVAL for n < 1, a null pointer, an alpha that is not positive and finite, a beta that is negative or not finite. */
 int lora_cg_spectrum(const double *alpha, const double *beta, int n, double *lambda_min, double *lambda_max);
+
+/* ---- implicit time stepping (NEW).  One sweep is one forward-Euler step of du/dt = S(u) + f - u with step 1.
+ * The theta scheme with step tau > 0 and 0 <= theta <= 1 (1: backward Euler, 1/2: Crank-Nicolson, 0: the explicit step) is
+ *     (1 + theta tau) u+ - theta tau S(u+) = u + (1 - theta) tau (S(u) - u) + tau f,
+ * one solve per step with A = sigma I - tau' S, sigma = fl(1 + tau'), tau' = fl(theta tau).  Started from x0 = u the first
+ * residual of that system is exactly r0 = tau (S(u) + f - u) -- the right-hand side cancels -- so no right-hand-side grid
+ * exists: conjugate gradients accumulate the increment straight into d_u.  A is symmetric for point-symmetric taps and positive
+ * definite whenever rho(S) <= 1.  Plans, range rules, status codes and their order, the bit-for-bit repeatability and the
+ * buffer contract are those of lora_plan_apply_dot above (option "cg" = 1, no source on the plan); every operation named
+ * below is its own fp64 rounding. */
+/* q = (sigma I - tau S) p in one pass: on every interior cell of [begin, end) d_q = fl(fl(sigma d_p) - fl(tau acc)), acc as in
+ * lora_plan_apply_dot, and *out = the lora_grid_dot of a = d_p, b = d_q.  Also LORA_EINVAL for a sigma or tau that is not
+ * finite.  With sigma == tau == 1 it equals lora_plan_apply_dot bit for bit in d_q and in the record on data without NaNs
+ * (1 x is exact).  The general shifted operator: screened Poisson / Helmholtz-type solves through the public CG entries. */
+int lora_plan_apply_dot_shift(lora_plan *plan, const void *d_p, void *d_q, double sigma, double tau, int begin, int end,
+                              lora_grid_dot *out, void *stream);
+/* The start of a step in one launch: on every interior cell of [begin, end) t = fl(acc + d_f) (d_f == NULL: t = acc, no zero is
+ * added), d = fl(t - d_u), r = fl(tau d), stored to BOTH d_r and d_p; *out_rr = the lora_grid_dot of a = b = r.  acc has the
+ * bits lora_plan_step_region(plan, d_u, spare, begin, end) stores.  d_u is read once, halo included; d_f at the stored cells
+ * alone, so its halo is never loaded; the halos of d_r and d_p are neither read nor written (16-byte stores, 8 bytes for the
+ * odd tail point in 1D).  d_f may be NULL, the other buffers must be pairwise distinct; LORA_EINVAL also for a tau that is not
+ * finite.  It stands for a source sweep, a subtraction, a scale, a copy and a dot. */
+int lora_plan_theta_start(lora_plan *plan, const void *d_u, const void *d_f, double tau, void *d_r, void *d_p, int begin, int end,
+                          lora_grid_dot *out_rr, void *stream);
+/* `steps` theta steps of d_u in place, the whole run enqueued on `stream` with NO host wait inside it.  The plan's three CG
+ * grids r, p, q and two device-resident states carry the run (lora_plan_prepare_theta allocates them ahead of time).
+ *   The run zeroes the halo of p once.  Each step enqueues lora_plan_theta_start(d_u, d_f, tau) -> r, p and then max_iters
+ *   iterations of
+ *     pq = lora_plan_apply_dot_shift(p, q, sigma, tau').dot;  alpha = rr / pq;  rr' = lora_plan_cg_update(d_u, r, p, q, alpha).dot;
+ *     beta = rr' / rr;  lora_plan_cg_direction(p, r, beta);  rr = rr'
+ *   over the whole interior.  One lane behind each fold keeps the scalars: behind the start's, rr = rr0 = the start's dot, the
+ *   step's iteration count 0, thresh = fl(rtol2 rr0) with rtol2 = fl(rtol rtol) from the host, and `done` cleared -- or set at
+ *   once when rr0 == 0 (the level is steady; the step counts with 0 iterations); behind the update's, alpha / beta / rr as in
+ *   lora_plan_run_cg_until and then the STOP RULE: if rr' <= thresh the step is done and counted; if it was the step's
+ *   max_iters-th iteration the step is done, counted, and counted as unconverged -- not an error.  Every launch that finds
+ *   `done` or `breakdown` set returns before it loads or stores anything, so the launches a step does not need cost a launch
+ *   each and no memory traffic; the next step's start clears `done`.  Breakdown (lora_plan_run_cg_until's rule, also a start
+ *   whose dot is not finite) is sticky for the run: d_u keeps the last good iterate and steps_done the steps finished before.
+ *   At the end the call waits ONCE on `stream`, reads the states and the history back, and stores ONE
+ *   lora_plan_residual_src(d_u, d_f) over the whole interior in r->steady: how far the last level is from the steady state.
+ *   iterations (NULL, or `steps` ints): the iterations of each finished step; for the step a breakdown interrupted the
+ *   iterations applied before it; 0 for the steps behind it.
+ *   BIT CONTRACT: d_u after the run is bit for bit what a host loop over the public entries gives that calls, per step s,
+ *   lora_plan_theta_start and then iterations[s] iterations as written above, alpha, beta, thresh and the stop test in host
+ *   fp64 -- the driver launches the same kernels at the same geometry.
+ *   No halo cell of d_u is ever written, d_f is never written, everything is ordered on `stream` alone.
+ *   LORA_EINVAL unless 0 <= theta <= 1, tau > 0 and finite, steps >= 0, max_iters >= 1, rtol >= 0 and finite; for a null plan,
+ *   d_u or r; for d_f == d_u or a caller's buffer that is one of the plan's grids.  LORA_EUNSUPPORTED for a misaligned buffer,
+ *   a plan whose option "cg" reads 0, and taps that are not point-symmetric; then the reductions' codes.  steps == 0 returns
+ *   LORA_OK and touches nothing.  BLOCKS (once, at its end).  Choose max_iters near the iterations a step needs: DESIGN 3.10
+ *   has the cost of a launch that exits early. */
+typedef struct lora_theta_result {
+    int steps_done, breakdown, unconverged_steps;
+    long long iterations_total; /* over the finished steps ...                                                     */
+    int iterations_max;         /* ... and the largest of them                                                     */
+    double last_rr0, last_rr;   /* r.r at the start of the last step begun and at the run's end (NaN: no step ran) */
+    lora_grid_diff steady;      /* a = S(d_u) + f against b = d_u after the run                                    */
+} lora_theta_result;
+int lora_plan_run_theta(lora_plan *plan, void *d_u, const void *d_f, double theta, double tau, int steps, int max_iters, double rtol,
+                        int *iterations, lora_theta_result *r, void *stream);
+/* Allocate now what lora_plan_run_theta(..., steps) would allocate on first need: the three grids, the two states and the
+ * history.  LORA_EINVAL for steps < 0, LORA_EUNSUPPORTED for a plan whose option "cg" reads 0. */
+int lora_plan_prepare_theta(lora_plan *plan, int steps);
 void lora_plan_destroy(lora_plan *plan);
 
 /* ========================================================================================

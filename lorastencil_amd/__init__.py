@@ -19,6 +19,7 @@ from .ops import (  # noqa: F401
     GridStats,
     LoraError,
     Plan,
+    ThetaResult,
     UntilResult,
     cg_spectrum,
     chebyshev_coeffs,
@@ -41,6 +42,7 @@ from .ops import (  # noqa: F401
     run_host_cg,
     run_host_chebyshev,
     run_host_leapfrog,
+    run_host_theta,
     run_host_until,
     separable_3x3x3,
     set_default_leap3,

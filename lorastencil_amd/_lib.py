@@ -94,6 +94,13 @@ class CgResult(ctypes.Structure):
                 ("rho_estimate", ctypes.c_double), ("breakdown", ctypes.c_int)]
 
 
+class ThetaResult(ctypes.Structure):
+    """lora_theta_result: what a run of the implicit stepper reports."""
+    _fields_ = [("steps_done", ctypes.c_int), ("breakdown", ctypes.c_int), ("unconverged_steps", ctypes.c_int),
+                ("iterations_total", ctypes.c_longlong), ("iterations_max", ctypes.c_int), ("last_rr0", ctypes.c_double),
+                ("last_rr", ctypes.c_double), ("steady", GridDiff)]
+
+
 NORM_MAX, NORM_RMS = 0, 1
 
 _comm_begin_t = ctypes.CFUNCTYPE(ctypes.c_int, _vp)
@@ -266,6 +273,14 @@ SIGNATURES = {
     "lora_cg_spectrum": (ctypes.c_int, [_dp, _dp, ctypes.c_int, _dp, _dp]),
     "lora_run_host_cg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Until), ctypes.POINTER(CgResult), _ip, ctypes.c_int,
                                         ctypes.POINTER(RunInfo)]),
+    "lora_plan_apply_dot_shift": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(GridDot), _vp]),
+    "lora_plan_theta_start": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDot), _vp]),
+    "lora_plan_run_theta": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, _ip,
+                                           ctypes.POINTER(ThetaResult), _vp]),
+    "lora_plan_prepare_theta": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lora_run_host_theta": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_double, _ip, ctypes.c_int, ctypes.POINTER(RunInfo), ctypes.POINTER(ThetaResult)]),
     "lora_run_host_leapfrog": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int,
                                               ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),

@@ -917,7 +917,7 @@ void release_run_state(lora_plan *plan) {
     drop_graph(plan);
     torus_drop(plan);
     for (DeviceGrid *g : {&plan->scratch, &plan->records, &plan->leap[0], &plan->leap[1], &plan->cheb_probe, &plan->cg[0], &plan->cg[1],
-                          &plan->cg[2], &plan->cg_state})
+                          &plan->cg[2], &plan->cg_state, &plan->theta_state})
         g->release();
 }
 }  // namespace lora

@@ -2,6 +2,10 @@
 // kernels_reduce.hip / reduce.cpp).  The public entries of the three kernels, the run-until driver with a true-residual probe
 // (its grids: lora_plan::cg, its device-resident scalars: lora_plan::cg_state), the spectrum of a run's Lanczos tridiagonal
 // (host only), and the host-buffer operator (its skeleton: hostrun.cpp).
+//
+// Below them the implicit time stepper (kernels: kernels_theta.hip and the pointwise kernels of kernels_cg.hip):
+// theta-scheme steps of du/dt = S(u) + f - u, each a CG solve on sigma I - tau' S started from the level itself, a whole run
+// enqueued with no host wait.  Its entries go through the same CgLaunch as everything above.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -42,12 +46,27 @@ struct CgLaunch {
         if (int rc = hip_status(launch_apply_dot(p, rt, static_cast<const double *>(d_p), static_cast<double *>(d_q), st, records, s), "apply_dot launch")) return rc;
         return hip_status(launch_cg_fold(records, rt.groups, st, st ? CG_FOLD_APPLY : CG_FOLD_PLAIN, cap, s), "fold launch");
     }
-    int update(void *d_x, void *d_r, const void *d_p, const void *d_q, double alpha, CgState *st, int cap) const {
+    // sigma p - tau S(p) in place of p - S(p): the same tiles, the same fold
+    int apply_dot_shift(const void *d_p, void *d_q, double sigma, double tau, CgState *st) const {
+        if (int rc = hip_status(launch_apply_dot_shift(p, rt, static_cast<const double *>(d_p), static_cast<double *>(d_q), sigma, tau, st, records, s),
+                                "apply_dot_shift launch"))
+            return rc;
+        return hip_status(launch_cg_fold(records, rt.groups, st, st ? CG_FOLD_APPLY : CG_FOLD_PLAIN, 0, s), "fold launch");
+    }
+    // r = p = tau (S(u) + f - u) and the fold of r.r; with a state, the step's start behind it
+    int theta_start(const void *d_u, const void *d_f, double tau, void *d_r, void *d_p, CgState *st, ThetaState *ts) const {
+        if (int rc = hip_status(launch_theta_start(p, rt, static_cast<const double *>(d_u), static_cast<const double *>(d_f), tau,
+                                                   static_cast<double *>(d_r), static_cast<double *>(d_p), st, records, s),
+                                "theta_start launch"))
+            return rc;
+        return hip_status(launch_cg_fold(records, rt.groups, st, st ? CG_FOLD_THETA_START : CG_FOLD_PLAIN, 0, s, ts), "fold launch");
+    }
+    int update(void *d_x, void *d_r, const void *d_p, const void *d_q, double alpha, CgState *st, int cap, ThetaState *ts = nullptr) const {
         if (int rc = hip_status(launch_cg_pointwise(CG_OP_UPDATE, a, kind, groups, static_cast<double *>(d_x), static_cast<double *>(d_r),
                                                     static_cast<const double *>(d_p), static_cast<const double *>(d_q), alpha, st, records, s),
                                 "cg_update launch"))
             return rc;
-        return hip_status(launch_cg_fold(records, groups, st, st ? CG_FOLD_UPDATE : CG_FOLD_PLAIN, cap, s), "fold launch");
+        return hip_status(launch_cg_fold(records, groups, st, st ? (ts ? CG_FOLD_THETA_UPDATE : CG_FOLD_UPDATE) : CG_FOLD_PLAIN, cap, s, ts), "fold launch");
     }
     int direction(void *d_p, const void *d_r, double beta, const CgState *st) const {
         return hip_status(launch_cg_pointwise(CG_OP_DIRECTION, a, kind, groups, static_cast<double *>(d_p), nullptr, static_cast<const double *>(d_r),
@@ -78,6 +97,18 @@ int ensure_cg(lora_plan *plan, int max_times) {
     if (plan->cg_cap >= cap && plan->cg_state.ready(state_bytes(plan->cg_cap))) return LORA_OK;
     if (!plan->cg_state.ensure(state_bytes(cap))) return LORA_ENOMEM;
     plan->cg_cap = cap;
+    return LORA_OK;
+}
+
+size_t theta_bytes(int cap) { return sizeof(ThetaState) + (sizeof(long long) + sizeof(double)) * (size_t) cap; }
+
+// the stepper's grids and states: the CG set, and the ThetaState with room for `steps` entries (an earlier, larger one is kept)
+int ensure_theta(lora_plan *plan, int steps) {
+    if (int rc = ensure_cg(plan, 1)) return rc;
+    const int cap = steps > 1 ? steps : 1;
+    if (plan->theta_cap >= cap && plan->theta_state.ready(theta_bytes(plan->theta_cap))) return LORA_OK;
+    if (!plan->theta_state.ensure(theta_bytes(cap))) return LORA_ENOMEM;
+    plan->theta_cap = cap;
     return LORA_OK;
 }
 
@@ -310,6 +341,158 @@ int lora_run_host_cg(int shape, const double *in, const double *source, double *
     if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
     // per iteration: p read, q written; x, r, p, q read, x, r written; r, p read, p written
     return g.finish(r->until.times_done, 11.0, 1, quiet, info);
+}
+
+// ---- the implicit stepper ------------------------------------------------------------------------------------------------------
+int lora_plan_apply_dot_shift(lora_plan *plan, const void *d_p, void *d_q, double sigma, double tau, int begin, int end, lora_grid_dot *out,
+                              void *stream) {
+    if (!plan || !d_p || !d_q || !out) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::reduction_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p) || d_p == d_q || !std::isfinite(sigma) || !std::isfinite(tau)) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_p, d_q)) return rc;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_p, d_q, s)) return rc;
+    *out = {0.0, 0.0, 0, 0};
+    if (!some) return LORA_OK;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(begin, end)) return LORA_EINVAL;
+    if (int rc = L.apply_dot_shift(d_p, d_q, sigma, tau, nullptr)) return rc;
+    return L.result(out);
+}
+
+int lora_plan_theta_start(lora_plan *plan, const void *d_u, const void *d_f, double tau, void *d_r, void *d_p, int begin, int end,
+                          lora_grid_dot *out_rr, void *stream) {
+    if (!plan || !d_u || !d_r || !d_p || !out_rr) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::reduction_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p) || !std::isfinite(tau)) return LORA_EINVAL;
+    if (d_u == d_r || d_u == d_p || d_r == d_p || d_f == d_u || d_f == d_r || d_f == d_p) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_u, d_r)) return rc;
+    if (int rc = lora::check_buffers(d_p, d_f ? d_f : d_p)) return rc;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_u, d_r, s)) return rc;
+    *out_rr = {0.0, 0.0, 0, 0};
+    if (!some) return LORA_OK;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(begin, end)) return LORA_EINVAL;
+    if (int rc = L.theta_start(d_u, d_f, tau, d_r, d_p, nullptr, nullptr)) return rc;
+    return L.result(out_rr);
+}
+
+int lora_plan_prepare_theta(lora_plan *plan, int steps) {
+    if (!plan || steps < 0) return LORA_EINVAL;
+    if (!lora::has_cg(plan->p)) return lora::no_cg_kernels(plan->p);
+    if (lora_device_count() <= 0) return lora::no_device();
+    lora::ReduceRecord *records = nullptr;  // (the run folds into the plan's records: they are part of what it needs)
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    return lora::ensure_theta(plan, steps);
+}
+
+int lora_plan_run_theta(lora_plan *plan, void *d_u, const void *d_f, double theta, double tau, int steps, int max_iters, double rtol,
+                        int *iterations, lora_theta_result *r, void *stream) {
+    if (!plan || !d_u || !r || d_f == d_u) return LORA_EINVAL;
+    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
+        !std::isfinite(rtol))
+        return LORA_EINVAL;
+    if (lora::misaligned(d_u) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    const Plan &p = plan->p;
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    if (!lora::taps_symmetric(p))
+        return lora::unsupported("the implicit stepper needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: sigma I - tau S is not symmetric otherwise");
+    *r = {0, 0, 0, 0, 0, lora::kNaN, lora::kNaN, {0.0, 0.0, 0.0, -1, 0, 0}};
+    if (steps == 0) return LORA_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_u, d_u, s)) return rc;
+    if (int rc = lora::ensure_theta(plan, steps)) return rc;
+    void *d_r = plan->cg[0].ptr, *d_p = plan->cg[1].ptr, *d_q = plan->cg[2].ptr;
+    for (const void *own : {d_r, d_p, d_q, plan->cg_state.ptr, plan->theta_state.ptr})
+        if (own == d_u || own == d_f) return LORA_EINVAL;
+    lora::CgState *st = static_cast<lora::CgState *>(plan->cg_state.ptr);
+    lora::ThetaState *ts = static_cast<lora::ThetaState *>(plan->theta_state.ptr);
+    const int cap = plan->theta_cap;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
+
+    // the operator of the step and the stop rule's factor, each operation its own rounding
+    const double tt = theta * tau, sigma = 1.0 + tt, rtol2 = rtol * rtol;
+    // the whole run is enqueued here: nothing below waits for the device before the read-back
+    if (int rc = lora::hip_status(lora::launch_cg_fold(records, 0, st, lora::CG_FOLD_THETA_INIT, cap, s, ts, rtol2, max_iters), "fold launch")) return rc;
+    if (int rc = lora::hip_status(lora::launch_halo(p, d_p, nullptr, lora::HALO_ZERO, s), "halo launch")) return rc;
+    for (int step = 0; step < steps; ++step) {
+        if (int rc = L.theta_start(d_u, d_f, tau, d_r, d_p, st, ts)) return rc;
+        for (int i = 0; i < max_iters; ++i) {
+            if (int rc = L.apply_dot_shift(d_p, d_q, sigma, tt, st)) return rc;
+            if (int rc = L.update(d_u, d_r, d_p, d_q, 0.0, st, 0, ts)) return rc;
+            if (int rc = L.direction(d_p, d_r, 0.0, st)) return rc;
+        }
+    }
+    // the one wait: the two states and the history come back behind the steady-state probe's synchronise
+    lora::CgState now = {};
+    lora::ThetaState tnow = {};
+    std::vector<long long> hist((size_t) steps);
+    if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
+    if (int rc = lora::hip_status(hipMemcpyAsync(&tnow, ts, sizeof tnow, hipMemcpyDeviceToHost, s), "state download")) return rc;
+    if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), ts + 1, sizeof(long long) * steps, hipMemcpyDeviceToHost, s), "history download"))
+        return rc;
+    if (int rc = lora::residual_whole(plan, d_u, d_f, &r->steady, s)) return rc;
+    r->steps_done = (int) tnow.steps_done;
+    r->breakdown = (now.breakdown & lora::CG_HALT_BREAKDOWN) ? 1 : 0;
+    r->unconverged_steps = (int) tnow.unconverged;
+    r->last_rr0 = tnow.rr0;
+    r->last_rr = now.rr;
+    for (int step = 0; step < steps; ++step) {
+        // a step the breakdown interrupted reports the iterations applied before it; the steps behind it never ran
+        const int k = step < r->steps_done ? (int) hist[step] : (step == r->steps_done ? (int) now.iteration : 0);
+        if (iterations) iterations[step] = k;
+        if (step < r->steps_done) {
+            r->iterations_total += k;
+            if (k > r->iterations_max) r->iterations_max = k;
+        }
+    }
+    return LORA_OK;
+}
+
+int lora_run_host_theta(int shape, const double *in, const double *source, double *out, const double *params, double theta, double tau,
+                        int steps, int max_iters, double rtol, const int *dims, int quiet, lora_run_info *info, lora_theta_result *result) {
+    if (!in || !out || !dims || !result) return LORA_EINVAL;
+    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
+        !std::isfinite(rtol))
+        return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("an implicit run (its source is an argument)")) return rc;
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
+    if (rc != LORA_OK) return rc;
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
+    void *d_u = g.b[0], *d_f = g.b[1];
+    if ((rc = lora::hip_status(hipMemcpy(d_u, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if (source)
+        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    // set-up outside the timed region: the plan's grids and states, and one warm-up application into the plan's own q
+    if ((rc = lora_plan_prepare_theta(plan, steps))) return rc;
+    lora_grid_dot warm;
+    if ((rc = lora_plan_apply_dot_shift(plan, d_u, plan->cg[2].ptr, 1.0, 1.0, 0, 0, &warm, nullptr))) return rc;
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
+
+    g.tic();
+    if ((rc = lora_plan_run_theta(plan, d_u, d_f, theta, tau, steps, max_iters, rtol, nullptr, result, g.s))) return rc;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();  // every step's start and iterations, and the steady-state probe
+    if ((rc = lora::hip_status(hipMemcpy(out, d_u, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    // per step: u (and f) read, r and p written; per iteration the eleven grids of a CG iteration (lora_run_host_cg)
+    const double per_step = (source ? 4.0 : 3.0) + (steps > 0 ? 11.0 * (double) result->iterations_total / steps : 0.0);
+    return g.finish(steps, per_step, 1, quiet, info);
 }
 
 }  // extern "C"

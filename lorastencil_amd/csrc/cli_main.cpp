@@ -28,6 +28,10 @@
 //                      max |S(u) + f - u| <= TOL (time_size is the cap); f from --source= when given; one GPU, fp64
 //   --cg               solve u = S(u) + f by conjugate gradients (lora_run_host_cg): needs --until=TOL, time_size is the cap;
 //                      f from --source= when given; needs no RHO and prints the one its coefficients give; one GPU, fp64
+//   --implicit=TAU     time_size implicit steps of du/dt = S(u) + f - u with step TAU > 0 (lora_run_host_theta), each a CG solve
+//                      on the device: --theta=TH (0 <= TH <= 1, default 1: backward Euler; 0.5: Crank-Nicolson), at most
+//                      --iters=N iterations a step (default 50) to |r| <= R |r0| with --rtol=R (default 1e-8); f from
+//                      --source= when given; one GPU, fp64
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -154,6 +158,9 @@ int main(int argc, char *argv[]) {
     double chebyshev_rho = 0.0;
     bool leap3 = false;
     bool cg = false;
+    bool implicit = false, implicit_option = false;
+    double implicit_tau = 0.0, implicit_theta = 1.0, implicit_rtol = 1e-8;
+    int implicit_iters = 50;
     lora_until how = {0.0, 0.0, LORA_NORM_MAX, 60, 0};
     for (int i = kDim + 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -215,6 +222,49 @@ int main(int argc, char *argv[]) {
             leap3 = true;
         else if (a == "--cg")
             cg = true;
+        else if (a.rfind("--implicit=", 0) == 0 || a.rfind("--theta=", 0) == 0 || a.rfind("--rtol=", 0) == 0) {
+            const std::string v = a.substr(a.find('=') + 1);
+            char *rest = nullptr;
+            const double x = std::strtod(v.c_str(), &rest);
+            const bool number = !v.empty() && *rest == '\0' && std::isfinite(x);
+            if (a[2] == 'i') {
+                if (!number || !(x > 0.0)) {
+                    std::cerr << "Invalid argument: --implicit=TAU needs a finite number TAU > 0.\n";
+                    return 1;
+                }
+                implicit_tau = x;
+                implicit = true;
+            } else if (a[2] == 't') {
+                if (!number || !(x >= 0.0 && x <= 1.0)) {
+                    std::cerr << "Invalid argument: --theta=TH needs a number TH with 0 <= TH <= 1.\n";
+                    return 1;
+                }
+                implicit_theta = x;
+                implicit_option = true;
+            } else {
+                if (!number || !(x >= 0.0)) {
+                    std::cerr << "Invalid argument: --rtol=R needs a finite non-negative number.\n";
+                    return 1;
+                }
+                implicit_rtol = x;
+                implicit_option = true;
+            }
+        }
+        else if (a.rfind("--iters=", 0) == 0) {
+            try {
+                size_t used = 0;
+                const std::string v = a.substr(8);
+                implicit_iters = std::stoi(v, &used);
+                if (used != v.size()) implicit_iters = 0;
+            } catch (const std::exception &) {
+                implicit_iters = 0;
+            }
+            if (implicit_iters < 1) {
+                std::cerr << "Invalid argument: --iters=N needs a positive integer.\n";
+                return 1;
+            }
+            implicit_option = true;
+        }
         else if (a.rfind("--chebyshev=", 0) == 0) {
             const std::string v = a.substr(12);
             char *rest = nullptr;
@@ -272,6 +322,15 @@ int main(int argc, char *argv[]) {
             std::cerr << "Unknown option: " << a << "\n";
             return 1;
         }
+    }
+
+    if (implicit && (cg || chebyshev || leapfrog || until || gpus_given || grid[0] > 0 || check || bf16)) {
+        std::cerr << "--implicit runs a fixed number of implicit steps on one GPU in fp64: not with --cg, --chebyshev, --leapfrog, --until, --gpus, --grid, --check or --dtype=bf16\n";
+        return 1;
+    }
+    if (implicit_option && !implicit) {
+        std::cerr << "--theta, --iters and --rtol choose the scheme and the solves of an implicit run: only with --implicit=TAU\n";
+        return 1;
     }
 
     if (leapfrog && (gpus_given || grid[0] > 0 || check || until || source_kind || bf16)) {
@@ -355,7 +414,7 @@ int main(int argc, char *argv[]) {
             for (int i = 0; i < dims[0]; ++i)
                 for (int j = 0; j < (kDim > 1 ? dims[1] : 1); ++j)
                     for (int k = 0; k < (kDim > 2 ? dims[2] : 1); ++k) at(i, j, k) = source_value;
-        if (!chebyshev && !cg) lora_set_default_source(source.data());  // (a Chebyshev or CG run takes its source as an argument)
+        if (!chebyshev && !cg && !implicit) lora_set_default_source(source.data());  // (a Chebyshev, CG or implicit run takes its source as an argument)
     }
 
     if (check && (custom_bc || normalize)) {
@@ -372,7 +431,16 @@ int main(int argc, char *argv[]) {
     }
     lora_until_result reached = {};
     lora_cg_result solved = {};
-    if (cg) {
+    lora_theta_result stepped = {};
+    if (implicit) {
+        // the input is level 0, its halo the boundary values; time_size steps; the operator prints the reference's three lines
+        const int rc = lora_run_host_theta(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, implicit_theta,
+                                           implicit_tau, times, implicit_iters, implicit_rtol, dims, 0, nullptr, &stepped);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+    } else if (cg) {
         // the input is the start iterate, its halo the boundary values; time_size is the cap; the operator prints the reference's three lines
         how.max_times = times;
         const int rc = lora_run_host_cg(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, &how, &solved, dims, 0, nullptr);
@@ -465,6 +533,11 @@ int main(int argc, char *argv[]) {
             break;
     }
 
+    if (extra && implicit)
+        std::printf("Implicit: theta = %g, tau = %g, steps = %d%s, iterations = %lld (max %d of %d a step, rtol %g), unconverged steps = %d, "
+                    "steady residual = %g (max |S(u) + f - u|)\n",
+                    implicit_theta, implicit_tau, stepped.steps_done, stepped.breakdown ? ", broke down" : "", stepped.iterations_total,
+                    stepped.iterations_max, implicit_iters, implicit_rtol, stepped.unconverged_steps, stepped.steady.max_abs);
     if (extra && chebyshev) std::printf("Chebyshev: u(k+1) = w(k+1) (S(u(k)) + f) + (1 - w(k+1)) u(k-1), rho = %g, steps = %d\n", chebyshev_rho, reached.times_done);
     if (extra && cg)
         std::printf("Conjugate gradients on I - S: iterations = %d%s, rho_estimate = %.17g (lambda in [%g, %g])\n", reached.times_done,
@@ -480,7 +553,7 @@ int main(int argc, char *argv[]) {
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
     if (extra && source_kind)
-        std::printf(chebyshev || cg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
+        std::printf(implicit ? "Source: f = %g %s (du/dt = S(u) + f - u)\n" : chebyshev || cg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {
         lora_run_info ri;
         if (lora_last_run_info(&ri) == LORA_OK && ri.sweep_seconds > 0) {

@@ -251,12 +251,27 @@ inline bool has_cg(const Plan &p) { return p.dtype == LORA_F64 && has_fused_resi
 // The scalars of a run, resident on the device; behind them in the same allocation the run's history: `cap` alphas, `cap` betas.
 struct CgState {
     double rr, pq, alpha, beta, r_abs_max;  // r.r of the current residual, p.q of the last apply, rr / pq, rr' / rr, max |r|
-    long long iteration, breakdown;         // iterations applied; sticky: pq or rr not finite, pq <= 0, a non-finite product
+    long long iteration, breakdown;         // iterations applied; sticky: pq or rr not finite, pq <= 0, a non-finite product (bits: CgHalt)
 };
+// The bits of CgState::breakdown, the word every launch of a run tests before it touches memory.  The CG driver only ever sets
+// the first; the implicit stepper (cg.cpp) also sets the second when a step has met its stop rule and clears it behind the
+// next step's start, so that the step's remaining launches are the same uniform early exit.
+enum CgHalt { CG_HALT_BREAKDOWN = 1, CG_HALT_DONE = 2 };
 enum CgOp { CG_OP_UPDATE = 0, CG_OP_DIRECTION = 1, CG_OP_START = 2 };
 // what the fold does with the scalars: nothing; rr = the record lora_plan_dot's fold left, the rest reset; pq and alpha; rr, beta,
 // the history and the iteration count
-enum CgFold { CG_FOLD_PLAIN = 0, CG_FOLD_START = 1, CG_FOLD_APPLY = 2, CG_FOLD_UPDATE = 3 };
+// the stepper's: THETA_INIT resets both states at the head of a run (no records read); THETA_START takes rr = rr0 from the
+// start launch's records, clears `done` and the step's iteration count, thresh = fl(rtol2 rr0), done at once if rr0 == 0;
+// THETA_UPDATE is UPDATE followed by the stop rule (rr' <= thresh, or the step's max_iters-th iteration) and the step's
+// entry in the history
+enum CgFold { CG_FOLD_PLAIN = 0, CG_FOLD_START = 1, CG_FOLD_APPLY = 2, CG_FOLD_UPDATE = 3, CG_FOLD_THETA_INIT = 4, CG_FOLD_THETA_START = 5,
+              CG_FOLD_THETA_UPDATE = 6 };
+// The stepper's scalars beside the CgState, resident on the device; behind them in the same allocation the per-step history:
+// `cap` iteration counts (long long), then `cap` final rr (double).
+struct ThetaState {
+    double rr0, thresh, rtol2;  // r.r at the step's start; fl(rtol2 rr0); fl(rtol rtol) from the host
+    long long max_iters, steps_done, unconverged, cap;
+};
 // q = fl(p - sweep(p)) on the interior cells of the tiles of `rt` and the records of dot(p, q), one per workgroup (no fold)
 hipError_t launch_apply_dot(const Plan &p, const ResidualTiles &rt, const double *d_p, double *d_q, const CgState *st, ReduceRecord *partial,
                             hipStream_t s);
@@ -267,7 +282,16 @@ hipError_t launch_apply_dot(const Plan &p, const ResidualTiles &rt, const double
 // With a state, coef is its alpha (UPDATE) / beta (DIRECTION) and a set breakdown flag makes the launch a no-op.
 hipError_t launch_cg_pointwise(int op, const ReduceArgs &a, int kind, int groups, double *g0, double *g1, const double *g2, const double *g3,
                                double coef, const CgState *st, ReduceRecord *partial, hipStream_t s);
-hipError_t launch_cg_fold(ReduceRecord *partial, int groups, CgState *st, int phase, int cap, hipStream_t s);
+hipError_t launch_cg_fold(ReduceRecord *partial, int groups, CgState *st, int phase, int cap, hipStream_t s, ThetaState *ts = nullptr,
+                          double rtol2 = 0.0, int max_iters = 0);
+
+// ---- the implicit stepper's stencil launches (kernels_theta.hip; host side: cg.cpp).  Plans: has_cg().
+// q = fl(fl(sigma p) - fl(tau sweep(p))) on the interior cells of the tiles of `rt` and the records of dot(p, q) (no fold)
+hipError_t launch_apply_dot_shift(const Plan &p, const ResidualTiles &rt, const double *d_p, double *d_q, double sigma, double tau,
+                                  const CgState *st, ReduceRecord *partial, hipStream_t s);
+// r = p = fl(tau fl(fl(sweep(u) + f) - u)) (f == nullptr: no addition) on those cells and the records of dot(r, r) (no fold)
+hipError_t launch_theta_start(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double tau, double *d_r,
+                              double *d_p, const CgState *st, ReduceRecord *partial, hipStream_t s);
 
 // ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_step2.hip: two, 2D) -------
 // Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
@@ -440,4 +464,6 @@ struct lora_plan {
     lora::DeviceGrid cg[3];         // lora_plan_run_cg_until: r, p, q -- all three or none
     lora::DeviceGrid cg_state;      // ... its CgState and, behind it, the history of cg_cap alphas and cg_cap betas
     int cg_cap = 0;
+    lora::DeviceGrid theta_state;   // lora_plan_run_theta: its ThetaState and, behind it, the history of theta_cap steps
+    int theta_cap = 0;
 };

@@ -1,6 +1,6 @@
 // hostrun.cpp -- lora::HostRun (engine.h): the skeleton of the host-buffer operators that stand in for the reference's gpu_*()
 // functions -- lora_run_host_dtype (capi.cpp), lora_run_host_until (reduce.cpp), lora_run_host_leapfrog (leapfrog.cpp),
-// lora_run_host_chebyshev (chebyshev.cpp), lora_run_host_cg (cg.cpp).
+// lora_run_host_chebyshev (chebyshev.cpp), lora_run_host_cg and lora_run_host_theta (cg.cpp).
 //
 // Reference behaviour followed (file:line under the reference's src/):
 //   timing = steady_clock around the launch loop + one device sync

@@ -15,6 +15,8 @@
 //   cg_fold       one wave folds the workgroups' records in the order of kernels_reduce.hip's fold (lane l takes records l,
 //                 l + 64, ..., then the butterfly) into record kReduceMaxGroups; in the driver its last act is the one-lane
 //                 update of the device-resident scalars (CgState: alpha = rr / pq, beta = rr' / rr in IEEE fp64 division).
+//                 The implicit stepper (cg.cpp, kernels_theta.hip) adds three phases: the reset at the head of
+//                 a run, the step start (rr = rr0, thresh = fl(rtol2 rr0)) and the update with the step's stop rule.
 // Every arithmetic operation outside a tap sum is its own rounding (#pragma clang fp contract(off), as step_epilogue.h).  No
 // atomics; records and scalars are written with plain vector stores.
 //
@@ -457,8 +459,30 @@ __global__ __launch_bounds__(kThreads, 4) void cg_pointwise_kernel(double *__res
 }
 
 // ---- the fold and, behind it, the one-lane update of the scalars -----------------------------------------------------------
-__global__ __launch_bounds__(64) void cg_fold_kernel(ReduceRecord *__restrict__ partial, int groups, CgState *st, int phase, int cap) {
-    if (phase != CG_FOLD_START && broken(st)) return;
+// the stepper: a step is finished after `iters` iterations at r.r = rr -- its entry in the history, and the counts
+__device__ __forceinline__ void theta_step_done(ThetaState *ts, long long iters, double rr, bool unconverged) {
+    long long *hist_iters = reinterpret_cast<long long *>(ts + 1);
+    double *hist_rr = reinterpret_cast<double *>(hist_iters + ts->cap);
+    const long long n = ts->steps_done;
+    if (n < ts->cap) {
+        hist_iters[n] = iters;
+        hist_rr[n] = rr;
+    }
+    ts->steps_done = n + 1;
+    ts->unconverged += unconverged ? 1 : 0;
+}
+__global__ __launch_bounds__(64) void cg_fold_kernel(ReduceRecord *__restrict__ partial, int groups, CgState *st, int phase, int cap, ThetaState *ts,
+                                                     double rtol2, int max_iters) {
+    if (phase == CG_FOLD_THETA_INIT) {  // the head of a stepper's run: both states reset, no record read
+        if (threadIdx.x != 0) return;
+        const CgState s0 = {0.0, 0.0, 0.0, 0.0, 0.0, 0, 0};
+        *st = s0;
+        const ThetaState t0 = {0.0, 0.0, rtol2, max_iters, 0, 0, cap};
+        *ts = t0;
+        return;
+    }
+    // a start is not held back by `done`, which belongs to the step before it
+    if (phase == CG_FOLD_THETA_START ? (st->breakdown & CG_HALT_BREAKDOWN) != 0 : (phase != CG_FOLD_START && broken(st))) return;
     DotAcc acc;
     acc.init();
     if (phase == CG_FOLD_START) {  // the record lora_plan_dot's own fold left
@@ -478,6 +502,15 @@ __global__ __launch_bounds__(64) void cg_fold_kernel(ReduceRecord *__restrict__ 
     if (phase == CG_FOLD_START) {
         CgState s0 = {acc.dot, 0.0, 0.0, 0.0, acc.amax, 0, (acc.nf > 0 || !finite64(acc.dot)) ? 1 : 0};
         *st = s0;
+    } else if (phase == CG_FOLD_THETA_START) {
+#pragma clang fp contract(off)
+        const double rr0 = acc.dot;
+        const bool bad = acc.nf > 0 || !finite64(rr0);
+        CgState s0 = {rr0, 0.0, 0.0, 0.0, acc.amax, 0, bad ? CG_HALT_BREAKDOWN : (rr0 == 0.0 ? CG_HALT_DONE : 0)};
+        *st = s0;
+        ts->rr0 = rr0;
+        ts->thresh = ts->rtol2 * rr0;
+        if (!bad && rr0 == 0.0) theta_step_done(ts, 0, 0.0, false);  // nothing to do: the level is steady
     } else if (phase == CG_FOLD_APPLY) {
         const double pq = acc.dot, rr = st->rr;
         st->pq = pq;
@@ -485,10 +518,10 @@ __global__ __launch_bounds__(64) void cg_fold_kernel(ReduceRecord *__restrict__ 
             st->breakdown = 1;
         else
             st->alpha = rr / pq;
-    } else {  // CG_FOLD_UPDATE: the iteration is applied
+    } else {  // CG_FOLD_UPDATE, CG_FOLD_THETA_UPDATE: the iteration is applied
         const double rr_new = acc.dot, beta = rr_new / st->rr;
         const long long it = st->iteration;
-        if (it < cap) {
+        if (phase == CG_FOLD_UPDATE && it < cap) {
             hist_alpha[it] = st->alpha;
             hist_beta[it] = beta;
         }
@@ -496,7 +529,15 @@ __global__ __launch_bounds__(64) void cg_fold_kernel(ReduceRecord *__restrict__ 
         st->rr = rr_new;
         st->r_abs_max = acc.amax;
         st->iteration = it + 1;
-        if (acc.nf > 0 || !finite64(rr_new)) st->breakdown = 1;
+        if (acc.nf > 0 || !finite64(rr_new)) {
+            st->breakdown = 1;
+        } else if (phase == CG_FOLD_THETA_UPDATE) {
+            const bool met = rr_new <= ts->thresh;
+            if (met || it + 1 >= ts->max_iters) {
+                st->breakdown = CG_HALT_DONE;
+                theta_step_done(ts, it + 1, rr_new, !met);
+            }
+        }
     }
 }
 
@@ -543,8 +584,10 @@ hipError_t launch_cg_pointwise(int op, const ReduceArgs &a, int kind, int groups
     return hipGetLastError();
 }
 
-hipError_t launch_cg_fold(ReduceRecord *partial, int groups, CgState *st, int phase, int cap, hipStream_t s) {
-    hipLaunchKernelGGL(cg_fold_kernel, dim3(1), dim3(64), 0, s, partial, groups, st, phase, cap);
+hipError_t launch_cg_fold(ReduceRecord *partial, int groups, CgState *st, int phase, int cap, hipStream_t s, ThetaState *ts, double rtol2,
+                          int max_iters) {
+    if (phase >= CG_FOLD_THETA_INIT && (!st || !ts)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cg_fold_kernel, dim3(1), dim3(64), 0, s, partial, groups, st, phase, cap, ts, rtol2, max_iters);
     return hipGetLastError();
 }
 

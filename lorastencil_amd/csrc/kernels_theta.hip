@@ -1,0 +1,493 @@
+// kernels_theta.hip -- the two stencil launches of the implicit time stepper (host side: cg.cpp), siblings of
+// apply_dot in kernels_cg.hip.  Both RESTATE the tile walk of their family in kernels_residual.hip exactly as apply_dot does
+// (window, tile sizes, tap order, centre value re-read from the window; residual_tiles.h for the walk), so `acc` has the bits
+// lora_plan_step_region stores; template parameter MODE picks what happens with a finished tap sum:
+//
+//   TH_SHIFT      q = fl(fl(sigma c) - fl(tau acc)), c the centre value: the operator sigma I - tau S applied to p, stored at
+//                 the lane's own two cells, and the record of dot(p, q)                               (lora_plan_apply_dot_shift)
+//   TH_START      r = fl(tau fl(acc - c)), stored to BOTH o0 and o1 (the stepper's r and p), and the record of dot(r, r)
+//   TH_START_SRC  r = fl(tau fl(fl(acc + f) - c)): f is read at the stored cells alone, with the store's own addressing -- as
+//                 the SRC form of kernels_residual.hip reads it -- so no halo cell of f is ever loaded.  "No source" is its
+//                 own instantiation, not "add a zero".                                                  (lora_plan_theta_start)
+// Stores are 16 bytes at the lane's own two cells, 8 bytes for the odd tail point in 1D: interior cells only, so the halos of
+// the stored grids are neither read nor written.  Every operation behind the tap sum is its own fp64 rounding (#pragma clang
+// fp contract(off)).  No atomics; records are written with plain vector stores, one per workgroup, folded by cg_fold_kernel.
+//
+// The state.  In the stepper every launch gets the CgState: its `breakdown` word carries two bits, CG_HALT_BREAKDOWN (sticky
+// for the run) and CG_HALT_DONE (the step met its stop rule; cleared behind the next start's fold).  A TH_SHIFT launch that
+// finds either returns before it loads or stores anything -- the uniform early exit of kernels_cg.hip; a start launch ignores
+// `done`, which belongs to the step before it.  The public entries pass no state.
+//
+// kernels_cg.hip's apply_dot kernels are left as they are: these are separate instantiations in a separate translation unit.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "device_common.h"
+#include "reduce_device.h"
+#include "residual_tiles.h"
+#include "step_epilogue.h"
+
+namespace lora {
+
+namespace {
+
+constexpr int kThreads = 256;
+
+enum { TH_SHIFT = 0, TH_START = 1, TH_START_SRC = 2 };
+
+struct ThetaCoef {
+    double sigma, tau;
+};
+
+template <int MODE>
+__device__ __forceinline__ bool halted(const CgState *st) {
+    if (!st) return false;
+    return MODE == TH_SHIFT ? st->breakdown != 0 : (st->breakdown & CG_HALT_BREAKDOWN) != 0;
+}
+
+// One cell: a = the swept value, c = the centre value, f = the source's (TH_START_SRC alone).  Returns the stored value; x, y
+// are the factors of the cell's product in the record.
+template <int MODE>
+__device__ __forceinline__ double theta_cell(double a, double c, double f, const ThetaCoef k, double &x, double &y) {
+#pragma clang fp contract(off)
+    if constexpr (MODE == TH_SHIFT) {
+        const double t = k.sigma * c;
+        const double u = k.tau * a;
+        const double q = t - u;
+        x = c;
+        y = q;
+        return q;
+    } else {
+        double t = a;
+        if constexpr (MODE == TH_START_SRC) t = step_epilogue<EPI_SOURCE>(a, f, 0.0, 0.0, 0.0);
+        const double d = t - c;
+        const double r = k.tau * d;
+        x = r;
+        y = r;
+        return r;
+    }
+}
+
+// N cells a lane holds of one row, the first `nvalid` (>= 1) of them inside the region: v = what the caller stores at the valid
+// cells; their products go into `acc`.
+template <int MODE, int N>
+__device__ __forceinline__ void theta_cells(DotAcc &acc, const double (&a)[N], const double (&c)[N], const double (&f)[N], const ThetaCoef k,
+                                            int nvalid, double (&v)[N]) {
+    double x[N], y[N];
+    bool valid[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        valid[j] = j < nvalid;
+        double xj, yj;
+        v[j] = theta_cell<MODE>(a[j], c[j], f[j], k, xj, yj);
+        x[j] = valid[j] ? xj : 0.0;
+        y[j] = valid[j] ? yj : 0.0;
+    }
+    acc.cells<N>(x, y, valid);
+}
+
+// the workgroup's record into its own slot
+__device__ __forceinline__ void finish(DotAcc &acc, ReduceRecord *__restrict__ partial) {
+    wave_reduce(acc);
+    __shared__ ReduceRecord sh[kThreads / 64];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kThreads / 64; ++w) acc.merge_record(sh[w]);
+        ReduceRecord r;
+        acc.to(r);
+        partial[blockIdx.x] = r;
+    }
+}
+
+// ---- 1D (kernels_cg.hip: apply_dot1d_kernel) -------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void theta1d_kernel(const double *__restrict__ in, const double *__restrict__ f, double *__restrict__ o0,
+                                                           double *__restrict__ o1, const ThetaCoef k, const CgState *st, const ResidualTiles rt,
+                                                           const Taps9 W, ReduceRecord *__restrict__ partial) {
+    if (halted<MODE>(st)) return;
+    DotAcc acc;
+    acc.init();
+    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
+        int o[3], n[3];
+        residual_tile_box(rt, t, o, n);
+        const int i = o[2] + 2 * (int) threadIdx.x;  // even: the region begins on an even point, tiles are 512 points
+        const int left = o[2] + n[2] - i;
+        if (left <= 0) continue;
+        double win[10];
+        d2 fv = {0.0, 0.0};
+        if (left >= 2) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                const d2 v = *reinterpret_cast<const d2 *>(in + i + 2 * q);
+                win[2 * q] = v.x;
+                win[2 * q + 1] = v.y;
+            }
+            if constexpr (MODE == TH_START_SRC) fv = *reinterpret_cast<const d2 *>(f + i + 4);
+        } else {  // odd tail: one point, scalar loads stay inside the padded array
+#pragma unroll
+            for (int q = 0; q < 9; ++q) win[q] = in[i + q];
+            win[9] = 0.0;
+            if constexpr (MODE == TH_START_SRC) fv.x = f[i + 4];
+        }
+        double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            a0 = fma(W.w[q], win[q], a0);
+            a1 = fma(W.w[q], win[q + 1], a1);
+        }
+        const double a[2] = {a0, a1}, c[2] = {win[4], win[5]}, ff[2] = {fv.x, fv.y};
+        double v[2];
+        theta_cells<MODE, 2>(acc, a, c, ff, k, left >= 2 ? 2 : 1, v);
+        if (left >= 2) {
+            *reinterpret_cast<d2 *>(o0 + i + 4) = (d2){v[0], v[1]};
+            if constexpr (MODE != TH_SHIFT) *reinterpret_cast<d2 *>(o1 + i + 4) = (d2){v[0], v[1]};
+        } else {
+            o0[i + 4] = v[0];
+            if constexpr (MODE != TH_SHIFT) o1[i + 4] = v[0];
+        }
+    }
+    finish(acc, partial);
+}
+
+// ---- 2D (kernels_cg.hip: apply_dot2d_kernel; the piece of f as kernels_residual.hip: residual2d_kernel<SRC>) ---------------
+constexpr int kTileW = 128;
+constexpr int kLdsW = kTileW + 8;
+constexpr int kChunksPerRow = kLdsW / 2;
+
+template <int TAPSET, int MODE>
+__global__ __launch_bounds__(kThreads, 3) void theta2d_kernel(const double *__restrict__ in, const double *__restrict__ f, double *__restrict__ o0,
+                                                              double *__restrict__ o1, const ThetaCoef kc, const CgState *st,
+                                                              const ResidualTiles rt, const Taps49 W, ReduceRecord *__restrict__ partial) {
+    constexpr int RPT = 8;
+    constexpr int TH = 4 * RPT;
+    constexpr int LH = TH + 6;
+    constexpr int NCHUNK = LH * kChunksPerRow;
+    constexpr int NIT = (NCHUNK + 255) / 256;
+    constexpr bool SRC = MODE == TH_START_SRC;
+    constexpr int kAhead = 4;  // window rows between the load of a row's piece of f and its use (as residual2d_kernel)
+    __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
+    if (halted<MODE>(st)) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = tid >> 6;
+    const int m = rt.dims[1], n = rt.dims[2], ld = n + 8;
+    DotAcc dacc;
+    dacc.init();
+    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
+        int o[3], nn[3];
+        residual_tile_box(rt, t, o, nn);
+        const int i0 = o[1], j0 = o[2], row_end = o[1] + nn[1];
+        const int col = j0 + 2 * lane;
+        d2 fv[SRC ? RPT : 1] = {};
+        // ---- stage the input window: padded rows i0+1 .. i0+TH+6, padded columns j0 .. j0+135 (clamped into the array)
+        {
+            d2 stage[NIT];
+            const int max_row = m + 7;
+            const int max_col = n + 6;
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int k = tid + it * 256;
+                if (NCHUNK % 256 == 0 || k < NCHUNK) {
+                    const int r = k / kChunksPerRow;
+                    const int c = k - r * kChunksPerRow;
+                    const int gr = min(i0 + 1 + r, max_row);
+                    const int gc = min(j0 + 2 * c, max_col);
+                    stage[it] = *reinterpret_cast<const d2 *>(in + (size_t) gr * ld + gc);
+                }
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int k = tid + it * 256;
+                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(tile + 2 * k) = stage[it];
+            }
+        }
+        __syncthreads();
+
+        // ---- compute: lane owns tile columns 2*lane+4, 2*lane+5 (window 2*lane .. 2*lane+9)
+        double acc0[RPT], acc1[RPT];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            acc0[r] = 0.0;
+            acc1[r] = 0.0;
+        }
+        const double *strip = tile + (wv * RPT) * kLdsW + 2 * lane;
+        d2 cur[5], nxt[5];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) cur[q] = *reinterpret_cast<const d2 *>(strip + 2 * q);
+#pragma unroll
+        for (int j = 0; j < RPT + 6; ++j) {
+            if (j + 1 < RPT + 6) {
+#pragma unroll
+                for (int q = 0; q < 5; ++q) nxt[q] = *reinterpret_cast<const d2 *>(strip + (j + 1) * kLdsW + 2 * q);
+            }
+            if constexpr (SRC) {  // the piece of f of output row j - 6 + kAhead, which completes kAhead window rows from here
+                const int r = j - 6 + kAhead;
+                if (r >= 0 && r < RPT) {
+                    const int row = i0 + wv * RPT + r;
+                    if (col < n && row < row_end) fv[r] = *reinterpret_cast<const d2 *>(f + (size_t) (row + 4) * ld + (col + 4));
+                }
+            }
+            double win[10];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                win[2 * q] = cur[q].x;
+                win[2 * q + 1] = cur[q].y;
+            }
+            // input row j of the strip is tap row dy = j - r of output row r
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) {
+                const int dy = j - r;
+                if (dy >= 0 && dy < 7) {
+#pragma unroll
+                    for (int dx = 0; dx < 7; ++dx) {
+                        if (tap_on<TAPSET>(dy, dx)) {
+                            const double wt = W.w[dy * 7 + dx];
+                            acc0[r] = fma(wt, win[dx + 1], acc0[r]);
+                            acc1[r] = fma(wt, win[dx + 2], acc1[r]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) {
+                if (j - r >= 0 && j - r < 7) asm volatile("" : "+v"(acc0[r]), "+v"(acc1[r]));
+            }
+            // output row j-6 is complete: its centre values are window row r + 3, this lane's columns
+            if (j >= 6) {
+                const int r = j - 6;
+                const int row = i0 + wv * RPT + r;
+                if (col < n && row < row_end) {  // (n and col are even: both cells or none)
+                    const d2 c = *reinterpret_cast<const d2 *>(strip + (r + 3) * kLdsW + 4);
+                    const d2 fr = fv[SRC ? r : 0];
+                    const double a[2] = {acc0[r], acc1[r]}, b[2] = {c.x, c.y}, ff[2] = {fr.x, fr.y};
+                    double v[2];
+                    theta_cells<MODE, 2>(dacc, a, b, ff, kc, 2, v);
+                    const size_t cell = (size_t) (row + 4) * ld + (col + 4);
+                    *reinterpret_cast<d2 *>(o0 + cell) = (d2){v[0], v[1]};
+                    if constexpr (MODE != TH_SHIFT) *reinterpret_cast<d2 *>(o1 + cell) = (d2){v[0], v[1]};
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 5; ++q) cur[q] = nxt[q];
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();  // every wave is done with the window before the next tile's is staged
+    }
+    finish(dacc, partial);
+}
+
+// ---- 3D (kernels_cg.hip: apply_dot3d_kernel; the pieces of f at residual3d_kernel<SRC>'s addresses, loaded in the epilogue) ---
+template <int TAPSET>
+__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
+    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
+}
+
+template <int TAPSET, int MODE>
+__global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__restrict__ in, const double *__restrict__ f, double *__restrict__ o0,
+                                                              double *__restrict__ o1, const ThetaCoef kc, const CgState *st,
+                                                              const ResidualTiles rt, const Taps27 W, ReduceRecord *__restrict__ partial) {
+    constexpr int RY = 4;
+    constexpr int TY = 4 * RY;
+    constexpr int LH = TY + 2;
+    constexpr int NCHUNK = LH * kChunksPerRow;
+    constexpr int NIT = (NCHUNK + 255) / 256;
+    constexpr bool SRC = MODE == TH_START_SRC;
+    __shared__ __attribute__((aligned(16))) double tile[2][LH * kLdsW];
+    if (halted<MODE>(st)) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = tid >> 6;
+    const int h = rt.dims[0], m = rt.dims[1], n = rt.dims[2], ld = n + 8;
+    const long plane = (long) (m + 4) * ld;
+    DotAcc dacc;
+    dacc.init();
+    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
+        int o3[3], n3[3];
+        residual_tile_box(rt, t, o3, n3);
+        const int k0 = o3[0], zc = n3[0], i0 = o3[1], j0 = o3[2], row_end = o3[1] + n3[1];
+        const int nplanes = zc + 2;  // input planes: padded k0 .. k0+zc+1
+
+        long goff[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int k = tid + it * 256;
+            const int r = k / kChunksPerRow;
+            const int c = k - r * kChunksPerRow;
+            const int gr = min(i0 + 1 + r, m + 3);  // padded rows i0+1 .. i0+TY+2
+            const int gc = min(j0 + 2 * c, n + 6);
+            goff[it] = (long) gr * ld + gc;
+        }
+        d2 stage[NIT];
+        auto load_plane = [&](int p) {
+            const double *src = in + (long) min(k0 + p, h + 1) * plane;
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (NCHUNK % 256 == 0 || tid + it * 256 < NCHUNK) stage[it] = *reinterpret_cast<const d2 *>(src + goff[it]);
+            }
+        };
+        auto write_plane = [&](int buf) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int k = tid + it * 256;
+                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(&tile[buf][2 * k]) = stage[it];
+            }
+        };
+
+        double acc0[3][RY], acc1[3][RY];
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int r = 0; r < RY; ++r) {
+                acc0[s][r] = 0.0;
+                acc1[s][r] = 0.0;
+            }
+
+        const int col = j0 + 2 * lane;
+        const bool col_ok = col < n;
+        const int strip_off = (wv * RY) * kLdsW + 2 * lane + 2;  // window = tile cols 2*lane+2 .. 2*lane+7
+        const long cell0 = (long) (i0 + wv * RY + 2) * ld + (col + 4);  // this lane's first cell inside a plane
+
+        load_plane(0);
+        write_plane(0);
+        __syncthreads();
+
+        auto consume = [&](int p, auto phase_tag) {
+            constexpr int PHASE = decltype(phase_tag)::value;
+            const bool more = p + 1 < nplanes;
+            if (more) load_plane(p + 1);
+            const double *strip = &tile[p & 1][strip_off];
+#pragma unroll
+            for (int j = 0; j < RY + 2; ++j) {
+                double win[6];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const d2 v = *reinterpret_cast<const d2 *>(strip + j * kLdsW + 2 * q);
+                    win[2 * q] = v.x;
+                    win[2 * q + 1] = v.y;
+                }
+#pragma unroll
+                for (int dz = 0; dz < 3; ++dz) {
+                    const int s = (PHASE - dz + 3) % 3;
+#pragma unroll
+                    for (int r = 0; r < RY; ++r) {
+                        const int dy = j - r;
+                        if (dy >= 0 && dy < 3) {
+#pragma unroll
+                            for (int dx = 0; dx < 3; ++dx) {
+                                if (tap_on3<TAPSET>(dz, dy, dx)) {
+                                    const double wt = W.w[dz * 9 + dy * 3 + dx];
+                                    acc0[s][r] = fma(wt, win[dx + 1], acc0[s][r]);
+                                    acc1[s][r] = fma(wt, win[dx + 2], acc1[s][r]);
+                                }
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+#pragma unroll
+                for (int r = 0; r < RY; ++r) asm volatile("" : "+v"(acc0[s][r]), "+v"(acc1[s][r]));
+
+            // output plane o = p - 2 is complete; its centre plane o + 1 = p - 1 is the other buffer's.  The pieces of f are
+            // loaded here, behind the tap loop, so that they are not live through it: the stores' addresses already are.
+            {
+                constexpr int s = (PHASE - 2 + 3) % 3;
+                const int o = p - 2;
+                if (o >= 0 && o < zc && col_ok) {
+                    const double *centre = &tile[(p - 1) & 1][strip_off + kLdsW + 2];  // tile row wv*RY + r + 1, cols 2*lane+4, +5
+                    const long base = (long) (k0 + o + 1) * plane + cell0;
+                    d2 fv[SRC ? RY : 1] = {};
+                    if constexpr (SRC) {
+#pragma unroll
+                        for (int r = 0; r < RY; ++r) {
+                            if (i0 + wv * RY + r < row_end) fv[r] = *reinterpret_cast<const d2 *>(f + base + (long) r * ld);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < RY; ++r) {
+                        if (i0 + wv * RY + r < row_end) {
+                            const d2 c = *reinterpret_cast<const d2 *>(centre + r * kLdsW);
+                            const d2 fr = fv[SRC ? r : 0];
+                            const double a[2] = {acc0[s][r], acc1[s][r]}, b[2] = {c.x, c.y}, ff[2] = {fr.x, fr.y};
+                            double v[2];
+                            theta_cells<MODE, 2>(dacc, a, b, ff, kc, 2, v);
+                            *reinterpret_cast<d2 *>(o0 + base + (long) r * ld) = (d2){v[0], v[1]};
+                            if constexpr (MODE != TH_SHIFT) *reinterpret_cast<d2 *>(o1 + base + (long) r * ld) = (d2){v[0], v[1]};
+                        }
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < RY; ++r) {
+                    acc0[s][r] = 0.0;
+                    acc1[s][r] = 0.0;
+                }
+            }
+            // (as residual3d_kernel: the refill goes into the buffer of plane p - 1, which other waves' epilogues may still read)
+            if (p >= 2) __syncthreads();
+            if (more) write_plane((p + 1) & 1);
+            __syncthreads();
+        };
+
+        for (int p = 0; p < nplanes; p += 3) {
+            consume(p, std::integral_constant<int, 0>{});
+            if (p + 1 < nplanes) consume(p + 1, std::integral_constant<int, 1>{});
+            if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
+        }
+    }
+    finish(dacc, partial);
+}
+
+template <int MODE>
+void launch_mode(const Plan &p, const ResidualTiles &rt, const double *in, const double *f, double *o0, double *o1, const ThetaCoef k,
+                 const CgState *st, ReduceRecord *partial, hipStream_t s) {
+    const dim3 grid((unsigned) rt.groups), block(kThreads);
+    if (p.ndim == 1) {
+        Taps9 w;
+        for (int t = 0; t < 9; ++t) w.w[t] = p.w[t];
+        hipLaunchKernelGGL(theta1d_kernel<MODE>, grid, block, 0, s, in, f, o0, o1, k, st, rt, w, partial);
+    } else if (p.ndim == 2) {
+        Taps49 w;
+        for (int t = 0; t < 49; ++t) w.w[t] = p.w[t];
+        if (p.tapset == TAPS2D_DIAMOND)
+            hipLaunchKernelGGL((theta2d_kernel<TAPS2D_DIAMOND, MODE>), grid, block, 0, s, in, f, o0, o1, k, st, rt, w, partial);
+        else if (p.tapset == TAPS2D_STAR)
+            hipLaunchKernelGGL((theta2d_kernel<TAPS2D_STAR, MODE>), grid, block, 0, s, in, f, o0, o1, k, st, rt, w, partial);
+        else
+            hipLaunchKernelGGL((theta2d_kernel<TAPS2D_BOX, MODE>), grid, block, 0, s, in, f, o0, o1, k, st, rt, w, partial);
+    } else {
+        Taps27 w;
+        for (int t = 0; t < 27; ++t) w.w[t] = p.w[t];
+        if (p.tapset == TAPS3D_STAR)
+            hipLaunchKernelGGL((theta3d_kernel<TAPS3D_STAR, MODE>), grid, block, 0, s, in, f, o0, o1, k, st, rt, w, partial);
+        else
+            hipLaunchKernelGGL((theta3d_kernel<TAPS3D_BOX, MODE>), grid, block, 0, s, in, f, o0, o1, k, st, rt, w, partial);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_apply_dot_shift(const Plan &p, const ResidualTiles &rt, const double *d_p, double *d_q, double sigma, double tau,
+                                  const CgState *st, ReduceRecord *partial, hipStream_t s) {
+    if (!has_cg(p) || rt.groups < 1 || rt.groups > kReduceMaxGroups) return hipErrorInvalidValue;
+    launch_mode<TH_SHIFT>(p, rt, d_p, nullptr, d_q, nullptr, ThetaCoef{sigma, tau}, st, partial, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_theta_start(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double tau, double *d_r,
+                              double *d_p, const CgState *st, ReduceRecord *partial, hipStream_t s) {
+    if (!has_cg(p) || rt.groups < 1 || rt.groups > kReduceMaxGroups) return hipErrorInvalidValue;
+    if (d_f)
+        launch_mode<TH_START_SRC>(p, rt, d_u, d_f, d_r, d_p, ThetaCoef{1.0, tau}, st, partial, s);
+    else
+        launch_mode<TH_START>(p, rt, d_u, nullptr, d_r, d_p, ThetaCoef{1.0, tau}, st, partial, s);
+    return hipGetLastError();
+}
+
+}  // namespace lora

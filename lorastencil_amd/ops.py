@@ -250,6 +250,21 @@ class CgResult(NamedTuple):
     breakdown: bool
 
 
+class ThetaResult(NamedTuple):
+    """What ``run_theta`` returns (lora_theta_result): the steps finished, whether CG broke down, the steps that used all their
+    iterations, the iterations of the finished steps (their sum and their largest, and ``iterations``: one count per step), r.r
+    at the start of the last step and at the run's end, and the true residual S(u) + f - u of the last level."""
+    steps_done: int
+    breakdown: bool
+    unconverged_steps: int
+    iterations_total: int
+    iterations_max: int
+    last_rr0: float
+    last_rr: float
+    steady: GridDiff
+    iterations: tuple = ()
+
+
 NORMS = {"max": _lib.NORM_MAX, "rms": _lib.NORM_RMS}
 
 
@@ -263,6 +278,11 @@ def _until_result(r) -> UntilResult:
 
 def _cg_result(r) -> CgResult:
     return CgResult(_until_result(r.until), r.lambda_min, r.lambda_max, r.rho_estimate, bool(r.breakdown))
+
+
+def _theta_result(r, iterations=()) -> ThetaResult:
+    return ThetaResult(r.steps_done, bool(r.breakdown), r.unconverged_steps, r.iterations_total, r.iterations_max, r.last_rr0, r.last_rr,
+                       _tuple_of(GridDiff, r.steady), tuple(int(k) for k in iterations))
 
 
 def _until_arg(tol, rtol, norm, check_every, max_times):
@@ -473,6 +493,31 @@ def run_host_cg(shape, in_: np.ndarray, tol: float, source=None, rtol: float = 0
     check(_lib.lib().lora_run_host_cg(sid, _p(in_), None if src is None else _p(src), _p(out), pp, ctypes.byref(u), ctypes.byref(r),
                                       _dims_arg(dims), int(quiet), ctypes.byref(info)), f"lora_run_host_cg({SHAPE_NAMES.get(sid, sid)})")
     return out, _cg_result(r), info
+
+
+def run_host_theta(shape, in_: np.ndarray, tau: float, steps: int, source=None, theta: float = 1.0, max_iters: int = 50,
+                   rtol: float = 1e-8, params=None, quiet: bool = True):
+    """``steps`` implicit steps of du/dt = S(u) + f - u with step ``tau`` from the padded float64 host array ``in_`` (level 0,
+    its halo the boundary values), ``source`` a padded host array of f or None (lora_run_host_theta).  ``theta``: 1 backward
+    Euler, 0.5 Crank-Nicolson.  Returns (the last level as a padded array, ThetaResult without per-step counts, RunInfo)."""
+    sid = shape_id(shape)
+    in_ = np.ascontiguousarray(in_, dtype=np.float64)
+    h = halo(sid)
+    if in_.ndim != len(h):
+        raise ValueError("in_ must be a padded array of the shape's rank")
+    src = None
+    if source is not None:
+        src = np.ascontiguousarray(source, dtype=np.float64)
+        if src.shape != in_.shape:
+            raise ValueError("source must be a padded array of in_'s size")
+    dims = [in_.shape[i] - 2 * h[i] for i in range(in_.ndim)]
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    r, info = _lib.ThetaResult(), RunInfo()
+    check(_lib.lib().lora_run_host_theta(sid, _p(in_), None if src is None else _p(src), _p(out), pp, float(theta), float(tau), int(steps),
+                                         int(max_iters), float(rtol), _dims_arg(dims), int(quiet), ctypes.byref(info), ctypes.byref(r)),
+          f"lora_run_host_theta({SHAPE_NAMES.get(sid, sid)})")
+    return out, _theta_result(r), info
 
 
 def _operator(cname: str, nd: int):
@@ -778,6 +823,38 @@ class Plan:
         """p = r + beta p on the interior cells of [begin, end) (lora_plan_cg_direction); asynchronous."""
         check(_lib.lib().lora_plan_cg_direction(self._h, _ptr(d_p), _ptr(d_r), float(beta), int(begin), int(end), _stream(stream)),
               "lora_plan_cg_direction")
+
+    # -- implicit time stepping: theta-scheme steps of du/dt = S(u) + f - u, each a CG solve on sigma I - tau S
+    def apply_dot_shift(self, d_p, d_q, sigma: float, tau: float, begin: int = 0, end: int = 0, stream=None) -> GridDot:
+        """q = sigma p - tau S(p) on the interior cells of [begin, end) in one pass; returns the dot of p and q
+        (lora_plan_apply_dot_shift)."""
+        out = _lib.GridDot()
+        check(_lib.lib().lora_plan_apply_dot_shift(self._h, _ptr(d_p), _ptr(d_q), float(sigma), float(tau), int(begin), int(end),
+                                                   ctypes.byref(out), _stream(stream)), "lora_plan_apply_dot_shift")
+        return _tuple_of(GridDot, out)
+
+    def theta_start(self, d_u, d_f, tau: float, d_r, d_p, begin: int = 0, end: int = 0, stream=None) -> GridDot:
+        """r = p = tau (S(u) + f - u) on the interior cells of [begin, end) in one pass (``d_f`` may be None); returns the dot
+        of r with itself (lora_plan_theta_start)."""
+        out = _lib.GridDot()
+        check(_lib.lib().lora_plan_theta_start(self._h, _ptr(d_u), _optr(d_f), float(tau), _ptr(d_r), _ptr(d_p), int(begin), int(end),
+                                               ctypes.byref(out), _stream(stream)), "lora_plan_theta_start")
+        return _tuple_of(GridDot, out)
+
+    def prepare_theta(self, steps: int):
+        """Allocate now what ``run_theta(..., steps=steps)`` would allocate on first need (three grids, the states, the history)."""
+        check(_lib.lib().lora_plan_prepare_theta(self._h, int(steps)), "lora_plan_prepare_theta")
+        return self
+
+    def run_theta(self, d_u, d_f, tau: float, steps: int, theta: float = 1.0, max_iters: int = 50, rtol: float = 1e-8,
+                  stream=None) -> ThetaResult:
+        """``steps`` implicit steps of ``d_u`` in place with step ``tau`` (lora_plan_run_theta): theta = 1 backward Euler, 0.5
+        Crank-Nicolson; each step a CG solve to |r| <= rtol |r0| in at most ``max_iters`` iterations, the whole run enqueued
+        without a host wait.  ``d_f`` may be None.  Blocks once, at its end."""
+        r, its = _lib.ThetaResult(), (ctypes.c_int * max(int(steps), 1))()
+        check(_lib.lib().lora_plan_run_theta(self._h, _ptr(d_u), _optr(d_f), float(theta), float(tau), int(steps), int(max_iters),
+                                             float(rtol), its, ctypes.byref(r), _stream(stream)), "lora_plan_run_theta")
+        return _theta_result(r, its[:max(int(steps), 0)])
 
     def prepare_cg(self, max_times: int):
         """Allocate now what ``run_cg_until(..., max_times=max_times)`` would allocate on first need (three grids, the state)."""
