@@ -187,6 +187,19 @@ struct lora_theta_result;
 int lora_run_host_theta(int shape, const double *in, const double *source, double *out, const double *params, double theta, double tau,
                         int steps, int max_iters, double rtol, const int *dims, int quiet, lora_run_info *info,
                         struct lora_theta_result *result);
+/* Multigrid V-cycles for u = S(u) + f on host arrays (fp64, 2D and 3D; see lora_plan_run_mg_until in group B): uploads the
+ * padded host array `in` (the start iterate, its halo the boundary values) and `source` (a padded host array of f, or NULL: none)
+ * outside the timed region, runs lora_plan_prepare_mg and then, timed, lora_plan_run_mg_until, and copies the iterate (the
+ * whole padded array) to `out`.  `m`, `u` and `r` must not be NULL.  Prints the operator's three lines unless `quiet`, counting
+ * CYCLES; fills lora_run_info with steps_per_launch = 1 and hbm_gbs from the bytes of one cycle as lora_plan_mg_cycle_cost
+ * counts them -- per launch actually enqueued, 8 bytes for every interior cell of every grid it reads or writes (the padded
+ * grid for a zeroing), summed over the levels; the probes are not counted.  The timed region holds the cycles and their
+ * probes.  LORA_EUNSUPPORTED for what lora_plan_run_mg_until refuses and while the thread has a default source
+ * (lora_set_default_source): the source is an argument here. */
+struct lora_mg;
+struct lora_mg_result;
+int lora_run_host_mg(int shape, const double *in, const double *source, double *out, const double *params, const struct lora_mg *m,
+                     const struct lora_until *u, struct lora_mg_result *r, const int *dims, int quiet, lora_run_info *info);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -765,6 +778,105 @@ int lora_plan_run_theta(lora_plan *plan, void *d_u, const void *d_f, double thet
 /* Allocate now what lora_plan_run_theta(..., steps) would allocate on first need: the three grids, the two states and the
  * history.  LORA_EINVAL for steps < 0, LORA_EUNSUPPORTED for a plan whose option "cg" reads 0. */
 int lora_plan_prepare_theta(lora_plan *plan, int steps);
+
+/* ---- geometric multigrid for u = S(u) + f (NEW).  Every solver above needs iterations that grow with the
+ * grid's side; a V-cycle reduces the residual by a factor that does not.  fp64, 2D and 3D shapes.
+ *   Coarsening is boundary-aligned and non-nested: a coarse grid spans the same interval as the fine one, from halo centre to
+ * halo centre, with n_c interior cells per axis in place of n, so its spacing is H = h (n + 1) / (n_c + 1) and any extents will
+ * do.  Prolongation is linear interpolation with position-dependent weights, restriction its scaled transpose, and the coarse
+ * taps are the fine ones rescaled by (h / H)^2 per axis.
+ *   Interpolation weights.  A fine index i and a coarse index j of one axis (both 0-based interior indices) have
+ *     p(i, j) = max(0, 1 - |(i + 1)(n_c + 1) - (j + 1)(n + 1)| / (n + 1)),
+ *   the numerator an exact integer; a coarse index outside [0, n_c) counts as a zero value (the zero halo of a correction).
+ *   In more dimensions the weight is the product over the axes.
+ *   Which plans (read-only option "mg": 1 or 0): plans whose option "cg" reads 1, of a 2D or 3D shape, for whose extents
+ *   lora_mg_coarse_dims succeeds. */
+/* Host only: the extents of the next coarser grid.  Per axis n_c = floor(n / 2), the innermost then rounded down to even (the
+ * fast kernels need an even innermost extent): (70, 260) -> (35, 130), (9, 10) -> (4, 4), (250, 250) -> (125, 124),
+ * (35, 17, 130) -> (17, 8, 64).  LORA_EINVAL for a null pointer, an unknown shape or an extent < 1; LORA_EUNSUPPORTED for a 1D
+ * shape and when any n_c would be below 4. */
+int lora_mg_coarse_dims(int shape, const int *dims, int *cdims);
+/* Host only: the taps of the coarse operator from the fine taps `w` (lora_shape_ntaps doubles, as lora_plan_set_weights takes
+ * them) for the grids `dims` -> `cdims`.  Per axis rho_a = (n_c + 1) / (n + 1) and q_a = rho_a^2 = (h / H)^2.  A tap at offset
+ * d != 0 becomes wc = w prod_a q_a^(d_a^2 / |d|^2) -- exactly w q_a for a tap along one axis -- and the centre tap
+ * wc[centre] = (sum of w) - (sum of the other wc), so the tap sum and point symmetry are kept: I - S scales like a second-order
+ * operator, which is what point-symmetric taps (no first moment) are to leading order.  LORA_EINVAL for a null pointer, an
+ * unknown shape or an extent < 1; LORA_EUNSUPPORTED for a 1D shape. */
+int lora_mg_coarse_taps(int shape, const double *w, const int *dims, const int *cdims, double *wc);
+/* The two transfer kernels.  `plan` is the FINE level's plan; the coarse grid is a padded array of the layout
+ * lora_padded_count(shape, cdims) with cdims = lora_mg_coarse_dims(dims).  Both are ASYNCHRONOUS on `stream` like
+ * lora_plan_cg_direction and take a capturing stream.  The buffer contract of this group holds (pieces of at most 16 bytes,
+ * nothing outside the two padded arrays); the same call gives the same bits every time (no atomics, a fixed order); nothing is
+ * contracted into a fused multiply-add.  Each output cell is a sum of exact integer numerators times values, scaled once:
+ * within (terms + 4) 2^-53 sum |weight value| of the exact result, `terms` the non-zero weights of the cell.
+ *   Status, in this order: LORA_EINVAL for a null plan or buffer, a non-finite scale, or equal buffers; LORA_EUNSUPPORTED for a
+ *   misaligned buffer; LORA_EUNSUPPORTED for a plan whose option "mg" reads 0; LORA_ENODEVICE without a device. */
+/* Restriction, a gather: on every interior cell j of the coarse grid
+ *     d_coarse[j] = fl(scale (prod_a rho_a) sum_i prod_a p(i_a, j_a) d_fine[i]),
+ * at most 5 fine cells per axis in range.  Only interior cells of d_fine are read; the halo of d_coarse is not written. */
+int lora_plan_mg_restrict(lora_plan *plan, const void *d_fine, void *d_coarse, double scale, void *stream);
+/* Prolongation and correction: on every interior cell i of the fine grid
+ *     d_fine[i] = fl(d_fine[i] + sum_j prod_a p(i_a, j_a) d_coarse[j]),
+ * at most 2 coarse cells per axis.  Halo cells of d_coarse are selected away before any arithmetic, so a NaN there reaches
+ * nothing; the halo of d_fine is not written. */
+int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine, void *stream);
+/* V-cycles until the TRUE residual of u = S(u) + f is small.  d_x holds the start iterate, the caller's boundary values in its
+ * halo; d_f may be NULL.
+ *   Levels.  Level 0 is the plan's grid with its taps w_0; level l + 1 has lora_mg_coarse_dims(dims_l) and
+ *   w_(l+1) = lora_mg_coarse_taps(w_l).  The hierarchy is as deep as lora_mg_coarse_dims goes (16 levels at most), or
+ *   m->max_levels levels (>= 2) if that is fewer.  On every level l below the coarsest, L, the smoother is damped Jacobi folded
+ *   into a source sweep: with d_l = fl(1 - w_l[centre]) and c_l = fl(omega / d_l) an internal plan (lora_plan_create +
+ *   lora_plan_set_weights + lora_plan_set_boundary(LORA_BC_DIRICHLET) + lora_plan_set_source(g_l)) carries the taps
+ *   s_l[t] = fl(c_l w_l[t]) for t != centre, s_l[centre] = fl(fl(c_l w_l[centre]) + fl(1 - c_l)), and the source g_l, the
+ *   level's right-hand side times c_l; g_0 = fl(c_0 d_f) is formed once per run (d_f == NULL: level 0 has no source).  Level
+ *   L is a plain plan with the taps w_L.
+ *   One cycle at level l < L:  m->pre applications of the smoothing plan on x_l, with the values lora_plan_run of that plan
+ *   gives;  z = one more source sweep of it, rs = fl(z - x_l) on the interior (c_l times the residual);
+ *   lora_plan_mg_restrict(rs -> g_(l+1)) with scale = fl(c_(l+1) / c_l), or fl(1 / c_l) when l + 1 == L;  x_(l+1) = 0 over its
+ *   whole padded grid;  the cycle at level l + 1;  lora_plan_mg_prolong_add(x_(l+1) -> x_l);  m->post applications.
+ *   At level L:  r = g_L, p = r on the interior with a zero halo, rr = lora_plan_dot(r, r).dot, then m->coarse_iters (0: min(64,
+ *   cells of the coarsest interior)) conjugate-gradient iterations on x_L exactly as lora_plan_run_cg_until writes them, with the
+ *   same kernels, device-resident scalars and sticky halt flag, and no probe; a residual that vanishes exactly halts the
+ *   level's remaining launches harmlessly.
+ *   A cycle is enqueued with NO host wait inside it.  u->check_every and u->max_times count CYCLES, and any check_every >= 1 is
+ *   legal here; the other rules of `u`, the stop rule and the fields of r->until are lora_plan_run_until's (times_done counts
+ *   cycles).  After each round the run probes the true residual of the caller's problem, S(d_x) + f - d_x with the plan's own
+ *   taps, exactly as lora_plan_run_cg_until does: ONE lora_plan_residual_src under LORA_NORM_MAX, else a source sweep into the
+ *   level's spare grid and lora_plan_diff.  The call BLOCKS at its probes only.
+ *   BIT CONTRACT: d_x after k cycles is bit for bit what a caller gets by building the level plans from the formulas above and
+ *   looping the public entries as written -- the residual subtraction and the g_0 scale single IEEE operations, the CG scalars
+ *   divided in host fp64.
+ *   Memory the plan owns (allocated on first need or by lora_plan_prepare_mg, never read before the run wrote it on `stream`,
+ *   freed with the plan): two fine-size grids (g_0 and the spare), three grids per level in between, one grid and the CG set
+ *   (three grids, the scalars) on the coarsest level.  d_x's halo is never written, d_f never at all.
+ *   r->levels and r->level_dims (level 0 first) describe the hierarchy.
+ *   LORA_EINVAL for a null plan, d_x, m, u or r; a bad `u`; pre < 0, post < 0 or pre + post < 1; omega not in (0, 2) or not
+ *   finite; max_levels < 0 or == 1; coarse_iters < 0; d_f == d_x; a caller's buffer that is one of the plan's own.
+ *   LORA_EUNSUPPORTED for a misaligned buffer, a plan whose option "mg" reads 0, taps that are not point-symmetric, and any
+ *   level's d_l not positive and finite; then the reductions' codes.
+ *   Limits: coarsening stops when any axis would go below 4, so a very thin grid (16 x 16384) gets a coarsest level that
+ *   coarse_iters iterations do not solve, and convergence degrades; there is no semi-coarsening. */
+typedef struct lora_mg {
+    int pre, post;    /* smoothing applications before / after the coarse correction            */
+    double omega;     /* damping of the Jacobi smoother, 0 < omega < 2 (0.8 is a good default)   */
+    int max_levels;   /* 0 = as deep as lora_mg_coarse_dims goes, else >= 2                      */
+    int coarse_iters; /* CG iterations on the coarsest level; 0 = min(64, its interior cells)    */
+} lora_mg;
+typedef struct lora_mg_result {
+    lora_until_result until;
+    int levels;
+    int level_dims[16][3]; /* interior extents of level l, outermost first (2D: [l][2] = 0)    */
+} lora_mg_result;
+int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lora_mg *m, const lora_until *u, lora_mg_result *r,
+                           void *stream);
+/* Allocate now what lora_plan_run_mg_until(plan, ..., m, ...) would allocate on first need.  Status as that call's for `m` and
+ * the plan; LORA_ENODEVICE without a device. */
+int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m);
+/* What one cycle of the plan's last lora_plan_run_mg_until enqueued, counted while it was enqueued: the number of launches
+ * (kernels and memsets; a coarsest-level iteration is five) and the bytes they move when every launch reads and writes each
+ * of its grids' interiors once (a zeroing writes the padded grid).  LORA_EINVAL for a null pointer or a plan on which no cycle
+ * has run. */
+int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes);
 void lora_plan_destroy(lora_plan *plan);
 
 /* ========================================================================================

@@ -18,6 +18,7 @@ from .ops import (  # noqa: F401
     GridDot,
     GridStats,
     LoraError,
+    MgResult,
     Plan,
     ThetaResult,
     UntilResult,
@@ -36,12 +37,15 @@ from .ops import (  # noqa: F401
     gpu_star_2d3r,
     gpu_star_3d1r,
     interior,
+    mg_coarse_dims,
+    mg_coarse_taps,
     padded_shape,
     reference_input,
     run_host,
     run_host_cg,
     run_host_chebyshev,
     run_host_leapfrog,
+    run_host_mg,
     run_host_theta,
     run_host_until,
     separable_3x3x3,

@@ -101,6 +101,17 @@ class ThetaResult(ctypes.Structure):
                 ("last_rr", ctypes.c_double), ("steady", GridDiff)]
 
 
+class Mg(ctypes.Structure):
+    """lora_mg: the shape of a V-cycle."""
+    _fields_ = [("pre", ctypes.c_int), ("post", ctypes.c_int), ("omega", ctypes.c_double), ("max_levels", ctypes.c_int),
+                ("coarse_iters", ctypes.c_int)]
+
+
+class MgResult(ctypes.Structure):
+    """lora_mg_result: the until-result counted in cycles, and the hierarchy that ran."""
+    _fields_ = [("until", UntilResult), ("levels", ctypes.c_int), ("level_dims", (ctypes.c_int * 3) * 16)]
+
+
 NORM_MAX, NORM_RMS = 0, 1
 
 _comm_begin_t = ctypes.CFUNCTYPE(ctypes.c_int, _vp)
@@ -281,6 +292,15 @@ SIGNATURES = {
     "lora_plan_prepare_theta": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lora_run_host_theta": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_double, _ip, ctypes.c_int, ctypes.POINTER(RunInfo), ctypes.POINTER(ThetaResult)]),
+    "lora_mg_coarse_dims": (ctypes.c_int, [ctypes.c_int, _ip, _ip]),
+    "lora_mg_coarse_taps": (ctypes.c_int, [ctypes.c_int, _dp, _ip, _ip, _dp]),
+    "lora_plan_mg_restrict": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
+    "lora_plan_mg_prolong_add": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "lora_plan_run_mg_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(MgResult), _vp]),
+    "lora_plan_prepare_mg": (ctypes.c_int, [_vp, ctypes.POINTER(Mg)]),
+    "lora_plan_mg_cycle_cost": (ctypes.c_int, [_vp, _ip, _dp]),
+    "lora_run_host_mg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(MgResult),
+                                        _ip, ctypes.c_int, ctypes.POINTER(RunInfo)]),
     "lora_run_host_leapfrog": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int,
                                               ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),

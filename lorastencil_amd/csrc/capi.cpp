@@ -913,9 +913,20 @@ int lora_gpu_star_3d1r(const double *in, double *out, const double *params, int 
 }  // extern "C"
 
 namespace lora {
+// What run_launches enqueues for `times` sweeps of a plan under the Dirichlet boundary: the halo copy (and the scratch grid's),
+// the schedule's fused launches and the single sweeps behind them (the multigrid driver's tally, mg.cpp).
+int dirichlet_run_launches(lora_plan *plan, int times) {
+    if (times <= 0) return 0;
+    const Schedule sc = plan_schedule(plan, times, false);
+    int done = 0;
+    for (int d : sc.depths) done += d;
+    return 1 + (sc.scratch ? 1 : 0) + (int) sc.depths.size() + (times - done);
+}
+
 void release_run_state(lora_plan *plan) {
     drop_graph(plan);
     torus_drop(plan);
+    mg_release(plan);
     for (DeviceGrid *g : {&plan->scratch, &plan->records, &plan->leap[0], &plan->leap[1], &plan->cheb_probe, &plan->cg[0], &plan->cg[1],
                           &plan->cg[2], &plan->cg_state, &plan->theta_state})
         g->release();

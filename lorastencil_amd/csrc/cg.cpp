@@ -5,7 +5,8 @@
 //
 // Below them the implicit time stepper (kernels: kernels_theta.hip and the pointwise kernels of kernels_cg.hip):
 // theta-scheme steps of du/dt = S(u) + f - u, each a CG solve on sigma I - tau' S started from the level itself, a whole run
-// enqueued with no host wait.  Its entries go through the same CgLaunch as everything above.
+// enqueued with no host wait.  Its entries go through the same CgLaunch as everything above, and so does the coarsest level of
+// a multigrid cycle (cg_fixed_iterations; the driver: mg.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -139,6 +140,37 @@ double bisect(const std::vector<double> &d, const std::vector<double> &e2, doubl
 const double kNaN = std::numeric_limits<double>::quiet_NaN();
 
 }  // namespace
+
+int ensure_cg_grids(lora_plan *plan) { return ensure_cg(plan, 1); }
+
+// The coarsest level of a multigrid cycle (mg.cpp): the iterations of lora_plan_run_cg_until below, through the same CgLaunch,
+// from a residual the caller has put into the plan's own r -- no source sweep, no probe, no host wait.
+int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, hipStream_t s, long *launches) {
+    const Plan &p = plan->p;
+    if (int rc = ensure_cg(plan, 1)) return rc;
+    void *d_r = plan->cg[0].ptr, *d_p = plan->cg[1].ptr, *d_q = plan->cg[2].ptr;
+    CgState *st = static_cast<CgState *>(plan->cg_state.ptr);
+    const int cap = plan->cg_cap;
+    ReduceRecord *records = nullptr;
+    if (int rc = reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
+    // p = r on the interior, with a zero halo; rr = r.r
+    static const int pads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+    const int *pad = pads[p.ndim - 1];
+    if (int rc = hip_status(launch_halo(p, d_p, nullptr, HALO_ZERO, s), "halo launch")) return rc;
+    if (int rc = hip_status(launch_copy_interior(p.dtype, p.ndim, p.dims, d_p, pad, d_r, pad, s), "copy launch")) return rc;
+    if (int rc = hip_status(launch_reduce_dot(L.a, L.kind, L.groups, d_r, d_r, records, s), "reduction kernel launch")) return rc;
+    if (int rc = hip_status(launch_cg_fold(records, L.groups, st, CG_FOLD_START, cap, s), "fold launch")) return rc;
+    for (int i = 0; i < iters; ++i) {
+        if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
+        if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
+        if (int rc = L.direction(d_p, d_r, 0.0, st)) return rc;
+    }
+    if (launches) *launches += 5 + 5L * iters;  // (the dot is a reduction and its fold)
+    return LORA_OK;
+}
+
 }  // namespace lora
 
 using lora::CgLaunch;

@@ -32,6 +32,10 @@
 //                      on the device: --theta=TH (0 <= TH <= 1, default 1: backward Euler; 0.5: Crank-Nicolson), at most
 //                      --iters=N iterations a step (default 50) to |r| <= R |r0| with --rtol=R (default 1e-8); f from
 //                      --source= when given; one GPU, fp64
+//   --mg[=PRE,POST]    (lorastencil_2d, lorastencil_3d) solve u = S(u) + f by multigrid V(PRE, POST) cycles (lora_run_host_mg; default
+//                      2,2; damped Jacobi with omega = 0.8, CG on the coarsest level): needs --until=TOL, time_size is the cap in
+//                      CYCLES, --check-every=N may be any N >= 1 (default 1); f from --source= when given; one GPU, fp64.  The
+//                      taps must leave 1 - w[centre] > 0 on every level: the reference's integer tables need --normalize
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -158,6 +162,8 @@ int main(int argc, char *argv[]) {
     double chebyshev_rho = 0.0;
     bool leap3 = false;
     bool cg = false;
+    bool mg = false, check_every_given = false;
+    lora_mg cycle = {2, 2, 0.8, 0, 0};
     bool implicit = false, implicit_option = false;
     double implicit_tau = 0.0, implicit_theta = 1.0, implicit_rtol = 1e-8;
     int implicit_iters = 50;
@@ -222,6 +228,17 @@ int main(int argc, char *argv[]) {
             leap3 = true;
         else if (a == "--cg")
             cg = true;
+        else if ((a == "--mg" || a.rfind("--mg=", 0) == 0) && kDim >= 2) {
+            mg = true;
+            if (a.size() > 4) {
+                int used = 0;
+                if (std::sscanf(a.c_str() + 5, "%d,%d%n", &cycle.pre, &cycle.post, &used) != 2 || a.c_str()[5 + used] != '\0' || cycle.pre < 0 ||
+                    cycle.post < 0 || cycle.pre + cycle.post < 1) {
+                    std::cerr << "Invalid argument: --mg=PRE,POST needs two non-negative integers, not both zero.\n";
+                    return 1;
+                }
+            }
+        }
         else if (a.rfind("--implicit=", 0) == 0 || a.rfind("--theta=", 0) == 0 || a.rfind("--rtol=", 0) == 0) {
             const std::string v = a.substr(a.find('=') + 1);
             char *rest = nullptr;
@@ -284,10 +301,11 @@ int main(int argc, char *argv[]) {
             } catch (const std::exception &) {
                 how.check_every = 0;
             }
-            if (how.check_every < 2 || how.check_every % 2) {
+            if (how.check_every < 1) {
                 std::cerr << "Invalid argument: --check-every=N needs a positive even integer.\n";
                 return 1;
             }
+            check_every_given = true;
         }
         else if (a.rfind("--gpus=", 0) == 0) {
             gpus_given = true;
@@ -323,6 +341,20 @@ int main(int argc, char *argv[]) {
             return 1;
         }
     }
+
+    if (!mg && (how.check_every < 2 || how.check_every % 2)) {  // (a multigrid run counts cycles: any N >= 1)
+        std::cerr << "Invalid argument: --check-every=N needs a positive even integer.\n";
+        return 1;
+    }
+    if (mg && (cg || chebyshev || implicit || leapfrog || gpus_given || grid[0] > 0 || check || bf16)) {
+        std::cerr << "--mg runs on one GPU in fp64 against its own residual: not with --cg, --chebyshev, --implicit, --leapfrog, --gpus, --grid, --check or --dtype=bf16\n";
+        return 1;
+    }
+    if (mg && !until) {
+        std::cerr << "--mg solves until the residual is small: it needs --until=TOL (time_size is the cap, in cycles)\n";
+        return 1;
+    }
+    if (mg && !check_every_given) how.check_every = 1;
 
     if (implicit && (cg || chebyshev || leapfrog || until || gpus_given || grid[0] > 0 || check || bf16)) {
         std::cerr << "--implicit runs a fixed number of implicit steps on one GPU in fp64: not with --cg, --chebyshev, --leapfrog, --until, --gpus, --grid, --check or --dtype=bf16\n";
@@ -414,7 +446,7 @@ int main(int argc, char *argv[]) {
             for (int i = 0; i < dims[0]; ++i)
                 for (int j = 0; j < (kDim > 1 ? dims[1] : 1); ++j)
                     for (int k = 0; k < (kDim > 2 ? dims[2] : 1); ++k) at(i, j, k) = source_value;
-        if (!chebyshev && !cg && !implicit) lora_set_default_source(source.data());  // (a Chebyshev, CG or implicit run takes its source as an argument)
+        if (!chebyshev && !cg && !implicit && !mg) lora_set_default_source(source.data());  // (a Chebyshev, CG, multigrid or implicit run takes its source as an argument)
     }
 
     if (check && (custom_bc || normalize)) {
@@ -432,7 +464,17 @@ int main(int argc, char *argv[]) {
     lora_until_result reached = {};
     lora_cg_result solved = {};
     lora_theta_result stepped = {};
-    if (implicit) {
+    lora_mg_result cycled = {};
+    if (mg) {
+        // the input is the start iterate, its halo the boundary values; time_size is the cap in cycles; the operator prints the reference's three lines
+        how.max_times = times;
+        const int rc = lora_run_host_mg(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, &cycle, &how, &cycled, dims, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+        reached = cycled.until;
+    } else if (implicit) {
         // the input is level 0, its halo the boundary values; time_size steps; the operator prints the reference's three lines
         const int rc = lora_run_host_theta(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, implicit_theta,
                                            implicit_tau, times, implicit_iters, implicit_rtol, dims, 0, nullptr, &stepped);
@@ -542,7 +584,12 @@ int main(int argc, char *argv[]) {
     if (extra && cg)
         std::printf("Conjugate gradients on I - S: iterations = %d%s, rho_estimate = %.17g (lambda in [%g, %g])\n", reached.times_done,
                     solved.breakdown ? ", broke down" : "", solved.rho_estimate, solved.lambda_min, solved.lambda_max);
-    if (extra && until && (chebyshev || cg))
+    if (extra && mg) {
+        std::printf("Multigrid: V(%d,%d) cycles = %d, omega = %g, levels = %d, coarsest =", cycle.pre, cycle.post, reached.times_done, cycle.omega, cycled.levels);
+        for (int d = 0; d < kDim; ++d) std::printf("%s%d", d ? " x " : " ", cycled.levels > 0 ? cycled.level_dims[cycled.levels - 1][d] : 0);
+        std::printf("\n");
+    }
+    if (extra && until && (chebyshev || cg || mg))
         std::printf("Until: times_done = %d, %s, residual = %g (max |S(u) + f - u|, tol %g, checked every %d steps)\n", reached.times_done,
                     reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
                     how.check_every);
@@ -553,7 +600,7 @@ int main(int argc, char *argv[]) {
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
     if (extra && source_kind)
-        std::printf(implicit ? "Source: f = %g %s (du/dt = S(u) + f - u)\n" : chebyshev || cg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
+        std::printf(implicit ? "Source: f = %g %s (du/dt = S(u) + f - u)\n" : chebyshev || cg || mg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {
         lora_run_info ri;
         if (lora_last_run_info(&ri) == LORA_OK && ri.sweep_seconds > 0) {

@@ -293,6 +293,34 @@ hipError_t launch_apply_dot_shift(const Plan &p, const ResidualTiles &rt, const 
 hipError_t launch_theta_start(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double tau, double *d_r,
                               double *d_p, const CgState *st, ReduceRecord *partial, hipStream_t s);
 
+// ---- geometric multigrid (kernels_mg.hip; host side: mg.cpp) ------------------------------------------------------
+// The extents of the next coarser grid (lora_mg_coarse_dims): LORA_OK, LORA_EUNSUPPORTED for 1D or an extent below 4.
+int mg_coarse_dims(int ndim, const int *dims, int *cdims);
+// Whether the plan has the transfer kernels and the V-cycle driver: the CG plans of 2D / 3D shapes that can be coarsened once.
+// Read-only option "mg".
+inline bool has_mg(const Plan &p) {
+    int c[3];
+    return has_cg(p) && p.ndim >= 2 && mg_coarse_dims(p.ndim, p.dims, c) == LORA_OK;
+}
+// A fine grid of `dims` and the next coarser one of `cdims` (both with an even innermost extent), padded like a plan's arrays.
+//   restrict     coarse = fl(coef sum_i (prod_a num_a(i_a, j_a)) fine[i]) on every interior coarse cell, num_a the integer
+//                numerator (n + 1) - |(i + 1)(n_c + 1) - (j + 1)(n + 1)| where positive; coef = scale prod_a rho_a / (n_a + 1),
+//                rounded once on the host
+//   prolong_add  fine = fl(fine + fl(coef sum_j (prod_a num_a) coarse[j])) on every interior fine cell; coef = 1 / prod_a (n_a + 1)
+hipError_t launch_mg_restrict(int ndim, const int *dims, const int *cdims, const double *d_fine, double *d_coarse, double scale, hipStream_t s);
+hipError_t launch_mg_prolong_add(int ndim, const int *dims, const int *cdims, const double *d_coarse, double *d_fine, hipStream_t s);
+// the driver's two pointwise launches over the interior of a grid of `dims`: a = fl(a - b) and a = fl(c b)
+hipError_t launch_mg_sub(int ndim, const int *dims, double *d_a, const double *d_b, hipStream_t s);
+hipError_t launch_mg_scale(int ndim, const int *dims, double *d_a, const double *d_b, double c, hipStream_t s);
+// cg.cpp: the coarsest level of a cycle.  `iters` CG iterations on A = I - S of `plan` from d_x (whose halo is zero) with the
+// first residual in the plan's own r grid (plan->cg[0], written by the caller): p = r with a zero halo, rr = r.r, then the
+// iterations of lora_plan_run_cg_until through the same launches, no probe and no host wait.  *launches += what it enqueued.
+int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, hipStream_t s, long *launches);
+int ensure_cg_grids(lora_plan *plan);  // cg.cpp: the plan's three CG grids and its state (lora_plan_prepare_cg's, unchecked)
+int dirichlet_run_launches(lora_plan *plan, int times);  // capi.cpp: the launches of lora_plan_run(times) under the Dirichlet boundary, no graph
+struct MgHierarchy;                    // mg.cpp: the levels a plan owns for lora_plan_run_mg_until
+void mg_release(lora_plan *plan);      // mg.cpp: frees them (release_run_state)
+
 // ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_step2.hip: two, 2D) -------
 // Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
 hipError_t launch_source(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
@@ -466,4 +494,5 @@ struct lora_plan {
     int cg_cap = 0;
     lora::DeviceGrid theta_state;   // lora_plan_run_theta: its ThetaState and, behind it, the history of theta_cap steps
     int theta_cap = 0;
+    lora::MgHierarchy *mg = nullptr;  // lora_plan_run_mg_until: the level plans and their grids (mg.cpp; freed by mg_release)
 };

@@ -1,0 +1,498 @@
+// mg.cpp -- geometric multigrid for u = S(u) + f (kernels: kernels_mg.hip, the smoother: the source sweeps, the
+// coarsest level: the CG launches of cg.cpp).  The host-only geometry (coarse extents, coarse taps), the public entries of the
+// two transfer kernels, the level hierarchy a plan owns (lora_plan::mg), the V-cycle driver with the true-residual probe of the
+// CG driver, and the host-buffer operator (its skeleton: hostrun.cpp).
+//
+// Coarsening is boundary-aligned and non-nested (kernels_mg.hip has the geometry): level l + 1 has floor(n / 2) cells per axis,
+// the innermost rounded down to even, and the taps of level l rescaled by (h / H)^2 per axis.  On every level but the coarsest
+// the smoother is damped Jacobi folded into the taps of an internal plan with the level's right-hand side as its source, so a
+// smoothing application is one source sweep and the level's residual one more sweep and a subtraction.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "engine.h"
+
+namespace lora {
+
+int mg_coarse_dims(int ndim, const int *dims, int *cdims) {
+    if (ndim < 2) return LORA_EUNSUPPORTED;
+    for (int d = 0; d < ndim; ++d) {
+        int nc = dims[d] / 2;
+        if (d == ndim - 1) nc &= ~1;  // the fast kernels need an even innermost extent
+        if (nc < 4) return LORA_EUNSUPPORTED;
+        cdims[d] = nc;
+    }
+    return LORA_OK;
+}
+
+namespace {
+
+constexpr int kMaxLevels = 16;  // lora_mg_result::level_dims
+
+int centre_tap(int ndim) { return ndim == 2 ? 24 : 13; }
+
+// the offset of tap t along the axes of `dims` (outermost first): 7 x 7 taps of radius 3, 3 x 3 x 3 of radius 1, row-major
+void tap_offset(int ndim, int t, int *d) {
+    if (ndim == 2) {
+        d[0] = t / 7 - 3;
+        d[1] = t % 7 - 3;
+    } else {
+        d[0] = t / 9 - 1;
+        d[1] = t / 3 % 3 - 1;
+        d[2] = t % 3 - 1;
+    }
+}
+
+void coarse_taps(int ndim, const double *w, const int *dims, const int *cdims, double *wc) {
+    const int ntaps = ndim == 2 ? 49 : 27, c = centre_tap(ndim);
+    double q[3];
+    for (int a = 0; a < ndim; ++a) {
+        const double rho = (double) (cdims[a] + 1) / (double) (dims[a] + 1);
+        q[a] = rho * rho;
+    }
+    double sum = 0.0, others = 0.0;
+    for (int t = 0; t < ntaps; ++t) sum += w[t];
+    for (int t = 0; t < ntaps; ++t) {
+        if (t == c) continue;
+        int d[3];
+        tap_offset(ndim, t, d);
+        double len2 = 0.0;
+        for (int a = 0; a < ndim; ++a) len2 += (double) (d[a] * d[a]);
+        double f = 1.0;
+        for (int a = 0; a < ndim; ++a)
+            if (d[a] != 0) f *= (double) (d[a] * d[a]) == len2 ? q[a] : std::pow(q[a], (double) (d[a] * d[a]) / len2);
+        wc[t] = w[t] * f;
+        others += wc[t];
+    }
+    wc[c] = sum - others;
+}
+
+bool taps_symmetric(const double *w, int ntaps) {
+    for (int t = 0; t < ntaps; ++t)
+        if (w[t] != w[ntaps - 1 - t]) return false;
+    return true;
+}
+
+// any check_every >= 1 counts cycles; the other rules are lora_plan_run_until's
+bool bad_mg_until(const lora_until *u) {
+    if (u->check_every < 1 || u->max_times < 0 || (u->norm != LORA_NORM_MAX && u->norm != LORA_NORM_RMS)) return true;
+    return !(u->tol >= 0.0) || !(u->rtol >= 0.0);
+}
+
+bool bad_mg(const lora_mg *m) {
+    if (m->pre < 0 || m->post < 0 || (long) m->pre + m->post < 1) return true;
+    if (!(m->omega > 0.0 && m->omega < 2.0)) return true;  // (a NaN fails both)
+    return m->max_levels < 0 || m->max_levels == 1 || m->coarse_iters < 0;
+}
+
+int no_mg_kernels() {
+    return unsupported("this plan has no multigrid kernels: they take fp64 plans with the conjugate-gradient kernels (option \"cg\"), of a 2D or "
+                       "3D shape, whose extents halve to at least 4 cells per axis");
+}
+
+// What a level is on the host: extents, taps, the smoother's factor and taps.
+struct LevelDesc {
+    int dims[3] = {0, 0, 0};
+    double w[49] = {0}, s[49] = {0};
+    double d = 0.0, c = 0.0;
+};
+
+// The levels of a plan for `m`: LORA_OK, or LORA_EUNSUPPORTED for a level whose diagonal 1 - w[centre] is not positive and finite.
+int describe_levels(const Plan &p, const lora_mg *m, std::vector<LevelDesc> &out) {
+    const int cap = m->max_levels ? (m->max_levels < kMaxLevels ? m->max_levels : kMaxLevels) : kMaxLevels;
+    const int c = centre_tap(p.ndim);
+    out.clear();
+    LevelDesc lv;
+    for (int a = 0; a < p.ndim; ++a) lv.dims[a] = p.dims[a];
+    std::memcpy(lv.w, p.w, sizeof(double) * p.ntaps);
+    for (;;) {
+        lv.d = 1.0 - lv.w[c];
+        if (!(lv.d > 0.0) || !std::isfinite(lv.d))
+            return unsupported("a multigrid level's diagonal 1 - w[centre] is not positive and finite: damped Jacobi cannot smooth it");
+        lv.c = m->omega / lv.d;
+        for (int t = 0; t < p.ntaps; ++t) lv.s[t] = lv.c * lv.w[t];
+        {
+            const double keep = 1.0 - lv.c;
+            lv.s[c] = lv.s[c] + keep;
+        }
+        out.push_back(lv);
+        LevelDesc next;
+        if ((int) out.size() >= cap || mg_coarse_dims(p.ndim, lv.dims, next.dims) != LORA_OK) break;
+        coarse_taps(p.ndim, lv.w, lv.dims, next.dims, next.w);
+        lv = next;
+    }
+    return LORA_OK;
+}
+
+struct Level {
+    LevelDesc desc;
+    lora_plan *smooth = nullptr;  // levels below the coarsest: Dirichlet, taps s, source g
+    lora_plan *plain = nullptr;   // the coarsest level: taps w; its CG set holds r (= g), p, q
+    DeviceGrid x, spare, g;       // level 0: x is the caller's; the coarsest: x alone
+    size_t bytes = 0;             // of a padded grid
+    double cells = 0.0;           // of the interior
+    double *cur = nullptr, *other = nullptr;  // where the level's iterate is during a cycle, and the level's free grid
+};
+
+}  // namespace
+
+struct MgHierarchy {
+    std::vector<Level> levels;
+    double omega = 0.0;
+    int max_levels = 0, device = -1;
+    unsigned epoch = 0;
+    long launches = 0;  // of the last cycle enqueued ...
+    double bytes = 0.0; // ... and the bytes its launches move
+    ~MgHierarchy() {
+        for (Level &lv : levels) {
+            lora_plan_destroy(lv.smooth);
+            lora_plan_destroy(lv.plain);
+            lv.x.release();
+            lv.spare.release();
+            lv.g.release();
+        }
+    }
+};
+
+void mg_release(lora_plan *plan) {
+    delete plan->mg;
+    plan->mg = nullptr;
+}
+
+namespace {
+
+// an internal plan of the hierarchy: the thread's defaults (boundary, normalised taps) must not reach it
+int make_plan(lora_plan **out, int shape, const int *dims, const double *taps, int ntaps, int boundary) {
+    const int old_bc = lora_set_default_boundary(LORA_BC_REFERENCE), old_norm = lora_set_default_normalize(0);
+    int rc = lora_plan_create(out, shape, LORA_F64, dims, nullptr);
+    lora_set_default_boundary(old_bc);
+    lora_set_default_normalize(old_norm);
+    if (rc == LORA_OK) rc = lora_plan_set_weights(*out, taps, ntaps);
+    if (rc == LORA_OK) rc = lora_plan_set_boundary(*out, boundary);
+    // launched directly and through two grids alone: no graph, no scratch grid (neither moves a bit)
+    if (rc == LORA_OK) rc = lora_plan_set_option(*out, "graph", 0);
+    if (rc == LORA_OK) rc = lora_plan_set_option(*out, "scratch", 0);
+    return rc;
+}
+
+// The plan's hierarchy for `m` on the current device, built or rebuilt when the taps, the damping, the depth or the device changed.
+int ensure_hierarchy(lora_plan *plan, const lora_mg *m, bool with_source) {
+    const Plan &p = plan->p;
+    int device = -1;
+    if (int rc = hip_status(hipGetDevice(&device), "hipGetDevice")) return rc;
+    MgHierarchy *h = plan->mg;
+    if (!(h && h->omega == m->omega && h->max_levels == m->max_levels && h->epoch == p.epoch && h->device == device)) {
+        mg_release(plan);
+        std::vector<LevelDesc> descs;
+        if (int rc = describe_levels(p, m, descs)) return rc;
+        h = new (std::nothrow) MgHierarchy();
+        if (!h) return LORA_ENOMEM;
+        plan->mg = h;
+        h->omega = m->omega;
+        h->max_levels = m->max_levels;
+        h->epoch = p.epoch;
+        h->device = device;
+        h->levels.resize(descs.size());
+        const int L = (int) descs.size() - 1;
+        for (int l = 0; l <= L; ++l) {
+            Level &lv = h->levels[l];
+            lv.desc = descs[l];
+            lv.bytes = lora_padded_count(p.shape, lv.desc.dims) * sizeof(double);
+            lv.cells = 1.0;
+            for (int a = 0; a < p.ndim; ++a) lv.cells *= lv.desc.dims[a];
+            const int rc = l < L ? make_plan(&lv.smooth, p.shape, lv.desc.dims, lv.desc.s, p.ntaps, LORA_BC_DIRICHLET)
+                                 : make_plan(&lv.plain, p.shape, lv.desc.dims, lv.desc.w, p.ntaps, LORA_BC_REFERENCE);
+            if (rc != LORA_OK) {
+                mg_release(plan);
+                return rc;
+            }
+        }
+    }
+    const int L = (int) h->levels.size() - 1;
+    for (int l = 0; l <= L; ++l) {
+        Level &lv = h->levels[l];
+        bool ok = true;
+        if (l > 0) ok = ok && lv.x.ensure(lv.bytes);
+        if (l < L) ok = ok && lv.spare.ensure(lv.bytes);
+        if (l < L && (l > 0 || with_source)) ok = ok && lv.g.ensure(lv.bytes);
+        if (!ok) return LORA_ENOMEM;
+        if (l == L) {
+            if (int rc = ensure_cg_grids(lv.plain)) return rc;
+            ReduceRecord *records = nullptr;
+            if (int rc = reduction_records(lv.plain, &records)) return rc;
+        } else if (l > 0) {
+            if (int rc = lora_plan_set_source(lv.smooth, lv.g.ptr)) return rc;
+        }
+    }
+    return LORA_OK;
+}
+
+// what a cycle enqueues (lora_plan_mg_cycle_cost)
+struct Tally {
+    long launches = 0;
+    double bytes = 0.0;
+    void add(int n, double cells, double grids) {  // n launches that move `grids` grids of `cells` cells between them
+        launches += n;
+        bytes += 8.0 * cells * grids;
+    }
+};
+
+// `times` applications of the level's smoothing plan from lv.cur, with the values lora_plan_run of that plan gives; the iterate
+// ends in lv.cur.  With a source: the launch layer directly, two applications per launch where the plan has them (2D), so that
+// an even count never runs as single sweeps and nothing re-copies a halo both grids already share.  Without one (level 0 of a
+// run without f) the plan's own fused families apply, whose sums may run in another order than single sweeps: lora_plan_run.
+int smooth(Level &lv, int times, hipStream_t s, Tally &tally) {
+    if (times <= 0) return LORA_OK;
+    const Plan &p = lv.smooth->p;
+    if (!p.source) {
+        if (int rc = lora_plan_run(lv.smooth, lv.cur, lv.other, times, s)) return rc;
+        const int n = dirichlet_run_launches(lv.smooth, times);  // a halo copy, then launches that read one grid and write one
+        tally.add(n, lv.cells, 2.0 * (n - 1));
+        if (times % 2) std::swap(lv.cur, lv.other);
+        return LORA_OK;
+    }
+    for (int left = times; left > 0;) {
+        const int k = (p.steps_per_launch == 2 && left >= 2) ? 2 : 1;
+        if (int rc = launch_apps(p, {k, 0, p.dims[0]}, lv.cur, lv.other, s)) return rc;
+        tally.add(1, lv.cells, 3.0);
+        std::swap(lv.cur, lv.other);
+        left -= k;
+    }
+    return LORA_OK;
+}
+
+struct Run {
+    lora_plan *plan;
+    MgHierarchy *h;
+    const lora_mg *m;
+    hipStream_t s;
+    int ndim, L, coarse_iters;
+};
+
+// one V-cycle from level l down and up again; the level's iterate is in levels[l].cur before and after
+int cycle(const Run &r, int l, Tally &tally) {
+    Level &lv = r.h->levels[l];
+    if (l == r.L) {
+        if (int rc = cg_fixed_iterations(lv.plain, lv.cur, r.coarse_iters, r.s, &tally.launches)) return rc;
+        tally.bytes += 8.0 * lv.cells * (3.0 + 11.0 * r.coarse_iters);  // the copy and the dot; eleven grids an iteration (lora_run_host_cg)
+        return LORA_OK;
+    }
+    Level &co = r.h->levels[l + 1];
+    const Plan &sp = lv.smooth->p;
+    if (int rc = smooth(lv, r.m->pre, r.s, tally)) return rc;
+    // rs = fl(S_s(x) + g - x) = c_l times the level's residual, in the level's free grid
+    if (int rc = launch_apps(sp, {1, 0, sp.dims[0]}, lv.cur, lv.other, r.s)) return rc;
+    if (int rc = hip_status(launch_mg_sub(r.ndim, lv.desc.dims, lv.other, lv.cur, r.s), "residual subtraction launch")) return rc;
+    tally.add(2, lv.cells, (sp.source ? 3.0 : 2.0) + 3.0);
+    // the coarse right-hand side: scaled for the coarse smoother, unscaled for the coarsest level's CG
+    const bool last = l + 1 == r.L;
+    const double scale = last ? 1.0 / lv.desc.c : co.desc.c / lv.desc.c;
+    double *g = static_cast<double *>(last ? co.plain->cg[0].ptr : co.g.ptr);
+    if (int rc = hip_status(launch_mg_restrict(r.ndim, lv.desc.dims, co.desc.dims, lv.other, g, scale, r.s), "restriction launch")) return rc;
+    tally.add(1, lv.cells + co.cells, 1.0);
+    co.cur = static_cast<double *>(co.x.ptr);
+    co.other = static_cast<double *>(co.spare.ptr);
+    if (int rc = hip_status(hipMemsetAsync(co.cur, 0, co.bytes, r.s), "coarse start")) return rc;
+    tally.add(1, (double) co.bytes / 8.0, 1.0);
+    if (int rc = cycle(r, l + 1, tally)) return rc;
+    if (int rc = hip_status(launch_mg_prolong_add(r.ndim, lv.desc.dims, co.desc.dims, co.cur, lv.cur, r.s), "prolongation launch")) return rc;
+    tally.add(1, 2.0 * lv.cells + co.cells, 1.0);
+    return smooth(lv, r.m->post, r.s, tally);
+}
+
+void fill_levels(const std::vector<LevelDesc> &descs, lora_mg_result *r) {
+    r->levels = (int) descs.size();
+    for (int l = 0; l < kMaxLevels; ++l)
+        for (int a = 0; a < 3; ++a) r->level_dims[l][a] = l < (int) descs.size() ? descs[l].dims[a] : 0;
+}
+
+// what both the run and the prepare call refuse before a device is asked for
+int admit_mg(const lora_plan *plan, const lora_mg *m) {
+    const Plan &p = plan->p;
+    if (!has_mg(p)) return no_mg_kernels();
+    if (!taps_symmetric(p.w, p.ntaps))
+        return unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
+    std::vector<LevelDesc> descs;
+    return describe_levels(p, m, descs);
+}
+
+}  // namespace
+}  // namespace lora
+
+using lora::Plan;
+
+extern "C" {
+
+int lora_mg_coarse_dims(int shape, const int *dims, int *cdims) {
+    const int nd = lora::shape_ndim(shape);
+    if (nd == 0 || !dims || !cdims) return LORA_EINVAL;
+    for (int d = 0; d < nd; ++d)
+        if (dims[d] < 1) return LORA_EINVAL;
+    return lora::mg_coarse_dims(nd, dims, cdims);
+}
+
+int lora_mg_coarse_taps(int shape, const double *w, const int *dims, const int *cdims, double *wc) {
+    const int nd = lora::shape_ndim(shape);
+    if (nd == 0 || !w || !dims || !cdims || !wc) return LORA_EINVAL;
+    for (int d = 0; d < nd; ++d)
+        if (dims[d] < 1 || cdims[d] < 1) return LORA_EINVAL;
+    if (nd < 2) return LORA_EUNSUPPORTED;
+    lora::coarse_taps(nd, w, dims, cdims, wc);
+    return LORA_OK;
+}
+
+int lora_plan_mg_restrict(lora_plan *plan, const void *d_fine, void *d_coarse, double scale, void *stream) {
+    if (!plan || !d_fine || !d_coarse || !std::isfinite(scale) || d_fine == d_coarse) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_fine, d_coarse)) return rc;
+    const Plan &p = plan->p;
+    if (!lora::has_mg(p)) return lora::no_mg_kernels();
+    if (lora_device_count() <= 0) return lora::no_device();
+    int cdims[3] = {0, 0, 0};
+    lora::mg_coarse_dims(p.ndim, p.dims, cdims);
+    return lora::hip_status(lora::launch_mg_restrict(p.ndim, p.dims, cdims, static_cast<const double *>(d_fine), static_cast<double *>(d_coarse),
+                                                     scale, static_cast<hipStream_t>(stream)),
+                            "restriction launch");
+}
+
+int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine, void *stream) {
+    if (!plan || !d_coarse || !d_fine || d_fine == d_coarse) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_coarse, d_fine)) return rc;
+    const Plan &p = plan->p;
+    if (!lora::has_mg(p)) return lora::no_mg_kernels();
+    if (lora_device_count() <= 0) return lora::no_device();
+    int cdims[3] = {0, 0, 0};
+    lora::mg_coarse_dims(p.ndim, p.dims, cdims);
+    return lora::hip_status(lora::launch_mg_prolong_add(p.ndim, p.dims, cdims, static_cast<const double *>(d_coarse), static_cast<double *>(d_fine),
+                                                        static_cast<hipStream_t>(stream)),
+                            "prolongation launch");
+}
+
+int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m) {
+    if (!plan || !m || lora::bad_mg(m)) return LORA_EINVAL;
+    if (int rc = lora::admit_mg(plan, m)) return rc;
+    if (lora_device_count() <= 0) return lora::no_device();
+    lora::ReduceRecord *records = nullptr;  // (the probe folds into the plan's records: they are part of what a run needs)
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    return lora::ensure_hierarchy(plan, m, true);
+}
+
+int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes) {
+    if (!plan || !launches || !bytes || !plan->mg || plan->mg->launches == 0) return LORA_EINVAL;
+    *launches = (int) plan->mg->launches;
+    *bytes = plan->mg->bytes;
+    return LORA_OK;
+}
+
+int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lora_mg *m, const lora_until *u, lora_mg_result *r,
+                           void *stream) {
+    if (!plan || !d_x || !m || !u || !r || lora::bad_mg_until(u) || lora::bad_mg(m) || d_f == d_x) return LORA_EINVAL;
+    if (lora::misaligned(d_x) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    const Plan &p = plan->p;
+    if (!lora::has_mg(p)) return lora::no_mg_kernels();
+    if (!lora::taps_symmetric(p.w, p.ntaps))
+        return lora::unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
+    std::vector<lora::LevelDesc> descs;
+    if (int rc = lora::describe_levels(p, m, descs)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_x, d_x, s)) return rc;
+    *r = {{0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}}, 0, {{0}}};
+    lora::fill_levels(descs, r);
+    if (u->max_times < u->check_every) return LORA_OK;
+    if (int rc = lora::ensure_hierarchy(plan, m, d_f != nullptr)) return rc;
+    lora::MgHierarchy *h = plan->mg;
+    const int L = (int) h->levels.size() - 1;
+    for (const lora::Level &lv : h->levels) {
+        const void *own[] = {lv.x.ptr, lv.spare.ptr, lv.g.ptr, lv.plain ? lv.plain->cg[0].ptr : nullptr, lv.plain ? lv.plain->cg[1].ptr : nullptr,
+                             lv.plain ? lv.plain->cg[2].ptr : nullptr};
+        for (const void *o : own)
+            if (o && (o == d_x || o == d_f)) return LORA_EINVAL;
+    }
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+
+    // once per run, on this stream: level 0's source g_0 = fl(c_0 f) and the halos every level's free grid shares with its iterate
+    lora::Level &top = h->levels[0];
+    double *x0 = static_cast<double *>(d_x), *spare0 = static_cast<double *>(top.spare.ptr);
+    if (int rc = lora_plan_set_source(top.smooth, d_f ? top.g.ptr : nullptr)) return rc;
+    if (d_f)
+        if (int rc = lora::hip_status(lora::launch_mg_scale(p.ndim, p.dims, static_cast<double *>(top.g.ptr), static_cast<const double *>(d_f),
+                                                            top.desc.c, s),
+                                      "source scale launch"))
+            return rc;
+    if (int rc = lora::hip_status(lora::launch_halo(p, spare0, d_x, lora::HALO_COPY, s), "halo copy")) return rc;
+    for (int l = 1; l < L; ++l)
+        if (int rc = lora::hip_status(lora::launch_halo(h->levels[l].smooth->p, h->levels[l].spare.ptr, nullptr, lora::HALO_ZERO, s), "halo reset"))
+            return rc;
+    h->levels[L].cur = static_cast<double *>(h->levels[L].x.ptr);
+
+    const int cells_L = (int) std::fmin(h->levels[L].cells, 64.0);
+    const lora::Run run = {plan, h, m, s, p.ndim, L, m->coarse_iters ? m->coarse_iters : cells_L};
+    // the sweep of the two-pass probe: the plan's own single sweep with f as its source (as lora_plan_run_cg_until)
+    Plan with_f = p;
+    with_f.source = d_f;
+    const lora::Apps whole = {1, 0, p.dims[0]};
+    static const int pads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+    const bool fused = u->norm == LORA_NORM_MAX;
+    lora_until_result &ur = r->until;
+    while (ur.times_done + u->check_every <= u->max_times) {
+        for (int i = 0; i < u->check_every; ++i) {
+            lora::Tally tally;
+            top.cur = x0;
+            top.other = spare0;
+            if (int rc = lora::cycle(run, 0, tally)) return rc;
+            if (top.cur != x0) {  // an odd number of launches moved the iterate: back into the caller's grid, interior cells only
+                if (int rc = lora::hip_status(lora::launch_copy_interior(LORA_F64, p.ndim, p.dims, x0, pads[p.ndim - 1], top.cur, pads[p.ndim - 1], s),
+                                              "copy launch"))
+                    return rc;
+                tally.add(1, top.cells, 2.0);
+            }
+            h->launches = tally.launches;
+            h->bytes = tally.bytes;
+        }
+        if (fused) {
+            if (int rc = lora::residual_whole(plan, d_x, d_f, &ur.last, s)) return rc;
+        } else {
+            if (int rc = lora::launch_apps(with_f, whole, d_x, spare0, s)) return rc;
+            if (int rc = lora::diff_whole(plan, spare0, d_x, &ur.last, s)) return rc;
+        }
+        ur.times_done += u->check_every;
+        if (lora::until_decide(u, &ur)) break;
+    }
+    return LORA_OK;
+}
+
+int lora_run_host_mg(int shape, const double *in, const double *source, double *out, const double *params, const lora_mg *m,
+                     const lora_until *u, lora_mg_result *r, const int *dims, int quiet, lora_run_info *info) {
+    if (!in || !out || !dims || !m || !u || !r || lora::bad_mg_until(u) || lora::bad_mg(m)) return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("a multigrid run (its source is an argument)")) return rc;
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
+    if (rc != LORA_OK) return rc;
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
+    void *d_x = g.b[0], *d_f = g.b[1];
+    if ((rc = lora::hip_status(hipMemcpy(d_x, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if (source)
+        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    // set-up outside the timed region: the hierarchy, and one probe as a warm-up (it writes no grid)
+    if ((rc = lora_plan_prepare_mg(plan, m))) return rc;
+    lora_grid_diff warm;
+    if ((rc = lora_plan_residual_src(plan, d_x, d_f, 0, 0, &warm, nullptr))) return rc;
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
+
+    g.tic();
+    if ((rc = lora_plan_run_mg_until(plan, d_x, d_f, m, u, r, g.s))) return rc;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();  // the cycles and their probes
+    if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    // per cycle: the bytes its launches move (lora_plan_mg_cycle_cost), in grids of the fine level
+    const double per_cycle = plan->mg && plan->mg->launches ? plan->mg->bytes / (8.0 * g.points) : 0.0;
+    return g.finish(r->until.times_done, per_cycle, 1, quiet, info);
+}
+
+}  // extern "C"

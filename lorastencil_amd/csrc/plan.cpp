@@ -505,6 +505,8 @@ const Option kOptions[] = {
     {"fused_residual", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_fused_residual(q) ? 1 : 0; }},
     // whether the plan has the conjugate-gradient kernels (lora_plan_apply_dot, lora_plan_cg_update, lora_plan_cg_direction)
     {"cg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_cg(q) ? 1 : 0; }},
+    // whether the plan has the multigrid transfer kernels and the V-cycle driver (lora_plan_mg_restrict, lora_plan_run_mg_until)
+    {"mg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_mg(q) ? 1 : 0; }},
     // whether the plan carries a source (lora_plan_set_source)
     {"source", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return q.source ? 1 : 0; }},
 };

@@ -265,6 +265,14 @@ class ThetaResult(NamedTuple):
     iterations: tuple = ()
 
 
+class MgResult(NamedTuple):
+    """What ``run_mg_until`` returns (lora_mg_result): the until-result counted in CYCLES and the extents of the levels that ran,
+    level 0 first."""
+    until: UntilResult
+    levels: int
+    level_dims: tuple
+
+
 NORMS = {"max": _lib.NORM_MAX, "rms": _lib.NORM_RMS}
 
 
@@ -283,6 +291,14 @@ def _cg_result(r) -> CgResult:
 def _theta_result(r, iterations=()) -> ThetaResult:
     return ThetaResult(r.steps_done, bool(r.breakdown), r.unconverged_steps, r.iterations_total, r.iterations_max, r.last_rr0, r.last_rr,
                        _tuple_of(GridDiff, r.steady), tuple(int(k) for k in iterations))
+
+
+def _mg_result(r, nd: int) -> MgResult:
+    return MgResult(_until_result(r.until), r.levels, tuple(tuple(r.level_dims[l][a] for a in range(nd)) for l in range(r.levels)))
+
+
+def _mg_arg(pre, post, omega, max_levels, coarse_iters):
+    return _lib.Mg(int(pre), int(post), float(omega), int(max_levels), int(coarse_iters))
 
 
 def _until_arg(tol, rtol, norm, check_every, max_times):
@@ -493,6 +509,57 @@ def run_host_cg(shape, in_: np.ndarray, tol: float, source=None, rtol: float = 0
     check(_lib.lib().lora_run_host_cg(sid, _p(in_), None if src is None else _p(src), _p(out), pp, ctypes.byref(u), ctypes.byref(r),
                                       _dims_arg(dims), int(quiet), ctypes.byref(info)), f"lora_run_host_cg({SHAPE_NAMES.get(sid, sid)})")
     return out, _cg_result(r), info
+
+
+def mg_coarse_dims(shape, dims: Sequence[int]) -> tuple:
+    """The extents of the next coarser multigrid level (lora_mg_coarse_dims; host only): floor(n / 2) per axis, the innermost
+    rounded down to even.  Raises LoraError (LORA_EUNSUPPORTED) for a 1D shape and when an extent would fall below 4."""
+    sid = shape_id(shape)
+    out = (ctypes.c_int * 3)()
+    if len(dims) != ndim(sid):
+        raise ValueError("wrong number of sizes for the shape")
+    check(_lib.lib().lora_mg_coarse_dims(sid, _dims_arg(dims), out), "lora_mg_coarse_dims")
+    return tuple(out[: ndim(sid)])
+
+
+def mg_coarse_taps(shape, w, dims: Sequence[int], cdims: Sequence[int]) -> np.ndarray:
+    """The taps of the coarse operator for the grids ``dims`` -> ``cdims`` from the fine taps ``w`` (lora_mg_coarse_taps; host
+    only): w q_a along axis a with q_a = ((n_c + 1) / (n + 1))^2, the geometric blend for diagonal taps, the centre tap keeping
+    the tap sum."""
+    sid = shape_id(shape)
+    w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+    if w.size != ntaps(sid) or len(dims) != ndim(sid) or len(cdims) != ndim(sid):
+        raise ValueError("wrong number of taps or sizes for the shape")
+    out = np.zeros_like(w)
+    check(_lib.lib().lora_mg_coarse_taps(sid, _p(w), _dims_arg(dims), _dims_arg(cdims), _p(out)), "lora_mg_coarse_taps")
+    return out
+
+
+def run_host_mg(shape, in_: np.ndarray, tol: float, source=None, pre: int = 2, post: int = 2, omega: float = 0.8, max_levels: int = 0,
+                coarse_iters: int = 0, rtol: float = 0.0, norm="max", check_every: int = 1, max_times: int = 50, params=None,
+                quiet: bool = True):
+    """Multigrid V(pre, post) cycles for u = S(u) + f from the padded float64 host array ``in_`` (the start iterate, its halo the
+    boundary values), ``source`` a padded host array of f or None (lora_run_host_mg): until the true residual is <= tol + rtol *
+    max|S(u) + f|, checked every ``check_every`` cycles, ``max_times`` cycles at most.  Returns (the iterate as a padded array,
+    MgResult, RunInfo)."""
+    sid = shape_id(shape)
+    in_ = np.ascontiguousarray(in_, dtype=np.float64)
+    h = halo(sid)
+    if in_.ndim != len(h):
+        raise ValueError("in_ must be a padded array of the shape's rank")
+    src = None
+    if source is not None:
+        src = np.ascontiguousarray(source, dtype=np.float64)
+        if src.shape != in_.shape:
+            raise ValueError("source must be a padded array of in_'s size")
+    dims = [in_.shape[i] - 2 * h[i] for i in range(in_.ndim)]
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    m, u = _mg_arg(pre, post, omega, max_levels, coarse_iters), _until_arg(tol, rtol, norm, check_every, max_times)
+    r, info = _lib.MgResult(), RunInfo()
+    check(_lib.lib().lora_run_host_mg(sid, _p(in_), None if src is None else _p(src), _p(out), pp, ctypes.byref(m), ctypes.byref(u),
+                                      ctypes.byref(r), _dims_arg(dims), int(quiet), ctypes.byref(info)), f"lora_run_host_mg({SHAPE_NAMES.get(sid, sid)})")
+    return out, _mg_result(r, in_.ndim), info
 
 
 def run_host_theta(shape, in_: np.ndarray, tau: float, steps: int, source=None, theta: float = 1.0, max_iters: int = 50,
@@ -871,6 +938,40 @@ class Plan:
         check(_lib.lib().lora_plan_run_cg_until(self._h, _ptr(d_x), _optr(d_f), ctypes.byref(u), ctypes.byref(r), _stream(stream)),
               "lora_plan_run_cg_until")
         return _cg_result(r)
+
+    # -- geometric multigrid (plans whose option "mg" reads 1); the coarse grid is a padded array of mg_coarse_dims(shape, dims)
+    def mg_restrict(self, d_fine, d_coarse, scale: float = 1.0, stream=None):
+        """coarse = scale * prod(rho) * P^T fine on the interior cells of the coarse grid (lora_plan_mg_restrict); asynchronous."""
+        check(_lib.lib().lora_plan_mg_restrict(self._h, _ptr(d_fine), _ptr(d_coarse), float(scale), _stream(stream)), "lora_plan_mg_restrict")
+
+    def mg_prolong_add(self, d_coarse, d_fine, stream=None):
+        """fine = fine + P coarse on the interior cells of the fine grid, P linear interpolation with a zero coarse halo
+        (lora_plan_mg_prolong_add); asynchronous."""
+        check(_lib.lib().lora_plan_mg_prolong_add(self._h, _ptr(d_coarse), _ptr(d_fine), _stream(stream)), "lora_plan_mg_prolong_add")
+
+    def prepare_mg(self, pre: int = 2, post: int = 2, omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0):
+        """Allocate now what ``run_mg_until`` with the same cycle would allocate on first need (the level plans and their grids)."""
+        m = _mg_arg(pre, post, omega, max_levels, coarse_iters)
+        check(_lib.lib().lora_plan_prepare_mg(self._h, ctypes.byref(m)), "lora_plan_prepare_mg")
+        return self
+
+    def run_mg_until(self, d_x, d_f, tol: float, pre: int = 2, post: int = 2, omega: float = 0.8, max_levels: int = 0,
+                     coarse_iters: int = 0, rtol: float = 0.0, norm="max", check_every: int = 1, max_times: int = 50,
+                     stream=None) -> MgResult:
+        """Multigrid V(pre, post) cycles for u = S(u) + f, damped Jacobi with ``omega`` as the smoother and CG on the coarsest
+        level, in rounds of ``check_every`` cycles until the TRUE residual max|S(u) + f - u| is <= tol + rtol * max|S(u) + f|
+        (lora_plan_run_mg_until).  ``d_x``: the start iterate with the boundary values in its halo, then the solution;
+        ``d_f``: a padded device grid or None.  Needs point-symmetric taps."""
+        m, u, r = _mg_arg(pre, post, omega, max_levels, coarse_iters), _until_arg(tol, rtol, norm, check_every, max_times), _lib.MgResult()
+        check(_lib.lib().lora_plan_run_mg_until(self._h, _ptr(d_x), _optr(d_f), ctypes.byref(m), ctypes.byref(u), ctypes.byref(r),
+                                                _stream(stream)), "lora_plan_run_mg_until")
+        return _mg_result(r, len(self.dims))
+
+    def mg_cycle_cost(self):
+        """(launches, bytes) of one cycle of the last ``run_mg_until`` (lora_plan_mg_cycle_cost)."""
+        n, b = ctypes.c_int(), ctypes.c_double()
+        check(_lib.lib().lora_plan_mg_cycle_cost(self._h, ctypes.byref(n), ctypes.byref(b)), "lora_plan_mg_cycle_cost")
+        return n.value, b.value
 
     # -- reductions on the device (these block until the result is on the host)
     def stats(self, d_buf, begin: int = 0, end: int = 0, stream=None) -> GridStats:

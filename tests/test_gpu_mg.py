@@ -1,0 +1,684 @@
+"""GPU tests of the multigrid transfer kernels and the V-cycle driver (kernels_mg.hip, mg.cpp).
+
+Yardsticks, none of them the code under test: dense per-axis interpolation matrices from the closed form of the header,
+applied in numpy's extended precision, for the two transfer kernels; a Python loop over the public entries, its level plans
+built from the header's formulas, for the bits of a cycle; ``numpy.linalg.solve`` on the dense system and the closed form of
+rho for the solves; and for grid independence a numpy model of the cycle written here from the same formulas (its own
+coarsening rule and coarse taps, an exact dense solve on the coarsest level), which never calls the engine.
+
+Buffers are carved by tests/arena.py at offsets 16 and 240, the guard bands NaN.
+
+Grid independence, the factor between the engine's and the model's residual after each of the first six cycles.  Both are fp64
+runs of one algorithm that differ in summation order and in the coarsest solve, so the yardstick for "how far apart may two such
+runs be" is the model against itself with its taps summed in the opposite order.  MEASURED (numpy, this file's model, seed 5):
+the residuals of the two orders differ by a factor of at most 1.00000000037 at 64 x 64 and 1.00000000016 at 256 x 256 over the
+first six cycles -- the noise of evaluating a residual 1e-4 of |f| from an iterate 1e3 |f| large.  CHOSEN: the deviation from 1
+with a tenfold margin, factor = 1 + 10 (measured - 1), computed in the test from the model's two runs (1.0000000037 with the
+figures above).  It was fixed before the engine was run and is never taken from the engine's output.
+"""
+import functools
+import math
+import os
+import subprocess
+import zlib
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+OFFSETS = (16, 240)
+U = 2.0 ** -53
+
+TRANSFER_CASES = [
+    ("star2d1r", (8, 8), (4, 4)),              # the smallest legal
+    ("star2d1r", (9, 10), (4, 4)),             # ratios 2.0 and 2.2: windows of varying width
+    ("box2d3r", (70, 260), (35, 130)),         # odd coarse outer extent, partial tiles
+    ("star3d1r", (8, 8, 8), (4, 4, 4)),        # the smallest legal in 3D
+    ("box3d1r", (35, 17, 130), (17, 8, 64)),   # odd outer extents in 3D
+]
+TRANSFER_IDS = [f"{s}-{'x'.join(map(str, d))}" for s, d, _ in TRANSFER_CASES]
+
+
+@pytest.fixture(scope="module")
+def L(engine_built):
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import lorastencil_amd as L
+
+    return L
+
+
+# ---- the closed forms of the header, in numpy ------------------------------------------------------------------------------------
+def P_axis(n, nc, dtype=np.float64):
+    """p(i, j) = max(0, 1 - |(i + 1)(n_c + 1) - (j + 1)(n + 1)| / (n + 1)) as an n x n_c matrix; the numerator an exact integer"""
+    i = np.arange(n, dtype=np.int64)[:, None] + 1
+    j = np.arange(nc, dtype=np.int64)[None, :] + 1
+    num = (n + 1) - np.abs(i * (nc + 1) - j * (n + 1))
+    return np.maximum(num, 0).astype(dtype) / dtype(n + 1)
+
+
+def apply_axes(mats, x):
+    """(M_0 (x) M_1 (x) ...) x for one matrix per axis"""
+    for a, m in enumerate(mats):
+        x = np.moveaxis(np.tensordot(m, x, axes=(1, a)), 0, a)
+    return x
+
+
+def tap_offsets(nd):
+    if nd == 2:
+        return [(t // 7 - 3, t % 7 - 3) for t in range(49)]
+    return [(t // 9 - 1, t // 3 % 3 - 1, t % 3 - 1) for t in range(27)]
+
+
+def jacobi_taps(nd):
+    """1 / (2 nd) on the 2 nd nearest neighbours: the 5- and 7-point Jacobi iteration"""
+    offs = tap_offsets(nd)
+    w = np.zeros(len(offs))
+    for t, d in enumerate(offs):
+        if sum(abs(x) for x in d) == 1:
+            w[t] = 1.0 / (2 * nd)
+    return w
+
+
+def jacobi_rho(dims):
+    """the header's closed form: the mean of cos(pi / (n + 1)) over the axes"""
+    return sum(math.cos(math.pi / (n + 1)) for n in dims) / len(dims)
+
+
+def smoother_taps(w, omega):
+    """(s, c) of the header: d = fl(1 - w[centre]), c = fl(omega / d), s[t] = fl(c w[t]), s[centre] = fl(fl(c w[centre]) + fl(1 - c))"""
+    ct = len(w) // 2
+    d = 1.0 - w[ct]
+    c = omega / d
+    s = c * w
+    s[ct] = s[ct] + (1.0 - c)
+    return s, c
+
+
+# ---- grids --------------------------------------------------------------------------------------------------------------------
+class Grids:
+    """n grids of one padded shape carved from one poisoned allocation; grid i starts as values[i] or stays NaN (None)"""
+
+    def __init__(self, L, shape, dims, offset, values):
+        import torch
+        from arena import carve
+
+        self.L, self.shape, self.dims = L, shape, tuple(dims)
+        self.arena = carve(L.padded_shape(shape, dims), "f64", n_buffers=len(values), offset_bytes=offset)
+        self.v = self.arena.views
+        for view, a in zip(self.v, values):
+            if a is not None:
+                view.copy_(torch.from_numpy(np.array(a)))
+
+    def interior_mask(self):
+        import torch
+
+        m = torch.zeros(self.v[0].shape, dtype=torch.bool, device="cuda")
+        self.L.interior(self.shape, m)[...] = True
+        return m
+
+    def bits(self, i):
+        return self.arena.bits(i).clone()
+
+    def guards(self, what):
+        import torch
+        from arena import assert_guards_intact
+
+        torch.cuda.synchronize()
+        assert_guards_intact(self.arena, what)
+
+    def host(self, i):
+        return self.L.interior(self.shape, self.v[i]).cpu().numpy().copy()
+
+
+def padded(L, shape, dims, interior, halo):
+    """a padded array with the given interior; halo: a number for every halo cell, or an array of the padded shape to take them from"""
+    a = np.array(halo, dtype=np.float64) if isinstance(halo, np.ndarray) else np.full(L.padded_shape(shape, dims), float(halo))
+    L.interior(shape, a)[...] = interior
+    return a
+
+
+def same_bits(a, b):
+    import torch
+
+    return torch.equal(a.view(torch.int64), b.view(torch.int64))
+
+
+@functools.lru_cache(maxsize=None)
+def transfer_data(shape, dims, cdims):
+    """seeded normal interiors of a fine and a coarse grid (two each), made once, read-only"""
+    rng = np.random.default_rng(zlib.crc32(repr(("mg", shape, dims)).encode()))
+    out = [rng.standard_normal(dims) * 3.0, rng.standard_normal(dims) * 3.0, rng.standard_normal(cdims) * 3.0, rng.standard_normal(cdims) * 3.0]
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def transfer_yardstick(dims, cdims):
+    """per axis: P in extended precision, |P| (the same: no weight is negative), and the 0 / 1 pattern of its non-zero weights"""
+    LD = np.longdouble
+    assert np.finfo(LD).eps <= 2.0 ** -63, "the yardstick wants an extended-precision long double"
+    P = [P_axis(n, nc, LD) for n, nc in zip(dims, cdims)]
+    pattern = [(p > 0).astype(np.float64) for p in P]
+    rho = float(np.prod([(nc + 1) / (n + 1) for n, nc in zip(dims, cdims)]))
+    return P, pattern, rho
+
+
+# ---- the transfer kernels -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,dims,cdims", TRANSFER_CASES, ids=TRANSFER_IDS)
+def test_restriction_against_the_dense_matrices(L, shape, dims, cdims):
+    import torch
+
+    assert L.mg_coarse_dims(shape, dims) == cdims
+    plan = L.Plan(shape, dims)
+    assert plan.get_option("mg") == 1
+    fine, _, coarse_old, _ = transfer_data(shape, dims, cdims)
+    P, pattern, rho = transfer_yardstick(dims, cdims)
+    LD = np.longdouble
+    for off, scale in zip(OFFSETS, (1.0, -0.37)):
+        gf = Grids(L, shape, dims, off, [padded(L, shape, dims, fine, np.nan)])       # NaN in every halo cell of the source
+        gc = Grids(L, shape, cdims, off, [padded(L, shape, cdims, coarse_old, 7.5)])  # old values: every interior cell is overwritten
+        before_f, before_c, inner = gf.bits(0), gc.bits(0), gc.interior_mask()
+        plan.mg_restrict(gf.v[0], gc.v[0], scale)
+        gf.guards(f"{shape} {dims} restrict: fine")
+        gc.guards(f"{shape} {dims} restrict: coarse")
+        assert torch.equal(gf.arena.bits(0), before_f), "the fine grid was written"
+        assert torch.equal(gc.arena.bits(0)[~inner], before_c[~inner]), "a halo cell of the coarse grid was written"
+        got = gc.host(0)
+        exact = LD(scale) * LD(rho) * apply_axes([p.T for p in P], fine.astype(LD))
+        mass = abs(scale) * rho * apply_axes([p.T.astype(np.float64) for p in P], np.abs(fine))
+        terms = apply_axes([q.T for q in pattern], np.ones(dims))
+        bound = (terms + 4) * U * mass
+        err = np.abs(got.astype(LD) - exact).astype(np.float64)
+        print(shape, dims, "restrict scale", scale, "terms", terms.min(), "..", terms.max(), "max err / bound", np.max(err / bound))
+        assert np.isfinite(got).all() and terms.max() <= 5 ** len(dims) and terms.min() >= 3 ** len(dims)
+        assert np.all(err <= bound)
+        # the same call gives the same bits
+        first = gc.bits(0)
+        plan.mg_restrict(gf.v[0], gc.v[0], scale)
+        torch.cuda.synchronize()
+        assert torch.equal(gc.arena.bits(0), first)
+
+
+@pytest.mark.parametrize("shape,dims,cdims", TRANSFER_CASES, ids=TRANSFER_IDS)
+def test_prolongation_against_the_dense_matrices(L, shape, dims, cdims):
+    import torch
+
+    plan = L.Plan(shape, dims)
+    fine, _, coarse, _ = transfer_data(shape, dims, cdims)
+    P, pattern, _ = transfer_yardstick(dims, cdims)
+    LD = np.longdouble
+    for off in OFFSETS:
+        fine0 = padded(L, shape, dims, fine, 2.25)
+        gf = Grids(L, shape, dims, off, [fine0, fine0])
+        gc = Grids(L, shape, cdims, off, [padded(L, shape, cdims, coarse, np.nan)])  # NaN in every halo cell of the source
+        before_f, before_c, inner = gf.bits(0), gc.bits(0), gf.interior_mask()
+        plan.mg_prolong_add(gc.v[0], gf.v[0])
+        gf.guards(f"{shape} {dims} prolong: fine")
+        gc.guards(f"{shape} {dims} prolong: coarse")
+        assert torch.equal(gc.arena.bits(0), before_c), "the coarse grid was written"
+        assert torch.equal(gf.arena.bits(0)[~inner], before_f[~inner]), "a halo cell of the fine grid was written"
+        got = gf.host(0)
+        exact = fine.astype(LD) + apply_axes(P, coarse.astype(LD))
+        mass = np.abs(fine) + apply_axes([p.astype(np.float64) for p in P], np.abs(coarse))
+        terms = 1 + apply_axes(pattern, np.ones(cdims))  # the fine cell's own value is a term of weight 1
+        bound = (terms + 4) * U * mass
+        err = np.abs(got.astype(LD) - exact).astype(np.float64)
+        print(shape, dims, "prolong terms", terms.min(), "..", terms.max(), "max err / bound", np.max(err / bound))
+        assert np.isfinite(got).all() and terms.max() <= 1 + 2 ** len(dims)
+        assert np.all(err <= bound)
+        # the same call gives the same bits
+        plan.mg_prolong_add(gc.v[0], gf.v[1])
+        torch.cuda.synchronize()
+        assert torch.equal(gf.arena.bits(1), gf.arena.bits(0))
+
+
+@pytest.mark.parametrize("shape,dims,cdims", TRANSFER_CASES, ids=TRANSFER_IDS)
+def test_the_two_kernels_are_adjoint(L, shape, dims, cdims):
+    """dot(P e, r) prod(rho) == dot(e, R r) for R = prod(rho) P^T, through the kernels, within the bounds of their own errors"""
+    plan = L.Plan(shape, dims)
+    r, _, e, _ = transfer_data(shape, dims, cdims)
+    P, pattern, rho = transfer_yardstick(dims, cdims)
+    gf = Grids(L, shape, dims, 16, [padded(L, shape, dims, np.zeros(dims), 0.0), padded(L, shape, dims, r, np.nan)])
+    gc = Grids(L, shape, cdims, 240, [padded(L, shape, cdims, e, np.nan), None])
+    plan.mg_prolong_add(gc.v[0], gf.v[0])
+    plan.mg_restrict(gf.v[1], gc.v[1], 1.0)
+    gf.guards("adjoint: fine")
+    gc.guards("adjoint: coarse")
+    Pe, Rr = gf.host(0), gc.host(1)
+    lhs, rhs = math.fsum((Pe * r).ravel()) * rho, math.fsum((e * Rr).ravel())
+    # each kernel's output within its (terms + 4) u sum |weight value|; the two sums are exact, the scale one rounding
+    absP = [p.astype(np.float64) for p in P]
+    err_p = (1 + apply_axes(pattern, np.ones(cdims)) + 4) * U * apply_axes(absP, np.abs(e))
+    err_r = (apply_axes([q.T for q in pattern], np.ones(dims)) + 4) * U * rho * apply_axes([p.T for p in absP], np.abs(r))
+    bound = rho * math.fsum((np.abs(r) * err_p).ravel()) + math.fsum((np.abs(e) * err_r).ravel()) + 2 * U * abs(rhs)
+    print(shape, dims, "dot(P e, r) rho", lhs, "dot(e, R r)", rhs, "difference", lhs - rhs, "bound", bound)
+    assert abs(lhs - rhs) <= bound
+
+
+# ---- one cycle, bit for bit ------------------------------------------------------------------------------------------------------
+def level_tables(L, shape, dims, w, omega, max_levels=0):
+    """[(dims, w, s, c)] per level from the header's formulas; the coarse taps through the public host entry"""
+    out = []
+    while True:
+        s, c = smoother_taps(w, omega)
+        out.append((tuple(dims), w, s, c))
+        try:
+            nxt = L.mg_coarse_dims(shape, dims)
+        except L.LoraError:
+            break
+        if max_levels and len(out) >= max_levels:
+            break
+        w = L.mg_coarse_taps(shape, w, dims, nxt)
+        dims = nxt
+    return out
+
+
+class PublicCycle:
+    """The loop of the header's bit contract: level plans built with Plan + set_weights + set_boundary + set_source, the cycle a
+    loop over the public entries, the CG scalars divided in host fp64."""
+
+    def __init__(self, L, shape, dims, w, omega, pre, post, with_f, coarse_iters=0):
+        import torch
+
+        self.L, self.shape, self.pre, self.post = L, shape, pre, post
+        self.tab = level_tables(L, shape, dims, w, omega)
+        self.last = len(self.tab) - 1
+        self.plain, self.smooth, self.x, self.spare, self.g = [], [], [], [], []
+        for l, (d, wl, sl, cl) in enumerate(self.tab):
+            z = lambda: torch.zeros(L.padded_shape(shape, d), dtype=torch.float64, device="cuda")
+            self.plain.append(L.Plan(shape, d).set_weights(wl))
+            self.x.append(z())
+            self.spare.append(z())
+            self.g.append(z())
+            if l < self.last:
+                sm = L.Plan(shape, d).set_weights(sl).set_boundary("dirichlet")
+                if l > 0 or with_f:
+                    sm.set_source(self.g[l])
+                self.smooth.append(sm)
+        cells = int(np.prod(self.tab[-1][0]))
+        self.iters = coarse_iters or min(64, cells)
+        self.p, self.q = torch.zeros_like(self.x[-1]), torch.zeros_like(self.x[-1])
+
+    def inner(self, l, t):
+        return self.L.interior(self.shape, t)
+
+    def cycle(self, l, cur, other):
+        """one cycle on level l from the iterate in `cur`; returns the tensor that holds the iterate afterwards"""
+        if l == self.last:
+            plan, x, r, p, q = self.plain[l], cur, self.g[l], self.p, self.q
+            p.zero_()
+            self.inner(l, p).copy_(self.inner(l, r))
+            rr = plan.dot(r, r).dot
+            for _ in range(self.iters):
+                pq = plan.apply_dot(p, q).dot
+                if not (math.isfinite(pq) and pq > 0.0 and math.isfinite(rr)):
+                    break  # the sticky halt: the residual vanished exactly
+                alpha = rr / pq
+                rr_new = plan.cg_update(x, r, p, q, alpha).dot
+                beta = rr_new / rr
+                rr = rr_new
+                if not math.isfinite(rr_new):
+                    break
+                plan.cg_direction(p, r, beta)
+            return cur
+        sm, c = self.smooth[l], self.tab[l][3]
+        if self.pre:
+            sm.run(cur, other, self.pre)
+            if self.pre % 2:
+                cur, other = other, cur
+        sm.step(cur, other)
+        self.inner(l, other).copy_(self.inner(l, other) - self.inner(l, cur))
+        nxt_c = self.tab[l + 1][3]
+        scale = 1.0 / c if l + 1 == self.last else nxt_c / c
+        self.plain[l].mg_restrict(other, self.g[l + 1], scale)
+        self.x[l + 1].zero_()
+        coarse = self.cycle(l + 1, self.x[l + 1], self.spare[l + 1])
+        self.plain[l].mg_prolong_add(coarse, cur)
+        if self.post:
+            sm.run(cur, other, self.post)
+            if self.post % 2:
+                cur, other = other, cur
+        return cur
+
+    def run(self, x0, f, cycles):
+        import torch
+
+        self.x[0].copy_(torch.from_numpy(x0))
+        self.spare[0].zero_()
+        if f is not None:
+            self.g[0].copy_(torch.from_numpy(f) * self.tab[0][3])  # g_0 = fl(c_0 f): one multiplication
+        cur, other = self.x[0], self.spare[0]
+        for _ in range(cycles):
+            cur = self.cycle(0, cur, other)
+            other = self.spare[0] if cur is self.x[0] else self.x[0]
+        torch.cuda.synchronize()
+        return cur
+
+
+@pytest.mark.parametrize("shape,dims,levels", [("star2d1r", (16, 20), 3), ("box3d1r", (8, 8, 16), 2)])
+@pytest.mark.parametrize("with_f", [True, False], ids=["f", "nof"])
+def test_driver_equals_the_composition_of_the_public_entries(L, shape, dims, levels, with_f):
+    import torch
+
+    nd = len(dims)
+    rng = np.random.default_rng(zlib.crc32(repr(("cycle", shape, dims)).encode()))
+    if shape == "star2d1r":
+        w = jacobi_taps(2)
+    else:  # every one of the 27 taps, point-symmetric, the sum below 1, the centre not zero
+        w = rng.uniform(0.2, 1.0, 27)
+        w = (w + w[::-1]) / 2
+        w *= 0.9 / w.sum()
+    ps = L.padded_shape(shape, dims)
+    x0 = rng.standard_normal(ps)                      # non-zero halo values: the boundary
+    f = rng.standard_normal(ps) if with_f else None
+    pre, post, omega = 1, 2, 0.8
+    plan = L.Plan(shape, dims).set_weights(w)
+    ref = PublicCycle(L, shape, dims, w, omega, pre, post, with_f)
+    assert len(ref.tab) == levels
+    for off, cycles in zip(OFFSETS, (1, 2)):
+        g = Grids(L, shape, dims, off, [x0, f])
+        before_x, before_f, halo = g.bits(0), g.bits(1), ~g.interior_mask()
+        res = plan.run_mg_until(g.v[0], g.v[1] if with_f else None, tol=0.0, pre=pre, post=post, omega=omega, check_every=1, max_times=cycles)
+        g.guards(f"{shape} {dims} run_mg_until x{cycles}")
+        assert torch.equal(g.arena.bits(1), before_f), "d_f was written"
+        assert torch.equal(g.arena.bits(0)[halo], before_x[halo]), "a halo cell of d_x was written"
+        assert res.levels == levels and res.level_dims == tuple(t[0] for t in ref.tab)
+        assert res.until.times_done == cycles and res.until.checks == cycles and not res.until.converged and not res.until.diverged
+        expect = ref.run(x0, f, cycles)
+        assert same_bits(g.v[0], expect), f"{shape} {dims}: d_x after {cycles} cycle(s) differs from the loop over the public entries"
+        # the probe is the true residual of the caller's problem
+        last = plan.residual_src(g.v[0], g.v[1] if with_f else None)
+        assert res.until.residual == last.max_abs and res.until.last.argmax == last.argmax
+        launches, nbytes = plan.mg_cycle_cost()
+        print(shape, dims, "launches per cycle", launches, "bytes per cycle", nbytes)
+        assert launches > 5 * ref.iters and nbytes > 0
+
+
+# ---- solves -----------------------------------------------------------------------------------------------------------------------
+def dense_problem(L, shape, dims, w, f, x):
+    """A = I - S on the interior as a dense matrix and b = f + S(the halo of x): A u = b is u = S(u) + f with x's boundary"""
+    nd, side = len(dims), {2: 7, 3: 3}[len(dims)]
+    n = int(np.prod(dims))
+    idx = np.arange(n).reshape(dims)
+    taps = np.asarray(w).reshape((side,) * nd)
+    halo = [(a - b) // 2 for a, b in zip(x.shape, dims)]
+    S, b = np.zeros((n, n)), L.interior(shape, f).astype(np.float64).ravel().copy()
+    for cell in np.ndindex(*dims):
+        for t in zip(*np.nonzero(taps)):
+            nb = tuple(c + k - side // 2 for c, k in zip(cell, t))
+            if all(0 <= c < d for c, d in zip(nb, dims)):
+                S[idx[cell], idx[nb]] += taps[t]
+            else:
+                b[idx[cell]] += taps[t] * x[tuple(c + h for c, h in zip(nb, halo))]
+    return np.eye(n) - S, b
+
+
+@pytest.mark.parametrize("shape,dims", [("star2d1r", (16, 16)), ("star3d1r", (8, 8, 8))])
+def test_it_solves_the_jacobi_problem(L, shape, dims):
+    w = jacobi_taps(len(dims))
+    rng = np.random.default_rng(zlib.crc32(repr(("solve", dims)).encode()))
+    ps = L.padded_shape(shape, dims)
+    f = padded(L, shape, dims, rng.standard_normal(dims), 0.0)
+    x = padded(L, shape, dims, np.zeros(dims), rng.standard_normal(ps))  # zero start, non-zero boundary values
+    A, b = dense_problem(L, shape, dims, w, f, x)
+    tol = 1e-12 * np.abs(f).max()
+    rho = jacobi_rho(dims)
+    plan = L.Plan(shape, dims).set_weights(w)
+    g = Grids(L, shape, dims, 240, [x, f])
+    before_x, halo = g.bits(0), ~g.interior_mask()
+    res = plan.run_mg_until(g.v[0], g.v[1], tol=tol, max_times=40)
+    g.guards(f"{shape} {dims} solve")
+    import torch
+
+    assert torch.equal(g.arena.bits(0)[halo], before_x[halo]), "a halo cell of d_x was written"
+    err = np.abs(g.host(0).ravel() - np.linalg.solve(A, b)).max()
+    print(shape, dims, res, "error against numpy.linalg.solve:", err, "bound", tol / (1 - rho))
+    assert res.until.converged and not res.until.diverged and res.until.residual <= tol
+    assert plan.residual_src(g.v[0], g.v[1]).max_abs <= tol
+    assert err <= tol / (1 - rho)
+
+
+# ---- grid independence ------------------------------------------------------------------------------------------------------------
+def model_coarse_dims(dims):
+    c = [n // 2 for n in dims]
+    c[-1] &= ~1
+    return None if len(dims) < 2 or min(c) < 4 else tuple(c)
+
+
+def model_coarse_taps(w, dims, cdims):
+    nd = len(dims)
+    offs = tap_offsets(nd)
+    ct = len(offs) // 2
+    q = [((cdims[a] + 1) / (dims[a] + 1)) ** 2 for a in range(nd)]
+    wc = np.zeros_like(w)
+    for t, d in enumerate(offs):
+        if t != ct:
+            l2 = float(sum(x * x for x in d))
+            wc[t] = w[t] * np.prod([q[a] ** (d[a] * d[a] / l2) for a in range(nd)])
+    wc[ct] = w.sum() - np.delete(wc, ct).sum()
+    return wc
+
+
+def model_sweep(w, x, order=1):
+    """S(x) of an interior array with a zero halo, the taps summed in ascending (1) or descending (-1) order"""
+    offs = tap_offsets(x.ndim)
+    r = 3 if x.ndim == 2 else 1
+    xp = np.pad(x, r)
+    acc = np.zeros_like(x)
+    for t in (range(len(offs)) if order > 0 else range(len(offs) - 1, -1, -1)):
+        if w[t] != 0.0:
+            acc = acc + w[t] * xp[tuple(slice(r + d, r + d + n) for d, n in zip(offs[t], x.shape))]
+    return acc
+
+
+class Model:
+    """The V-cycle of the header in numpy on interior arrays with a zero halo; the coarsest level an exact dense solve."""
+
+    def __init__(self, w, dims, omega, pre, post, order):
+        self.pre, self.post, self.order, self.lv = pre, post, order, []
+        dims = tuple(dims)
+        while True:
+            s, c = smoother_taps(w, omega)
+            self.lv.append(dict(dims=dims, w=w, s=s, c=c))
+            nxt = model_coarse_dims(dims)
+            if nxt is None:
+                break
+            self.lv[-1]["P"] = [P_axis(n, nc) for n, nc in zip(dims, nxt)]
+            self.lv[-1]["rho"] = float(np.prod([(nc + 1) / (n + 1) for n, nc in zip(dims, nxt)]))
+            w, dims = model_coarse_taps(w, dims, nxt), nxt
+        last = self.lv[-1]
+        n = int(np.prod(last["dims"]))
+        eye = np.eye(n).reshape((n,) + last["dims"])
+        self.A = np.stack([(e - model_sweep(last["w"], e)).ravel() for e in eye], axis=1)
+
+    def cycle(self, l, x, g):
+        lv = self.lv[l]
+        if l == len(self.lv) - 1:
+            return np.linalg.solve(self.A, g.ravel()).reshape(g.shape)
+        for _ in range(self.pre):
+            x = model_sweep(lv["s"], x, self.order) + g
+        rs = (model_sweep(lv["s"], x, self.order) + g) - x
+        nxt = self.lv[l + 1]
+        scale = 1.0 / lv["c"] if l + 2 == len(self.lv) else nxt["c"] / lv["c"]
+        gc = scale * lv["rho"] * apply_axes([p.T for p in lv["P"]], rs)
+        x = x + apply_axes(lv["P"], self.cycle(l + 1, np.zeros(nxt["dims"]), gc))
+        for _ in range(self.post):
+            x = model_sweep(lv["s"], x, self.order) + g
+        return x
+
+    def residuals(self, f, target):
+        """max |S(u) + f - u| after each cycle from u = 0 until it is <= target"""
+        x, g, out = np.zeros_like(f), self.lv[0]["c"] * f, []
+        while not out or (out[-1] > target and len(out) < 40):
+            x = self.cycle(0, x, g)
+            out.append(np.abs((model_sweep(self.lv[0]["w"], x) + f) - x).max())
+        return out
+
+
+@functools.lru_cache(maxsize=None)
+def independence(n):
+    """the model in both tap orders and the engine, cycle by cycle, on the n x n Jacobi problem: zero start, random f"""
+    import lorastencil_amd as L
+    import torch
+
+    shape, dims = "star2d1r", (n, n)
+    w = jacobi_taps(2)
+    f = np.random.default_rng(5).standard_normal(dims)
+    target = 1e-8 * np.abs(f).max()  # the residual of the zero start is f
+    model = [Model(w, dims, 0.8, 2, 2, order).residuals(f, target) for order in (1, -1)]
+    plan = L.Plan(shape, dims).set_weights(w)
+    g = Grids(L, shape, dims, 16, [padded(L, shape, dims, np.zeros(dims), 0.0), padded(L, shape, dims, f, 0.0)])
+    engine = []
+    while not engine or (engine[-1] > target and len(engine) < 40):
+        res = plan.run_mg_until(g.v[0], g.v[1], tol=0.0, pre=2, post=2, omega=0.8, check_every=1, max_times=1)
+        engine.append(res.until.residual)
+    g.guards(f"grid independence {dims}")
+    return model, engine, plan.mg_cycle_cost()
+
+
+def test_cycles_do_not_grow_with_the_grid(L):
+    counts, deviation = {}, 0.0
+    for n in (64, 256):
+        model, engine, cost = independence(n)
+        counts[n] = (len(model[0]), len(engine))
+        deviation = max([deviation] + [max(a / b, b / a) - 1.0 for a, b in zip(model[0][:6], model[1][:6])])
+        print(n, "cycles: model", len(model[0]), "engine", len(engine), "launches, bytes per cycle", cost)
+        print("  model ", " ".join(f"{r:.3e}" for r in model[0]))
+        print("  engine", " ".join(f"{r:.3e}" for r in engine))
+    factor = 1.0 + 10.0 * deviation
+    print("the model's two tap orders differ by a factor of", 1.0 + deviation, "-> allowed factor", factor)
+    for n in (64, 256):
+        model, engine, _ = independence(n)
+        assert abs(counts[n][1] - counts[n][0]) <= 1, f"{n}: the engine needs {counts[n][1]} cycles, the model {counts[n][0]}"
+        ratios = [max(a / b, b / a) for a, b in zip(engine[:6], model[0][:6])]
+        print(n, "engine / model over the first six cycles:", " ".join(f"{r - 1:.2e}" for r in ratios))
+        assert all(r <= factor for r in ratios), f"{n}: a residual of the first six cycles is a factor {max(ratios)} from the model's"
+    assert abs(counts[64][1] - counts[256][1]) <= 1, f"cycles grow with the grid: {counts}"
+
+
+# ---- smaller checks ---------------------------------------------------------------------------------------------------------------
+def small_problem(L, seed=1):
+    shape, dims = "star2d1r", (16, 16)
+    rng = np.random.default_rng(seed)
+    ps = L.padded_shape(shape, dims)
+    f = padded(L, shape, dims, rng.standard_normal(dims), 0.0)
+    x = padded(L, shape, dims, np.zeros(dims), rng.standard_normal(ps))
+    return shape, dims, jacobi_taps(2), x, f
+
+
+def test_a_run_on_a_busy_devices_other_stream_gives_the_same_bits(L):
+    import torch
+
+    shape, dims, w, x, f = small_problem(L)
+    plan = L.Plan(shape, dims).set_weights(w)
+    g0 = Grids(L, shape, dims, 16, [x, f])
+    plan.run_mg_until(g0.v[0], g0.v[1], tol=0.0, max_times=3)  # torch's current stream: the null stream
+    torch.cuda.synchronize()
+    g1 = Grids(L, shape, dims, 16, [x, f])
+    mine, busy = torch.cuda.Stream(), torch.cuda.Stream()
+    a = torch.randn(2048, 2048, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(busy):
+        for _ in range(20):
+            a = (a @ a).clamp_(-1.0, 1.0)
+    res = L.Plan(shape, dims).set_weights(w).run_mg_until(g1.v[0], g1.v[1], tol=0.0, max_times=3, stream=mine)
+    g1.guards("run on a non-blocking stream")
+    assert res.until.times_done == 3
+    assert same_bits(g0.v[0], g1.v[0])
+
+
+def test_max_levels_is_honoured(L):
+    shape, dims, w, x, f = small_problem(L)
+    plan = L.Plan(shape, dims).set_weights(w)
+    g = Grids(L, shape, dims, 240, [x, f])
+    res = plan.run_mg_until(g.v[0], g.v[1], tol=0.0, max_levels=2, max_times=2)
+    g.guards("max_levels = 2")
+    assert res.levels == 2 and res.level_dims == ((16, 16), (8, 8))
+    deep = plan.run_mg_until(g.v[0], g.v[1], tol=0.0, max_times=1)
+    assert deep.levels == 3 and deep.level_dims == ((16, 16), (8, 8), (4, 4))
+    assert np.isfinite(deep.until.residual) and deep.until.residual < res.until.residual
+
+
+def test_a_plan_without_the_kernels_is_refused(L):
+    import torch
+    from lorastencil_amd import _lib
+
+    plan = L.Plan("star2d1r", (6, 10))
+    assert plan.get_option("cg") == 1 and plan.get_option("mg") == 0
+    x = torch.zeros(L.padded_shape("star2d1r", (6, 10)), dtype=torch.float64, device="cuda")
+    c = torch.zeros(L.padded_shape("star2d1r", (4, 4)), dtype=torch.float64, device="cuda")
+    for call in (lambda: plan.run_mg_until(x, None, tol=1e-9), lambda: plan.mg_restrict(x, c), lambda: plan.mg_prolong_add(c, x),
+                 lambda: plan.prepare_mg()):
+        with pytest.raises(L.LoraError) as e:
+            call()
+        assert e.value.status == _lib.LORA_EUNSUPPORTED
+
+
+def test_nan_in_the_source_is_reported_as_divergence(L):
+    import torch
+
+    shape, dims, w, x, f = small_problem(L)
+    f = f.copy()
+    L.interior(shape, f)[5, 7] = np.nan
+    plan = L.Plan(shape, dims).set_weights(w)
+    g = Grids(L, shape, dims, 240, [x, f])
+    before_x, before_f, halo = g.bits(0), g.bits(1), ~g.interior_mask()
+    res = plan.run_mg_until(g.v[0], g.v[1], tol=1e-9, max_times=5)
+    g.guards("NaN in f")
+    assert res.until.diverged and not res.until.converged and res.until.times_done == 1 and res.until.last.nonfinite > 0
+    assert torch.equal(g.arena.bits(0)[halo], before_x[halo]) and torch.equal(g.arena.bits(1), before_f)
+
+
+def test_run_host_mg_is_the_plan_driver(L):
+    import torch
+
+    from lorastencil_amd import _lib
+
+    shape, dims, w, x, f = small_problem(L)
+    # the host operator builds its plan from the shape's own taps (star2d1r ignores params): integers that sum to 100, so both
+    # sides run in normalised-weights mode, taps / 100 -- point-symmetric, the centre 0.16
+    old = _lib.lib().lora_set_default_normalize(1)
+    try:
+        plan = L.Plan(shape, dims)
+        g = Grids(L, shape, dims, 16, [x, f])
+        res = plan.run_mg_until(g.v[0], g.v[1], tol=0.0, max_times=2)
+        out, hres, info = L.run_host_mg(shape, x, 0.0, source=f, max_times=2)
+    finally:
+        _lib.lib().lora_set_default_normalize(old)
+    assert abs(plan.weights.sum() - 1.0) < 1e-12 and np.isfinite(res.until.residual)
+    assert hres.until.times_done == 2 and hres.levels == res.levels and hres.level_dims == res.level_dims
+    assert np.array_equal(out.view(np.int64), g.v[0].cpu().numpy().view(np.int64))
+    assert info.sweep_seconds > 0 and info.hbm_gbs > 0 and info.steps_per_launch == 1
+
+
+def test_cli_flag_mg(L):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe2, exe3 = (os.path.join(root, "lorastencil_amd", "bin", f"lorastencil_{d}d") for d in (2, 3))
+    run = lambda *a: subprocess.run(list(a), capture_output=True, text=True, timeout=120)
+    r = run(exe2, "star2d1r", "64", "64", "40", "--mg", "--normalize", "--source=point:1", "--until=1e-9")
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0
+    lines = r.stdout.splitlines()
+    assert lines[0] == "INFO: shape = star_2d1r, m = 64, n = 64, times = 40"
+    assert lines[1] == "LoRAStencil(2D star_2d1r): " and lines[2].startswith("Time = ") and lines[3].startswith("GStencil/s = ")
+    assert any(ln.startswith("Multigrid: V(2,2) cycles = ") and ln.endswith("omega = 0.8, levels = 5, coarsest = 4 x 4") for ln in lines)
+    assert any(ln.startswith("Until: times_done = ") and ", converged, residual = " in ln and "checked every 1 steps" in ln for ln in lines)
+    r = run(exe3, "star3d1r", "16", "16", "16", "40", "--mg=1,1", "--normalize", "--until=1e-9", "--check-every=3")
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0
+    assert any(ln.startswith("Multigrid: V(1,1) cycles = ") and ln.endswith("levels = 3, coarsest = 4 x 4 x 4") for ln in r.stdout.splitlines())
+    assert any(", converged, " in ln and "checked every 3 steps" in ln for ln in r.stdout.splitlines())
+    # the reference's integer taps leave no positive diagonal: refused, not run
+    r = run(exe2, "star2d1r", "64", "64", "40", "--mg", "--until=1e-9")
+    assert r.returncode == 1 and "diagonal" in r.stdout
+    # exclusive the way --cg is, and it needs --until
+    for extra in ("--cg", "--chebyshev=0.5", "--implicit=2", "--leapfrog", "--gpus=2", "--grid=1x2"):
+        r = run(exe2, "star2d1r", "64", "64", "40", "--mg", "--normalize", "--until=1e-9", extra)
+        assert r.returncode == 1 and "--mg runs on one GPU" in r.stderr, extra
+    r = run(exe2, "star2d1r", "64", "64", "40", "--mg", "--normalize")
+    assert r.returncode == 1 and "needs --until" in r.stderr
+    r = run(exe2, "star2d1r", "64", "64", "40", "--mg=0,0", "--normalize", "--until=1e-9")
+    assert r.returncode == 1 and "--mg=PRE,POST" in r.stderr
