@@ -200,6 +200,20 @@ struct lora_mg;
 struct lora_mg_result;
 int lora_run_host_mg(int shape, const double *in, const double *source, double *out, const double *params, const struct lora_mg *m,
                      const struct lora_until *u, struct lora_mg_result *r, const int *dims, int quiet, lora_run_info *info);
+/* Multigrid-preconditioned conjugate gradients for u = S(u) + f on host arrays (fp64, 2D and 3D; lora_plan_run_pcg_until in
+ * group B): as lora_run_host_mg, with lora_plan_prepare_pcg and one probe outside the timed region and lora_plan_run_pcg_until
+ * inside it.  `steps` of the printed lines are ITERATIONS; hbm_gbs from the bytes of one iteration: the cycle's tally
+ * (lora_plan_mg_cycle_cost) plus thirteen grids for the CG passes.  LORA_EINVAL also unless m->pre == m->post >= 1. */
+struct lora_pcg_result;
+int lora_run_host_pcg(int shape, const double *in, const double *source, double *out, const double *params, const struct lora_mg *m,
+                      const struct lora_until *u, struct lora_pcg_result *r, const int *dims, int quiet, lora_run_info *info);
+/* lora_run_host_theta with every step's solve preconditioned (lora_plan_run_theta_mg in group B): the hierarchy for the step's
+ * operator is built outside the timed region; the timed region holds the run with its state read-backs every `check_every`
+ * iterations.  hbm_gbs from counted bytes: per step the start, one cycle, the copy and the dot, per iteration a cycle and the
+ * thirteen grids of lora_run_host_pcg. */
+int lora_run_host_theta_mg(int shape, const double *in, const double *source, double *out, const double *params, double theta, double tau,
+                           int steps, int max_iters, double rtol, const struct lora_mg *m, int check_every, const int *dims, int quiet,
+                           lora_run_info *info, struct lora_theta_result *result);
 /* lora_run_info of the last group-A call on this thread (what the CLIs print after the reference's lines). */
 int lora_last_run_info(lora_run_info *info);
 
@@ -831,7 +845,8 @@ int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine
  *   level's right-hand side times c_l; g_0 = fl(c_0 d_f) is formed once per run (d_f == NULL: level 0 has no source).  Level
  *   L is a plain plan with the taps w_L.
  *   One cycle at level l < L:  m->pre applications of the smoothing plan on x_l, with the values lora_plan_run of that plan
- *   gives;  z = one more source sweep of it, rs = fl(z - x_l) on the interior (c_l times the residual);
+ *   gives;  rs = lora_plan_defect(x_l, g_l) with that plan's taps, fl(fl(acc + g_l) - x_l) on the interior: c_l times the
+ *   residual (the same bits as one more source sweep of it and a subtraction);
  *   lora_plan_mg_restrict(rs -> g_(l+1)) with scale = fl(c_(l+1) / c_l), or fl(1 / c_l) when l + 1 == L;  x_(l+1) = 0 over its
  *   whole padded grid;  the cycle at level l + 1;  lora_plan_mg_prolong_add(x_(l+1) -> x_l);  m->post applications.
  *   At level L:  r = g_L, p = r on the interior with a zero halo, rr = lora_plan_dot(r, r).dot, then m->coarse_iters (0: min(64,
@@ -872,11 +887,89 @@ int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
 /* Allocate now what lora_plan_run_mg_until(plan, ..., m, ...) would allocate on first need.  Status as that call's for `m` and
  * the plan; LORA_ENODEVICE without a device. */
 int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m);
-/* What one cycle of the plan's last lora_plan_run_mg_until enqueued, counted while it was enqueued: the number of launches
- * (kernels and memsets; a coarsest-level iteration is five) and the bytes they move when every launch reads and writes each
- * of its grids' interiors once (a zeroing writes the padded grid).  LORA_EINVAL for a null pointer or a plan on which no cycle
- * has run. */
+/* What the last cycle the plan enqueued took (lora_plan_run_mg_until, lora_plan_mg_precondition and the drivers on it), counted
+ * while it was enqueued: the number of launches (kernels and memsets; a coarsest-level iteration is five) and the bytes they
+ * move when every launch reads and writes each of its grids' interiors once (a zeroing writes the padded grid).  LORA_EINVAL
+ * for a null pointer or a plan on which no cycle has run. */
 int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes);
+
+/* ---- multigrid-preconditioned conjugate gradients, also for the implicit stepper's operator (NEW).  fp64, the
+ * plans whose read-only option "mg" reads 1; the read-only option "pcg" reads the same value.  Every operation named below is
+ * its own fp64 rounding; no atomics, fixed fold orders; pieces of at most 16 bytes, nothing outside the padded arrays;
+ * everything ordered on the caller's stream alone; plan-owned memory is allocated on first need or by a prepare call and
+ * written on the stream before it is read. */
+/* The defect of u = S(u) + f in one launch: on every interior cell of [begin, end) d_out = fl(fl(acc + d_f) - d_u); with
+ * d_f == NULL d_out = fl(acc - d_u), and no zero is added.  acc has exactly the bits lora_plan_step_region(plan, d_u, spare,
+ * begin, end) stores.  lora_plan_theta_start without the scale, the second store and the dot: it writes no record and needs no
+ * fold, so it is ASYNCHRONOUS on `stream` like lora_plan_cg_direction and takes a capturing stream.  d_u is read once, halo
+ * included; d_f at the stored cells alone; the halo of d_out is neither read nor written.  Plans and range rules are those of
+ * lora_plan_apply_dot (option "cg" = 1, no source on the plan, 1D included).
+ *   Status, in this order: LORA_EINVAL for a null plan, d_u or d_out, a bad range or begin, any two buffers equal;
+ *   LORA_EUNSUPPORTED for a misaligned buffer, then for a plan whose option "cg" reads 0; LORA_ENODEVICE without a device. */
+int lora_plan_defect(lora_plan *plan, const void *d_u, const void *d_f, void *d_out, int begin, int end, void *stream);
+/* The V-cycle of lora_plan_run_mg_until for A = sigma I - tau S (both finite, tau >= 0, sigma > 0).  The coarse taps stay
+ * lora_mg_coarse_taps of S: A = (sigma - tau) I + tau (I - S), and only the second-order part rescales.  Per level, with w the
+ * level's taps:
+ *     d = fl(sigma - fl(tau w[centre]))   (positive and finite, else LORA_EUNSUPPORTED)
+ *     c = fl(omega / d),  c' = fl(c tau)
+ *     s[t] = fl(c' w[t]) for t != centre,  s[centre] = fl(fl(c' w[centre]) + fl(1 - fl(c sigma)))
+ * A smoothing application is one source sweep with the taps s and the source c b; lora_plan_defect of that plan is c (b - A x);
+ * the restriction scales are lora_plan_run_mg_until's.  On the coarsest level the CG iterations apply
+ * lora_plan_apply_dot_shift(sigma, tau) in place of lora_plan_apply_dot -- unless sigma == tau == 1, where every product with 1
+ * is exact, the formulas give the d, c, s of lora_plan_run_mg_until bit for bit and the plain kernel runs.
+ *   z = M r is ONE such cycle for A z = r from z = 0:  g_0 = fl(c_0 d_r) on the interior;  d_z zeroed over its whole padded
+ *   array (its halo is the zero halo of a correction);  the cycle at level 0 with d_z as the iterate, the level's residual
+ *   lora_plan_defect(x_l, g_l) of the smoothing plan.  ASYNCHRONOUS: no probe, no host wait.  Only interior cells of d_r are read.
+ *   BIT CONTRACT: d_z is what a caller gets by composing the public entries as written: lora_plan_set_weights plans with the
+ *   formulas above, lora_plan_defect, the transfers and the CG entries.
+ *   Status as lora_plan_run_mg_until's for m, the plan, alignment, a caller's buffer that is one of the plan's own, point
+ *   symmetry and the level diagonals; also LORA_EINVAL for d_r == d_z or a bad pair; LORA_ENODEVICE without a device.  The
+ *   hierarchy is kept per plan for one (m->omega, m->max_levels, sigma, tau) at a time and rebuilt when they change;
+ *   lora_plan_mg_cycle_cost afterwards reports this call's launches (the scale, the zeroing and the halo resets included). */
+int lora_plan_mg_precondition(lora_plan *plan, const void *d_r, void *d_z, const lora_mg *m, double sigma, double tau, void *stream);
+/* Preconditioned CG for u = S(u) + f until the TRUE residual is small: A = I - S, M the V-cycle above with sigma = tau = 1.
+ * The plan owns one more grid, z, beside r, p, q and the hierarchy (lora_plan_prepare_pcg allocates all of it).
+ *   Start-up:  r = lora_plan_defect(d_x, d_f);  z = M r;  p = z on the interior, with a zeroed halo;  rz = lora_plan_dot(r, z).dot.
+ *   Iteration:
+ *     pq = lora_plan_apply_dot(p, q).dot;  alpha = rz / pq;  rr' = lora_plan_cg_update(d_x, r, p, q, alpha).dot;
+ *     z = M r;  rz' = lora_plan_dot(r, z).dot;  beta = rz' / rz;  lora_plan_cg_direction(p, z, beta);  rz = rz'
+ *   The scalars stay on the device, one lane behind each fold; the history holds alpha and beta as in lora_plan_run_cg_until.
+ *   Breakdown is sticky: pq not finite or <= 0; rz' not finite or < 0; a non-finite product; rz' == 0 (the residual vanished)
+ *   halts the remaining launches in the same way.  The V-cycle's own launches do not test the halt word and still run after a
+ *   halt: they write only z and the hierarchy's grids.  Every launch that could move d_x, r or p behind the start-up exits
+ *   first, so d_x stays the last good iterate.
+ *   Rounds, probe, stop rule and the fields of r->until are lora_plan_run_cg_until's (check_every even and >= 2; under
+ *   LORA_NORM_MAX one lora_plan_residual_src per round, else a source sweep into q and lora_plan_diff; the state is read back
+ *   in the probe's wait).  lambda_min / lambda_max: the Ritz values of M A from the run's coefficients (lora_cg_spectrum).
+ *   BIT CONTRACT: d_x after k iterations is the host loop over the public entries as written, alpha and beta divided in host
+ *   fp64.
+ *   Status as lora_plan_run_mg_until's, and LORA_EINVAL unless m->pre == m->post >= 1 (the preconditioner must be symmetric;
+ *   lora_plan_mg_precondition itself takes any m).  max_times < check_every returns LORA_OK and touches nothing. */
+typedef struct lora_pcg_result {
+    lora_until_result until;
+    double lambda_min, lambda_max; /* Ritz values of M A from the run's coefficients; NaN if no iteration ran */
+    int breakdown, levels;
+} lora_pcg_result;
+int lora_plan_run_pcg_until(lora_plan *plan, void *d_x, const void *d_f, const lora_mg *m, const lora_until *u, lora_pcg_result *r,
+                            void *stream);
+/* Allocate now what lora_plan_run_pcg_until(plan, ..., m, u with this max_times, ...) would allocate on first need.  Status as
+ * that call's for `m` and the plan; LORA_EINVAL for max_times < 0; LORA_ENODEVICE without a device. */
+int lora_plan_prepare_pcg(lora_plan *plan, const lora_mg *m, int max_times);
+/* lora_plan_run_theta with every step's solve preconditioned: the scheme, the argument rules, the result record and the
+ * per-step stop rule rr' <= fl(rtol2 rr0) (rr = r.r from the update's dot, decided on the device) are that call's;
+ * A = sigma I - tau' S is preconditioned by the hierarchy for (sigma, tau').  Per step:  lora_plan_theta_start into r and z (z is
+ * overwritten next);  z = M r;  p = z with a zero halo;  rz;  then the iterations of lora_plan_run_pcg_until with
+ * lora_plan_apply_dot_shift(sigma, tau').
+ *   A V-cycle cannot exit early, so the run does not enqueue max_iters iterations blindly: after every check_every iterations
+ *   (>= 1, any parity) the driver reads the state back -- one small copy and one stream wait -- and goes on to the next step
+ *   once the step is done.  At most check_every - 1 iterations are enqueued past the one that meets the rule; their CG launches
+ *   exit on `done`, their V-cycles run (DESIGN 3.12 has the cost).
+ *   iterations[s], unconverged_steps, breakdown handling and the final `steady` probe are lora_plan_run_theta's.
+ *   BIT CONTRACT: the host loop over the public entries, with iterations[s] iterations per step.
+ *   Also LORA_EINVAL for a null or bad m, unless m->pre == m->post >= 1, and for check_every < 1; LORA_EUNSUPPORTED as
+ *   lora_plan_mg_precondition for (sigma, tau').  theta == 0 is legal (A = I). */
+int lora_plan_run_theta_mg(lora_plan *plan, void *d_u, const void *d_f, double theta, double tau, int steps, int max_iters, double rtol,
+                           const lora_mg *m, int check_every, int *iterations, lora_theta_result *r, void *stream);
 void lora_plan_destroy(lora_plan *plan);
 
 /* ========================================================================================

@@ -19,6 +19,7 @@ from .ops import (  # noqa: F401
     GridStats,
     LoraError,
     MgResult,
+    PcgResult,
     Plan,
     ThetaResult,
     UntilResult,
@@ -46,6 +47,8 @@ from .ops import (  # noqa: F401
     run_host_chebyshev,
     run_host_leapfrog,
     run_host_mg,
+    run_host_pcg,
+    run_host_theta_mg,
     run_host_theta,
     run_host_until,
     separable_3x3x3,

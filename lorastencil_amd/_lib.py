@@ -112,6 +112,12 @@ class MgResult(ctypes.Structure):
     _fields_ = [("until", UntilResult), ("levels", ctypes.c_int), ("level_dims", (ctypes.c_int * 3) * 16)]
 
 
+class PcgResult(ctypes.Structure):
+    """lora_pcg_result: the until-result counted in iterations, the Ritz values of M A, and the hierarchy's depth."""
+    _fields_ = [("until", UntilResult), ("lambda_min", ctypes.c_double), ("lambda_max", ctypes.c_double), ("breakdown", ctypes.c_int),
+                ("levels", ctypes.c_int)]
+
+
 NORM_MAX, NORM_RMS = 0, 1
 
 _comm_begin_t = ctypes.CFUNCTYPE(ctypes.c_int, _vp)
@@ -301,6 +307,17 @@ SIGNATURES = {
     "lora_plan_mg_cycle_cost": (ctypes.c_int, [_vp, _ip, _dp]),
     "lora_run_host_mg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(MgResult),
                                         _ip, ctypes.c_int, ctypes.POINTER(RunInfo)]),
+    "lora_plan_defect": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "lora_plan_mg_precondition": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Mg), ctypes.c_double, ctypes.c_double, _vp]),
+    "lora_plan_run_pcg_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(PcgResult), _vp]),
+    "lora_plan_prepare_pcg": (ctypes.c_int, [_vp, ctypes.POINTER(Mg), ctypes.c_int]),
+    "lora_plan_run_theta_mg": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                              ctypes.POINTER(Mg), ctypes.c_int, _ip, ctypes.POINTER(ThetaResult), _vp]),
+    "lora_run_host_pcg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(PcgResult),
+                                         _ip, ctypes.c_int, ctypes.POINTER(RunInfo)]),
+    "lora_run_host_theta_mg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_double, ctypes.POINTER(Mg), ctypes.c_int, _ip, ctypes.c_int, ctypes.POINTER(RunInfo),
+                                              ctypes.POINTER(ThetaResult)]),
     "lora_run_host_leapfrog": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int,
                                               ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),

@@ -928,7 +928,7 @@ void release_run_state(lora_plan *plan) {
     torus_drop(plan);
     mg_release(plan);
     for (DeviceGrid *g : {&plan->scratch, &plan->records, &plan->leap[0], &plan->leap[1], &plan->cheb_probe, &plan->cg[0], &plan->cg[1],
-                          &plan->cg[2], &plan->cg_state, &plan->theta_state})
+                          &plan->cg[2], &plan->cg_state, &plan->theta_state, &plan->pcg_z})
         g->release();
 }
 }  // namespace lora

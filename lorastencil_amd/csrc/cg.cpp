@@ -7,6 +7,9 @@
 // theta-scheme steps of du/dt = S(u) + f - u, each a CG solve on sigma I - tau' S started from the level itself, a whole run
 // enqueued with no host wait.  Its entries go through the same CgLaunch as everything above, and so does the coarsest level of
 // a multigrid cycle (cg_fixed_iterations; the driver: mg.cpp).
+//
+// At the end the preconditioned drivers: conjugate gradients with z = M r, M one V-cycle of mg.cpp, for u = S(u) + f
+// and for the stepper's operator, the fused defect launch's public entry, and their host-buffer operators.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,17 +44,20 @@ struct CgLaunch {
     ReduceArgs a;
     int kind = 0, groups = 0;
     long long count = 0;
+    int pcg_cap = -1;  // >= 0: the preconditioned drivers' fold phases (alpha = rz / pq, no beta behind the update), with this history size
     CgLaunch(const Plan &plan, ReduceRecord *rec, hipStream_t stream) : p(plan), records(rec), s(stream) {}
     bool setup(int begin, int end) { return residual_tiles_setup(rt, p, begin, end) && interior_geometry(p, begin, end, a, kind, groups, count); }
     int apply_dot(const void *d_p, void *d_q, CgState *st, int cap) const {
         if (int rc = hip_status(launch_apply_dot(p, rt, static_cast<const double *>(d_p), static_cast<double *>(d_q), st, records, s), "apply_dot launch")) return rc;
-        return hip_status(launch_cg_fold(records, rt.groups, st, st ? CG_FOLD_APPLY : CG_FOLD_PLAIN, cap, s), "fold launch");
+        return hip_status(launch_cg_fold(records, rt.groups, st, st ? (pcg_cap >= 0 ? CG_FOLD_PCG_APPLY : CG_FOLD_APPLY) : CG_FOLD_PLAIN, cap, s),
+                          "fold launch");
     }
     // sigma p - tau S(p) in place of p - S(p): the same tiles, the same fold
     int apply_dot_shift(const void *d_p, void *d_q, double sigma, double tau, CgState *st) const {
         if (int rc = hip_status(launch_apply_dot_shift(p, rt, static_cast<const double *>(d_p), static_cast<double *>(d_q), sigma, tau, st, records, s),
                                 "apply_dot_shift launch"))
             return rc;
+        if (st && pcg_cap >= 0) return hip_status(launch_cg_fold(records, rt.groups, st, CG_FOLD_PCG_APPLY, pcg_cap, s), "fold launch");
         return hip_status(launch_cg_fold(records, rt.groups, st, st ? CG_FOLD_APPLY : CG_FOLD_PLAIN, 0, s), "fold launch");
     }
     // r = p = tau (S(u) + f - u) and the fold of r.r; with a state, the step's start behind it
@@ -67,7 +73,14 @@ struct CgLaunch {
                                                     static_cast<const double *>(d_p), static_cast<const double *>(d_q), alpha, st, records, s),
                                 "cg_update launch"))
             return rc;
+        if (st && pcg_cap >= 0)
+            return hip_status(launch_cg_fold(records, groups, st, ts ? CG_FOLD_PCG_THETA_UPDATE : CG_FOLD_PCG_UPDATE, pcg_cap, s, ts), "fold launch");
         return hip_status(launch_cg_fold(records, groups, st, st ? (ts ? CG_FOLD_THETA_UPDATE : CG_FOLD_UPDATE) : CG_FOLD_PLAIN, cap, s, ts), "fold launch");
+    }
+    // rz = r.z: lora_plan_dot's launches, and behind them the state's (first: CG_FOLD_PCG_RZ0, else beta = rz' / rz)
+    int dot_rz(const void *d_r, const void *d_z, CgState *st, bool first) const {
+        if (int rc = hip_status(launch_reduce_dot(a, kind, groups, d_r, d_z, records, s), "reduction kernel launch")) return rc;
+        return hip_status(launch_cg_fold(records, groups, st, first ? CG_FOLD_PCG_RZ0 : CG_FOLD_PCG_RZ, pcg_cap, s), "fold launch");
     }
     int direction(void *d_p, const void *d_r, double beta, const CgState *st) const {
         return hip_status(launch_cg_pointwise(CG_OP_DIRECTION, a, kind, groups, static_cast<double *>(d_p), nullptr, static_cast<const double *>(d_r),
@@ -87,7 +100,7 @@ struct CgLaunch {
     }
 };
 
-size_t state_bytes(int cap) { return sizeof(CgState) + 2 * sizeof(double) * (size_t) cap; }
+size_t state_bytes(int cap) { return sizeof(CgState) + 2 * sizeof(double) * (size_t) cap + sizeof(PcgState); }  // (engine.h: PcgState)
 
 // the three grids and the state with room for `max_times` coefficients (an earlier, larger history is kept)
 int ensure_cg(lora_plan *plan, int max_times) {
@@ -145,7 +158,7 @@ int ensure_cg_grids(lora_plan *plan) { return ensure_cg(plan, 1); }
 
 // The coarsest level of a multigrid cycle (mg.cpp): the iterations of lora_plan_run_cg_until below, through the same CgLaunch,
 // from a residual the caller has put into the plan's own r -- no source sweep, no probe, no host wait.
-int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, hipStream_t s, long *launches) {
+int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, double sigma, double tau, hipStream_t s, long *launches) {
     const Plan &p = plan->p;
     if (int rc = ensure_cg(plan, 1)) return rc;
     void *d_r = plan->cg[0].ptr, *d_p = plan->cg[1].ptr, *d_q = plan->cg[2].ptr;
@@ -162,8 +175,9 @@ int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, hipStream_t s, lo
     if (int rc = hip_status(launch_copy_interior(p.dtype, p.ndim, p.dims, d_p, pad, d_r, pad, s), "copy launch")) return rc;
     if (int rc = hip_status(launch_reduce_dot(L.a, L.kind, L.groups, d_r, d_r, records, s), "reduction kernel launch")) return rc;
     if (int rc = hip_status(launch_cg_fold(records, L.groups, st, CG_FOLD_START, cap, s), "fold launch")) return rc;
+    const bool shifted = !(sigma == 1.0 && tau == 1.0);  // (1, 1) keeps the plain kernel: the same bits on any data
     for (int i = 0; i < iters; ++i) {
-        if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
+        if (int rc = shifted ? L.apply_dot_shift(d_p, d_q, sigma, tau, st) : L.apply_dot(d_p, d_q, st, cap)) return rc;
         if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
         if (int rc = L.direction(d_p, d_r, 0.0, st)) return rc;
     }
@@ -171,6 +185,49 @@ int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, hipStream_t s, lo
     return LORA_OK;
 }
 
+int defect_whole(const Plan &p, const double *d_u, const double *d_f, double *d_out, hipStream_t s) {
+    if (!has_cg(p)) return no_cg_kernels(p);
+    ResidualTiles rt;
+    if (!residual_tiles_setup(rt, p, 0, p.dims[0])) return LORA_EINVAL;
+    return hip_status(launch_defect(p, rt, d_u, d_f, d_out, s), "defect launch");
+}
+
+// ---- the preconditioned drivers' shared pieces ------------------------------------------------------------------
+namespace {
+
+const int kPads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+
+// the drivers need a symmetric preconditioner: as many smoothing applications behind the coarse correction as before it
+bool asymmetric(const lora_mg *m) { return m->pre != m->post || m->pre < 1; }
+
+// whether a caller's buffer is one of the plan's own
+bool owned(const lora_plan *plan, const void *buf) {
+    if (!buf) return false;
+    for (const void *own : {plan->cg[0].ptr, plan->cg[1].ptr, plan->cg[2].ptr, plan->cg_state.ptr, plan->theta_state.ptr, plan->pcg_z.ptr})
+        if (own == buf) return true;
+    return mg_owns(plan, buf);
+}
+
+// z = M r, p = z on the interior (the halo of p is the run's zero halo), rz = r.z
+int pcg_first_direction(lora_plan *plan, const CgLaunch &L, const lora_mg *m, double sigma, double tau, CgState *st) {
+    const Plan &p = plan->p;
+    double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr);
+    double *d_z = static_cast<double *>(plan->pcg_z.ptr);
+    if (int rc = mg_precondition(plan, d_r, d_z, m, sigma, tau, L.s)) return rc;
+    if (int rc = hip_status(launch_copy_interior(p.dtype, p.ndim, p.dims, d_p, kPads[p.ndim - 1], d_z, kPads[p.ndim - 1], L.s), "copy launch")) return rc;
+    return L.dot_rz(d_r, d_z, st, true);
+}
+
+// behind an iteration's update: z = M r, rz' = r.z, beta = rz' / rz, p = z + beta p
+int pcg_next_direction(lora_plan *plan, const CgLaunch &L, const lora_mg *m, double sigma, double tau, CgState *st) {
+    double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr);
+    double *d_z = static_cast<double *>(plan->pcg_z.ptr);
+    if (int rc = mg_precondition(plan, d_r, d_z, m, sigma, tau, L.s)) return rc;
+    if (int rc = L.dot_rz(d_r, d_z, st, false)) return rc;
+    return L.direction(d_p, d_z, 0.0, st);
+}
+
+}  // namespace
 }  // namespace lora
 
 using lora::CgLaunch;
@@ -418,6 +475,24 @@ int lora_plan_theta_start(lora_plan *plan, const void *d_u, const void *d_f, dou
     return L.result(out_rr);
 }
 
+int lora_plan_defect(lora_plan *plan, const void *d_u, const void *d_f, void *d_out, int begin, int end, void *stream) {
+    if (!plan || !d_u || !d_out) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    const int some = lora::reduction_range(p, begin, end);
+    if (some < 0 || begin % lora::region_granularity(p)) return LORA_EINVAL;
+    if (d_u == d_out || d_f == d_u || d_f == d_out) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_u, d_out)) return rc;
+    if (lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
+    if (lora_device_count() <= 0) return lora::no_device();
+    if (!some) return LORA_OK;
+    lora::ResidualTiles rt;
+    if (!lora::residual_tiles_setup(rt, p, begin, end)) return LORA_EINVAL;
+    return lora::hip_status(lora::launch_defect(p, rt, static_cast<const double *>(d_u), static_cast<const double *>(d_f),
+                                                static_cast<double *>(d_out), static_cast<hipStream_t>(stream)),
+                            "defect launch");
+}
+
 int lora_plan_prepare_theta(lora_plan *plan, int steps) {
     if (!plan || steps < 0) return LORA_EINVAL;
     if (!lora::has_cg(plan->p)) return lora::no_cg_kernels(plan->p);
@@ -524,6 +599,246 @@ int lora_run_host_theta(int shape, const double *in, const double *source, doubl
     if ((rc = lora::hip_status(hipMemcpy(out, d_u, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
     // per step: u (and f) read, r and p written; per iteration the eleven grids of a CG iteration (lora_run_host_cg)
     const double per_step = (source ? 4.0 : 3.0) + (steps > 0 ? 11.0 * (double) result->iterations_total / steps : 0.0);
+    return g.finish(steps, per_step, 1, quiet, info);
+}
+
+// ---- multigrid-preconditioned conjugate gradients and the implicit stepper on them ------------------------------
+int lora_plan_prepare_pcg(lora_plan *plan, const lora_mg *m, int max_times) {
+    if (!plan || !m || max_times < 0 || lora::mg_bad(m, 1.0, 1.0) || lora::asymmetric(m)) return LORA_EINVAL;
+    if (int rc = lora::mg_admit(plan, m, 1.0, 1.0, nullptr)) return rc;
+    if (lora_device_count() <= 0) return lora::no_device();
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    if (int rc = lora::ensure_cg(plan, max_times)) return rc;
+    if (!plan->pcg_z.ensure(lora_plan_padded_bytes(plan))) return LORA_ENOMEM;
+    return lora::mg_prepare(plan, m, 1.0, 1.0);
+}
+
+int lora_plan_run_pcg_until(lora_plan *plan, void *d_x, const void *d_f, const lora_mg *m, const lora_until *u, lora_pcg_result *r,
+                            void *stream) {
+    if (!plan || !d_x || !m || !u || !r || lora::bad_until(u) || lora::mg_bad(m, 1.0, 1.0) || lora::asymmetric(m) || d_f == d_x) return LORA_EINVAL;
+    if (lora::misaligned(d_x) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    int levels = 0;
+    if (int rc = lora::mg_admit(plan, m, 1.0, 1.0, &levels)) return rc;
+    const Plan &p = plan->p;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_x, d_x, s)) return rc;
+    *r = {{0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}}, lora::kNaN, lora::kNaN, 0, levels};
+    if (u->max_times < u->check_every) return LORA_OK;
+    if (int rc = lora::ensure_cg(plan, u->max_times)) return rc;
+    if (!plan->pcg_z.ensure(lora_plan_padded_bytes(plan))) return LORA_ENOMEM;
+    if (int rc = lora::mg_prepare(plan, m, 1.0, 1.0)) return rc;
+    if (lora::owned(plan, d_x) || lora::owned(plan, d_f)) return LORA_EINVAL;
+    double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr), *d_q = static_cast<double *>(plan->cg[2].ptr);
+    lora::CgState *st = static_cast<lora::CgState *>(plan->cg_state.ptr);
+    const int cap = plan->cg_cap;
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
+    L.pcg_cap = cap;
+
+    // r = fl(fl(S(x) + f) - x) in one launch, z = M r, p = z with a zero halo, rz = r.z -- all on this stream
+    if (int rc = lora::hip_status(lora::launch_cg_fold(records, 0, st, lora::CG_FOLD_PCG_INIT, cap, s), "fold launch")) return rc;
+    if (int rc = lora::defect_whole(p, static_cast<const double *>(d_x), static_cast<const double *>(d_f), d_r, s)) return rc;
+    if (int rc = lora::hip_status(lora::launch_halo(p, d_p, nullptr, lora::HALO_ZERO, s), "halo launch")) return rc;
+    if (int rc = lora::pcg_first_direction(plan, L, m, 1.0, 1.0, st)) return rc;
+
+    Plan with_f = p;  // the sweep of the two-pass probe (as lora_plan_run_cg_until)
+    with_f.source = d_f;
+    const lora::Apps whole = {1, 0, p.dims[0]};
+    const bool fused = u->norm == LORA_NORM_MAX;
+    lora::CgState now = {};
+    lora_until_result &ur = r->until;
+    while (ur.times_done + u->check_every <= u->max_times) {
+        for (int i = 0; i < u->check_every; ++i) {
+            if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
+            if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
+            if (int rc = lora::pcg_next_direction(plan, L, m, 1.0, 1.0, st)) return rc;
+        }
+        // the scalars come back in the probe's wait
+        if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
+        if (fused) {
+            if (int rc = lora::residual_whole(plan, d_x, d_f, &ur.last, s)) return rc;
+        } else {
+            if (int rc = lora::launch_apps(with_f, whole, d_x, d_q, s)) return rc;
+            if (int rc = lora::diff_whole(plan, d_q, d_x, &ur.last, s)) return rc;
+        }
+        ur.times_done = (int) now.iteration;
+        bool stop = lora::until_decide(u, &ur);
+        if (now.breakdown) {
+            r->breakdown = 1;
+            if (!ur.converged) ur.diverged = 1;
+            stop = true;
+        }
+        if (stop) break;
+    }
+    const int n = ur.times_done;
+    if (n > 0) {
+        std::vector<double> hist(2 * (size_t) n);
+        const double *d_hist = reinterpret_cast<const double *>(st + 1);
+        if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * n, hipMemcpyDeviceToHost, s), "history download")) return rc;
+        if (n > 1)
+            if (int rc = lora::hip_status(hipMemcpyAsync(hist.data() + n, d_hist + cap, sizeof(double) * (n - 1), hipMemcpyDeviceToHost, s), "history download"))
+                return rc;
+        if (int rc = lora::hip_status(hipStreamSynchronize(s), "history download")) return rc;
+        lora_cg_spectrum(hist.data(), hist.data() + n, n, &r->lambda_min, &r->lambda_max);
+    }
+    return LORA_OK;
+}
+
+int lora_plan_run_theta_mg(lora_plan *plan, void *d_u, const void *d_f, double theta, double tau, int steps, int max_iters, double rtol,
+                           const lora_mg *m, int check_every, int *iterations, lora_theta_result *r, void *stream) {
+    if (!plan || !d_u || !r || !m || d_f == d_u) return LORA_EINVAL;
+    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
+        !std::isfinite(rtol) || check_every < 1)
+        return LORA_EINVAL;
+    // the operator of the step and the stop rule's factor, each operation its own rounding
+    const double tt = theta * tau, sigma = 1.0 + tt, rtol2 = rtol * rtol;
+    if (lora::mg_bad(m, sigma, tt) || lora::asymmetric(m)) return LORA_EINVAL;
+    if (lora::misaligned(d_u) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    if (int rc = lora::mg_admit(plan, m, sigma, tt, nullptr)) return rc;
+    const Plan &p = plan->p;
+    *r = {0, 0, 0, 0, 0, lora::kNaN, lora::kNaN, {0.0, 0.0, 0.0, -1, 0, 0}};
+    if (steps == 0) return LORA_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lora::admit_reduction(d_u, d_u, s)) return rc;
+    if (int rc = lora::ensure_theta(plan, steps)) return rc;
+    if (!plan->pcg_z.ensure(lora_plan_padded_bytes(plan))) return LORA_ENOMEM;
+    if (int rc = lora::mg_prepare(plan, m, sigma, tt)) return rc;
+    if (lora::owned(plan, d_u) || lora::owned(plan, d_f)) return LORA_EINVAL;
+    double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr), *d_q = static_cast<double *>(plan->cg[2].ptr);
+    double *d_z = static_cast<double *>(plan->pcg_z.ptr);
+    lora::CgState *st = static_cast<lora::CgState *>(plan->cg_state.ptr);
+    lora::ThetaState *ts = static_cast<lora::ThetaState *>(plan->theta_state.ptr);
+    lora::ReduceRecord *records = nullptr;
+    if (int rc = lora::reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
+    L.pcg_cap = plan->cg_cap;
+
+    if (int rc = lora::hip_status(lora::launch_cg_fold(records, 0, st, lora::CG_FOLD_THETA_INIT, plan->theta_cap, s, ts, rtol2, max_iters), "fold launch"))
+        return rc;
+    if (int rc = lora::hip_status(lora::launch_halo(p, d_p, nullptr, lora::HALO_ZERO, s), "halo launch")) return rc;
+    lora::CgState now = {};
+    for (int step = 0; step < steps; ++step) {
+        if (int rc = L.theta_start(d_u, d_f, tau, d_r, d_z, st, ts)) return rc;
+        if (int rc = lora::pcg_first_direction(plan, L, m, sigma, tt, st)) return rc;
+        // a V-cycle cannot exit early, so the step is enqueued in rounds of check_every iterations with the state read back between
+        for (int done = 0; done < max_iters;) {
+            const int round = check_every < max_iters - done ? check_every : max_iters - done;
+            for (int i = 0; i < round; ++i) {
+                if (int rc = L.apply_dot_shift(d_p, d_q, sigma, tt, st)) return rc;
+                if (int rc = L.update(d_u, d_r, d_p, d_q, 0.0, st, 0, ts)) return rc;
+                if (int rc = lora::pcg_next_direction(plan, L, m, sigma, tt, st)) return rc;
+            }
+            done += round;
+            if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
+            if (int rc = lora::hip_status(hipStreamSynchronize(s), "state download")) return rc;
+            if (now.breakdown) break;  // the step is done, or the run broke down
+        }
+        if (now.breakdown & lora::CG_HALT_BREAKDOWN) break;
+    }
+    lora::ThetaState tnow = {};
+    std::vector<long long> hist((size_t) steps);
+    if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
+    if (int rc = lora::hip_status(hipMemcpyAsync(&tnow, ts, sizeof tnow, hipMemcpyDeviceToHost, s), "state download")) return rc;
+    if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), ts + 1, sizeof(long long) * steps, hipMemcpyDeviceToHost, s), "history download"))
+        return rc;
+    if (int rc = lora::residual_whole(plan, d_u, d_f, &r->steady, s)) return rc;
+    r->steps_done = (int) tnow.steps_done;
+    r->breakdown = (now.breakdown & lora::CG_HALT_BREAKDOWN) ? 1 : 0;
+    r->unconverged_steps = (int) tnow.unconverged;
+    r->last_rr0 = tnow.rr0;
+    r->last_rr = now.rr;
+    for (int step = 0; step < steps; ++step) {
+        const int k = step < r->steps_done ? (int) hist[step] : (step == r->steps_done ? (int) now.iteration : 0);
+        if (iterations) iterations[step] = k;
+        if (step < r->steps_done) {
+            r->iterations_total += k;
+            if (k > r->iterations_max) r->iterations_max = k;
+        }
+    }
+    return LORA_OK;
+}
+
+int lora_run_host_pcg(int shape, const double *in, const double *source, double *out, const double *params, const lora_mg *m,
+                      const lora_until *u, lora_pcg_result *r, const int *dims, int quiet, lora_run_info *info) {
+    if (!in || !out || !dims || !m || !u || !r || lora::bad_until(u) || lora::mg_bad(m, 1.0, 1.0) || lora::asymmetric(m)) return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("a preconditioned conjugate-gradient run (its source is an argument)")) return rc;
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
+    if (rc != LORA_OK) return rc;
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
+    void *d_x = g.b[0], *d_f = g.b[1];
+    if ((rc = lora::hip_status(hipMemcpy(d_x, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if (source)
+        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    // set-up outside the timed region: the grids, the state, the hierarchy, and one probe as a warm-up (it writes no grid)
+    if ((rc = lora_plan_prepare_pcg(plan, m, u->max_times))) return rc;
+    lora_grid_diff warm;
+    if ((rc = lora_plan_residual_src(plan, d_x, d_f, 0, 0, &warm, nullptr))) return rc;
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
+
+    g.tic();
+    if ((rc = lora_plan_run_pcg_until(plan, d_x, d_f, m, u, r, g.s))) return rc;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();  // the start-up, the iterations and their probes
+    if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    // per iteration: the cycle's tally in grids of the fine level, and the CG passes -- p read, q written; x, r, p, q read, x, r
+    // written; r, z read; z, p read, p written
+    long launches = 0;
+    double cycle_bytes = 0.0;
+    lora::mg_cost(plan, &launches, &cycle_bytes);
+    return g.finish(r->until.times_done, cycle_bytes / (8.0 * g.points) + 13.0, 1, quiet, info);
+}
+
+int lora_run_host_theta_mg(int shape, const double *in, const double *source, double *out, const double *params, double theta, double tau,
+                           int steps, int max_iters, double rtol, const lora_mg *m, int check_every, const int *dims, int quiet,
+                           lora_run_info *info, lora_theta_result *result) {
+    if (!in || !out || !dims || !result || !m) return LORA_EINVAL;
+    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
+        !std::isfinite(rtol) || check_every < 1)
+        return LORA_EINVAL;
+    const double tt = theta * tau, sigma = 1.0 + tt;
+    if (lora::mg_bad(m, sigma, tt) || lora::asymmetric(m)) return LORA_EINVAL;
+    if (int rc = lora::default_source_refused("an implicit run (its source is an argument)")) return rc;
+    lora::HostRun g;
+    int rc = g.open(shape, LORA_F64, dims, params);
+    if (rc != LORA_OK) return rc;
+    lora_plan *plan = g.plan;
+    const size_t bytes = g.bytes;
+    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
+    void *d_u = g.b[0], *d_f = g.b[1];
+    if ((rc = lora::hip_status(hipMemcpy(d_u, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    if (source)
+        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
+    // set-up outside the timed region: the plan's grids and states, the hierarchy for (sigma, tau'), and one warm-up application
+    // into the plan's own q
+    if ((rc = lora::mg_admit(plan, m, sigma, tt, nullptr))) return rc;
+    if ((rc = lora_plan_prepare_theta(plan, steps))) return rc;
+    if (!plan->pcg_z.ensure(bytes)) return LORA_ENOMEM;
+    if ((rc = lora::mg_prepare(plan, m, sigma, tt))) return rc;
+    lora_grid_dot warm;
+    if ((rc = lora_plan_apply_dot_shift(plan, d_u, plan->cg[2].ptr, 1.0, 1.0, 0, 0, &warm, nullptr))) return rc;
+    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
+    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
+
+    g.tic();
+    if ((rc = lora_plan_run_theta_mg(plan, d_u, d_f, theta, tau, steps, max_iters, rtol, m, check_every, nullptr, result, g.s))) return rc;
+    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
+    g.toc();  // every step's start, cycles and iterations, the state read-backs, and the steady-state probe
+    if ((rc = lora::hip_status(hipMemcpy(out, d_u, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    // per step: u (and f) read, r and z written, one cycle, the copy and the dot; per iteration a cycle and the thirteen grids of
+    // lora_run_host_pcg (the iterations enqueued past a step's last are not counted)
+    long launches = 0;
+    double cycle_bytes = 0.0;
+    lora::mg_cost(plan, &launches, &cycle_bytes);
+    const double cycle = cycle_bytes / (8.0 * g.points);
+    const double per_step = (source ? 4.0 : 3.0) + cycle + 4.0 + (steps > 0 ? (cycle + 13.0) * (double) result->iterations_total / steps : 0.0);
     return g.finish(steps, per_step, 1, quiet, info);
 }
 

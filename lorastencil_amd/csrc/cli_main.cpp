@@ -36,6 +36,12 @@
 //                      2,2; damped Jacobi with omega = 0.8, CG on the coarsest level): needs --until=TOL, time_size is the cap in
 //                      CYCLES, --check-every=N may be any N >= 1 (default 1); f from --source= when given; one GPU, fp64.  The
 //                      taps must leave 1 - w[centre] > 0 on every level: the reference's integer tables need --normalize
+//   --pcg[=N]          (lorastencil_2d, lorastencil_3d) solve u = S(u) + f by conjugate gradients preconditioned with one V(N,N)
+//                      cycle (lora_run_host_pcg; default N = 2): needs --until=TOL, time_size is the cap in ITERATIONS,
+//                      --check-every=N even (default 2); what --mg excludes, and --mg itself
+//   --precond=mg[:N]   (lorastencil_2d, lorastencil_3d, with --implicit=TAU) every step's solve preconditioned with one V(N,N)
+//                      cycle for the step's operator (lora_run_host_theta_mg; default N = 2); the state is read back every
+//                      --check-every=N iterations (any N >= 1, default 2)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -162,7 +168,8 @@ int main(int argc, char *argv[]) {
     double chebyshev_rho = 0.0;
     bool leap3 = false;
     bool cg = false;
-    bool mg = false, check_every_given = false;
+    bool mg = false, check_every_given = false, pcg = false, precond = false;
+    int pcg_smooth = 2, precond_smooth = 2;
     lora_mg cycle = {2, 2, 0.8, 0, 0};
     bool implicit = false, implicit_option = false;
     double implicit_tau = 0.0, implicit_theta = 1.0, implicit_rtol = 1e-8;
@@ -235,6 +242,26 @@ int main(int argc, char *argv[]) {
                 if (std::sscanf(a.c_str() + 5, "%d,%d%n", &cycle.pre, &cycle.post, &used) != 2 || a.c_str()[5 + used] != '\0' || cycle.pre < 0 ||
                     cycle.post < 0 || cycle.pre + cycle.post < 1) {
                     std::cerr << "Invalid argument: --mg=PRE,POST needs two non-negative integers, not both zero.\n";
+                    return 1;
+                }
+            }
+        }
+        else if ((a == "--pcg" || a.rfind("--pcg=", 0) == 0) && kDim >= 2) {
+            pcg = true;
+            if (a.size() > 5) {
+                int used = 0;
+                if (std::sscanf(a.c_str() + 6, "%d%n", &pcg_smooth, &used) != 1 || a.c_str()[6 + used] != '\0' || pcg_smooth < 1) {
+                    std::cerr << "Invalid argument: --pcg=N needs a positive integer.\n";
+                    return 1;
+                }
+            }
+        }
+        else if ((a == "--precond=mg" || a.rfind("--precond=mg:", 0) == 0) && kDim >= 2) {
+            precond = true;
+            if (a.size() > 12) {
+                int used = 0;
+                if (std::sscanf(a.c_str() + 13, "%d%n", &precond_smooth, &used) != 1 || a.c_str()[13 + used] != '\0' || precond_smooth < 1) {
+                    std::cerr << "Invalid argument: --precond=mg:N needs a positive integer.\n";
                     return 1;
                 }
             }
@@ -342,7 +369,12 @@ int main(int argc, char *argv[]) {
         }
     }
 
-    if (!mg && (how.check_every < 2 || how.check_every % 2)) {  // (a multigrid run counts cycles: any N >= 1)
+    if (precond && !implicit) {
+        std::cerr << "--precond=mg preconditions the solves of an implicit run: only with --implicit=TAU\n";
+        return 1;
+    }
+    if ((pcg || precond) && !check_every_given) how.check_every = 2;
+    if (!mg && !precond && (how.check_every < 2 || how.check_every % 2)) {  // (a multigrid run counts cycles, a preconditioned step reads back: any N >= 1)
         std::cerr << "Invalid argument: --check-every=N needs a positive even integer.\n";
         return 1;
     }
@@ -355,6 +387,14 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     if (mg && !check_every_given) how.check_every = 1;
+    if (pcg && (mg || cg || chebyshev || implicit || leapfrog || gpus_given || grid[0] > 0 || check || bf16)) {
+        std::cerr << "--pcg runs on one GPU in fp64 against its own residual: not with --mg, --cg, --chebyshev, --implicit, --leapfrog, --gpus, --grid, --check or --dtype=bf16\n";
+        return 1;
+    }
+    if (pcg && !until) {
+        std::cerr << "--pcg solves until the residual is small: it needs --until=TOL (time_size is the cap, in iterations)\n";
+        return 1;
+    }
 
     if (implicit && (cg || chebyshev || leapfrog || until || gpus_given || grid[0] > 0 || check || bf16)) {
         std::cerr << "--implicit runs a fixed number of implicit steps on one GPU in fp64: not with --cg, --chebyshev, --leapfrog, --until, --gpus, --grid, --check or --dtype=bf16\n";
@@ -446,7 +486,7 @@ int main(int argc, char *argv[]) {
             for (int i = 0; i < dims[0]; ++i)
                 for (int j = 0; j < (kDim > 1 ? dims[1] : 1); ++j)
                     for (int k = 0; k < (kDim > 2 ? dims[2] : 1); ++k) at(i, j, k) = source_value;
-        if (!chebyshev && !cg && !implicit && !mg) lora_set_default_source(source.data());  // (a Chebyshev, CG, multigrid or implicit run takes its source as an argument)
+        if (!chebyshev && !cg && !implicit && !mg && !pcg) lora_set_default_source(source.data());  // (a Chebyshev, CG, multigrid or implicit run takes its source as an argument)
     }
 
     if (check && (custom_bc || normalize)) {
@@ -465,7 +505,26 @@ int main(int argc, char *argv[]) {
     lora_cg_result solved = {};
     lora_theta_result stepped = {};
     lora_mg_result cycled = {};
-    if (mg) {
+    lora_pcg_result pcged = {};
+    if (pcg) {
+        // the input is the start iterate, its halo the boundary values; time_size is the cap in iterations
+        how.max_times = times;
+        cycle.pre = cycle.post = pcg_smooth;
+        const int rc = lora_run_host_pcg(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, &cycle, &how, &pcged, dims, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+        reached = pcged.until;
+    } else if (implicit && precond) {
+        cycle.pre = cycle.post = precond_smooth;
+        const int rc = lora_run_host_theta_mg(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, implicit_theta,
+                                              implicit_tau, times, implicit_iters, implicit_rtol, &cycle, how.check_every, dims, 0, nullptr, &stepped);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
+    } else if (mg) {
         // the input is the start iterate, its halo the boundary values; time_size is the cap in cycles; the operator prints the reference's three lines
         how.max_times = times;
         const int rc = lora_run_host_mg(shape, matrix.data(), source_kind ? source.data() : nullptr, output.data(), params, &cycle, &how, &cycled, dims, 0, nullptr);
@@ -580,6 +639,13 @@ int main(int argc, char *argv[]) {
                     "steady residual = %g (max |S(u) + f - u|)\n",
                     implicit_theta, implicit_tau, stepped.steps_done, stepped.breakdown ? ", broke down" : "", stepped.iterations_total,
                     stepped.iterations_max, implicit_iters, implicit_rtol, stepped.unconverged_steps, stepped.steady.max_abs);
+    if (extra && implicit && precond)
+        std::printf("Preconditioner: one V(%d,%d) cycle a solve, omega = %g, state read back every %d iterations\n", precond_smooth, precond_smooth,
+                    cycle.omega, how.check_every);
+    if (extra && pcg)
+        std::printf("Preconditioned conjugate gradients on I - S: V(%d,%d), omega = %g, levels = %d, iterations = %d%s, lambda(M A) in [%g, %g]\n",
+                    pcg_smooth, pcg_smooth, cycle.omega, pcged.levels, reached.times_done, pcged.breakdown ? ", broke down" : "", pcged.lambda_min,
+                    pcged.lambda_max);
     if (extra && chebyshev) std::printf("Chebyshev: u(k+1) = w(k+1) (S(u(k)) + f) + (1 - w(k+1)) u(k-1), rho = %g, steps = %d\n", chebyshev_rho, reached.times_done);
     if (extra && cg)
         std::printf("Conjugate gradients on I - S: iterations = %d%s, rho_estimate = %.17g (lambda in [%g, %g])\n", reached.times_done,
@@ -589,7 +655,7 @@ int main(int argc, char *argv[]) {
         for (int d = 0; d < kDim; ++d) std::printf("%s%d", d ? " x " : " ", cycled.levels > 0 ? cycled.level_dims[cycled.levels - 1][d] : 0);
         std::printf("\n");
     }
-    if (extra && until && (chebyshev || cg || mg))
+    if (extra && until && (chebyshev || cg || mg || pcg))
         std::printf("Until: times_done = %d, %s, residual = %g (max |S(u) + f - u|, tol %g, checked every %d steps)\n", reached.times_done,
                     reached.converged ? "converged" : (reached.diverged ? "diverged" : "reached the cap"), reached.residual, how.tol,
                     how.check_every);
@@ -600,7 +666,7 @@ int main(int argc, char *argv[]) {
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
     if (extra && source_kind)
-        std::printf(implicit ? "Source: f = %g %s (du/dt = S(u) + f - u)\n" : chebyshev || cg || mg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
+        std::printf(implicit ? "Source: f = %g %s (du/dt = S(u) + f - u)\n" : chebyshev || cg || mg || pcg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {
         lora_run_info ri;
         if (lora_last_run_info(&ri) == LORA_OK && ri.sweep_seconds > 0) {

@@ -264,8 +264,18 @@ enum CgOp { CG_OP_UPDATE = 0, CG_OP_DIRECTION = 1, CG_OP_START = 2 };
 // start launch's records, clears `done` and the step's iteration count, thresh = fl(rtol2 rr0), done at once if rr0 == 0;
 // THETA_UPDATE is UPDATE followed by the stop rule (rr' <= thresh, or the step's max_iters-th iteration) and the step's
 // entry in the history
+// the preconditioned drivers' (mg.cpp), whose rz = r.z lives in the PcgState behind the history while CgState::rr
+// stays r.r: PCG_INIT resets the CgState at the head of a run (no records read); PCG_RZ0 takes rz from the record lora_plan_dot's
+// fold left; PCG_APPLY is APPLY with alpha = rz / pq; PCG_UPDATE is UPDATE without beta (rr, the count, alpha into the history),
+// PCG_THETA_UPDATE the same followed by the stepper's stop rule; PCG_RZ takes rz' from lora_plan_dot's record: beta = rz' / rz
+// into the state and the history entry of the iteration just applied, rz = rz'
 enum CgFold { CG_FOLD_PLAIN = 0, CG_FOLD_START = 1, CG_FOLD_APPLY = 2, CG_FOLD_UPDATE = 3, CG_FOLD_THETA_INIT = 4, CG_FOLD_THETA_START = 5,
-              CG_FOLD_THETA_UPDATE = 6 };
+              CG_FOLD_THETA_UPDATE = 6, CG_FOLD_PCG_INIT = 7, CG_FOLD_PCG_RZ0 = 8, CG_FOLD_PCG_APPLY = 9, CG_FOLD_PCG_UPDATE = 10,
+              CG_FOLD_PCG_THETA_UPDATE = 11, CG_FOLD_PCG_RZ = 12 };
+// The preconditioned drivers' scalar beside the CgState: in the same allocation, behind the `cap` alphas and `cap` betas.
+struct PcgState {
+    double rz, spare;  // r.z of the current residual
+};
 // The stepper's scalars beside the CgState, resident on the device; behind them in the same allocation the per-step history:
 // `cap` iteration counts (long long), then `cap` final rr (double).
 struct ThetaState {
@@ -292,6 +302,8 @@ hipError_t launch_apply_dot_shift(const Plan &p, const ResidualTiles &rt, const 
 // r = p = fl(tau fl(fl(sweep(u) + f) - u)) (f == nullptr: no addition) on those cells and the records of dot(r, r) (no fold)
 hipError_t launch_theta_start(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double tau, double *d_r,
                               double *d_p, const CgState *st, ReduceRecord *partial, hipStream_t s);
+// out = fl(fl(sweep(u) + f) - u) (f == nullptr: no addition) on those cells: no record, no fold (lora_plan_defect)
+hipError_t launch_defect(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double *d_out, hipStream_t s);
 
 // ---- geometric multigrid (kernels_mg.hip; host side: mg.cpp) ------------------------------------------------------
 // The extents of the next coarser grid (lora_mg_coarse_dims): LORA_OK, LORA_EUNSUPPORTED for 1D or an extent below 4.
@@ -315,11 +327,26 @@ hipError_t launch_mg_scale(int ndim, const int *dims, double *d_a, const double 
 // cg.cpp: the coarsest level of a cycle.  `iters` CG iterations on A = I - S of `plan` from d_x (whose halo is zero) with the
 // first residual in the plan's own r grid (plan->cg[0], written by the caller): p = r with a zero halo, rr = r.r, then the
 // iterations of lora_plan_run_cg_until through the same launches, no probe and no host wait.  *launches += what it enqueued.
-int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, hipStream_t s, long *launches);
+// With (sigma, tau) other than (1, 1) the operator is sigma I - tau S: apply_dot_shift in place of apply_dot.
+int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, double sigma, double tau, hipStream_t s, long *launches);
+// cg.cpp: the fused defect launch over the whole interior of `p` (a plan without a source; f may be nullptr) -- what
+// lora_plan_defect enqueues, for the V-cycle's internal plans
+int defect_whole(const Plan &p, const double *d_u, const double *d_f, double *d_out, hipStream_t s);
 int ensure_cg_grids(lora_plan *plan);  // cg.cpp: the plan's three CG grids and its state (lora_plan_prepare_cg's, unchecked)
 int dirichlet_run_launches(lora_plan *plan, int times);  // capi.cpp: the launches of lora_plan_run(times) under the Dirichlet boundary, no graph
 struct MgHierarchy;                    // mg.cpp: the levels a plan owns for lora_plan_run_mg_until
 void mg_release(lora_plan *plan);      // mg.cpp: frees them (release_run_state)
+// mg.cpp, for the preconditioned drivers of cg.cpp.  mg_admit: what lora_plan_mg_precondition refuses before a
+// device is asked for (a bad `m` or pair: LORA_EINVAL; the plan, point symmetry, the level diagonals: LORA_EUNSUPPORTED);
+// *levels = the depth of the hierarchy.  mg_prepare: the hierarchy for (m, sigma, tau) with every grid a cycle needs.
+// mg_precondition: z = M r enqueued on `s`, nothing checked.  mg_owns: whether `buf` is one of the hierarchy's grids.
+// mg_cost: the launches and bytes of the last cycle enqueued.
+bool mg_bad(const lora_mg *m, double sigma, double tau);  // what mg_admit answers with LORA_EINVAL
+int mg_admit(const lora_plan *plan, const lora_mg *m, double sigma, double tau, int *levels);
+int mg_prepare(lora_plan *plan, const lora_mg *m, double sigma, double tau);
+int mg_precondition(lora_plan *plan, const double *d_r, double *d_z, const lora_mg *m, double sigma, double tau, hipStream_t s);
+bool mg_owns(const lora_plan *plan, const void *buf);
+void mg_cost(const lora_plan *plan, long *launches, double *bytes);
 
 // ---- sweeps with a source term, out = fl(acc + f) (kernels_step.hip: one application; kernels_2d_step2.hip: two, 2D) -------
 // Plans whose `source` is set; the launch dispatcher picks them, nothing else does.
@@ -495,4 +522,5 @@ struct lora_plan {
     lora::DeviceGrid theta_state;   // lora_plan_run_theta: its ThetaState and, behind it, the history of theta_cap steps
     int theta_cap = 0;
     lora::MgHierarchy *mg = nullptr;  // lora_plan_run_mg_until: the level plans and their grids (mg.cpp; freed by mg_release)
+    lora::DeviceGrid pcg_z;           // lora_plan_run_pcg_until, lora_plan_run_theta_mg: z = M r, beside the CG set
 };

@@ -17,6 +17,7 @@
 //                 update of the device-resident scalars (CgState: alpha = rr / pq, beta = rr' / rr in IEEE fp64 division).
 //                 The implicit stepper (cg.cpp, kernels_theta.hip) adds three phases: the reset at the head of
 //                 a run, the step start (rr = rr0, thresh = fl(rtol2 rr0)) and the update with the step's stop rule.
+//                 The preconditioned drivers (mg.cpp) add phases for rz = r.z (engine.h: CgFold, PcgState).
 // Every arithmetic operation outside a tap sum is its own rounding (#pragma clang fp contract(off), as step_epilogue.h).  No
 // atomics; records and scalars are written with plain vector stores.
 //
@@ -481,25 +482,67 @@ __global__ __launch_bounds__(64) void cg_fold_kernel(ReduceRecord *__restrict__ 
         *ts = t0;
         return;
     }
+    if (phase == CG_FOLD_PCG_INIT) {  // the head of a preconditioned run: the state reset, no record read
+        if (threadIdx.x != 0) return;
+        const CgState s0 = {0.0, 0.0, 0.0, 0.0, 0.0, 0, 0};
+        *st = s0;
+        return;
+    }
     // a start is not held back by `done`, which belongs to the step before it
     if (phase == CG_FOLD_THETA_START ? (st->breakdown & CG_HALT_BREAKDOWN) != 0 : (phase != CG_FOLD_START && broken(st))) return;
+    const bool from_dot = phase == CG_FOLD_START || phase == CG_FOLD_PCG_RZ0 || phase == CG_FOLD_PCG_RZ;
     DotAcc acc;
     acc.init();
-    if (phase == CG_FOLD_START) {  // the record lora_plan_dot's own fold left
+    if (from_dot) {  // the record lora_plan_dot's own fold left
         acc.merge_record(partial[kReduceMaxGroups]);
     } else {
         for (int g = threadIdx.x; g < groups; g += 64) acc.merge_record(partial[g]);
         wave_reduce(acc);
     }
     if (threadIdx.x != 0) return;
-    if (phase != CG_FOLD_START) {
+    if (!from_dot) {
         ReduceRecord r;
         acc.to(r);
         partial[kReduceMaxGroups] = r;
     }
     if (!st) return;
     double *hist_alpha = reinterpret_cast<double *>(st + 1), *hist_beta = hist_alpha + cap;
-    if (phase == CG_FOLD_START) {
+    PcgState *ps = reinterpret_cast<PcgState *>(hist_beta + cap);  // (read and written by the PCG phases alone)
+    if (phase == CG_FOLD_PCG_RZ0 || phase == CG_FOLD_PCG_RZ) {
+        // rz = r.z with z = M r: not finite or negative is a breakdown; zero (r vanished) halts the launches behind it as well
+        const double rz_new = acc.dot;
+        if (phase == CG_FOLD_PCG_RZ) {
+            const double beta = rz_new / ps->rz;
+            const long long it = st->iteration - 1;  // the iteration whose update ran before z = M r
+            if (it >= 0 && it < cap) hist_beta[it] = beta;
+            st->beta = beta;
+        }
+        ps->rz = rz_new;
+        if (acc.nf > 0 || !finite64(rz_new) || !(rz_new > 0.0)) st->breakdown |= CG_HALT_BREAKDOWN;
+    } else if (phase == CG_FOLD_PCG_APPLY) {
+        const double pq = acc.dot, rz = ps->rz;
+        st->pq = pq;
+        if (acc.nf > 0 || !finite64(pq) || !(pq > 0.0) || !finite64(rz))
+            st->breakdown = 1;
+        else
+            st->alpha = rz / pq;
+    } else if (phase == CG_FOLD_PCG_UPDATE || phase == CG_FOLD_PCG_THETA_UPDATE) {  // the iteration is applied; beta follows z = M r
+        const double rr_new = acc.dot;
+        const long long it = st->iteration;
+        if (it < cap) hist_alpha[it] = st->alpha;
+        st->rr = rr_new;
+        st->r_abs_max = acc.amax;
+        st->iteration = it + 1;
+        if (acc.nf > 0 || !finite64(rr_new)) {
+            st->breakdown = 1;
+        } else if (phase == CG_FOLD_PCG_THETA_UPDATE) {
+            const bool met = rr_new <= ts->thresh;
+            if (met || it + 1 >= ts->max_iters) {
+                st->breakdown = CG_HALT_DONE;
+                theta_step_done(ts, it + 1, rr_new, !met);
+            }
+        }
+    } else if (phase == CG_FOLD_START) {
         CgState s0 = {acc.dot, 0.0, 0.0, 0.0, acc.amax, 0, (acc.nf > 0 || !finite64(acc.dot)) ? 1 : 0};
         *st = s0;
     } else if (phase == CG_FOLD_THETA_START) {
@@ -586,7 +629,8 @@ hipError_t launch_cg_pointwise(int op, const ReduceArgs &a, int kind, int groups
 
 hipError_t launch_cg_fold(ReduceRecord *partial, int groups, CgState *st, int phase, int cap, hipStream_t s, ThetaState *ts, double rtol2,
                           int max_iters) {
-    if (phase >= CG_FOLD_THETA_INIT && (!st || !ts)) return hipErrorInvalidValue;
+    const bool theta = (phase >= CG_FOLD_THETA_INIT && phase <= CG_FOLD_THETA_UPDATE) || phase == CG_FOLD_PCG_THETA_UPDATE;
+    if ((theta && !ts) || (phase >= CG_FOLD_THETA_INIT && !st)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cg_fold_kernel, dim3(1), dim3(64), 0, s, partial, groups, st, phase, cap, ts, rtol2, max_iters);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// kernels_theta.hip -- the two stencil launches of the implicit time stepper (host side: cg.cpp), siblings of
-// apply_dot in kernels_cg.hip.  Both RESTATE the tile walk of their family in kernels_residual.hip exactly as apply_dot does
+// kernels_theta.hip -- the two stencil launches of the implicit time stepper (host side: cg.cpp) and the fused
+// defect launch of the V-cycle (mg.cpp), siblings of apply_dot in kernels_cg.hip.  All RESTATE the tile walk of their family in kernels_residual.hip exactly as apply_dot does
 // (window, tile sizes, tap order, centre value re-read from the window; residual_tiles.h for the walk), so `acc` has the bits
 // lora_plan_step_region stores; template parameter MODE picks what happens with a finished tap sum:
 //
@@ -9,6 +9,10 @@
 //   TH_START_SRC  r = fl(tau fl(fl(acc + f) - c)): f is read at the stored cells alone, with the store's own addressing -- as
 //                 the SRC form of kernels_residual.hip reads it -- so no halo cell of f is ever loaded.  "No source" is its
 //                 own instantiation, not "add a zero".                                                  (lora_plan_theta_start)
+//   TH_DEFECT     d = fl(acc - c), stored to o0 alone: the start without the scale, the second store and the dot
+//   TH_DEFECT_SRC d = fl(fl(acc + f) - c), f read as TH_START_SRC reads it.  Neither writes a record, so nothing folds behind
+//                 them: one launch where a source sweep and a subtraction stood, at every level of the V-cycle of mg.cpp.
+//                                                                                                        (lora_plan_defect)
 // Stores are 16 bytes at the lane's own two cells, 8 bytes for the odd tail point in 1D: interior cells only, so the halos of
 // the stored grids are neither read nor written.  Every operation behind the tap sum is its own fp64 rounding (#pragma clang
 // fp contract(off)).  No atomics; records are written with plain vector stores, one per workgroup, folded by cg_fold_kernel.
@@ -34,7 +38,11 @@ namespace {
 
 constexpr int kThreads = 256;
 
-enum { TH_SHIFT = 0, TH_START = 1, TH_START_SRC = 2 };
+enum { TH_SHIFT = 0, TH_START = 1, TH_START_SRC = 2, TH_DEFECT = 3, TH_DEFECT_SRC = 4 };
+
+constexpr bool mode_src(int mode) { return mode == TH_START_SRC || mode == TH_DEFECT_SRC; }  // f is read
+constexpr bool mode_two(int mode) { return mode == TH_START || mode == TH_START_SRC; }       // o1 is stored too
+constexpr bool mode_dot(int mode) { return mode < TH_DEFECT; }                               // a record is written
 
 struct ThetaCoef {
     double sigma, tau;
@@ -46,7 +54,7 @@ __device__ __forceinline__ bool halted(const CgState *st) {
     return MODE == TH_SHIFT ? st->breakdown != 0 : (st->breakdown & CG_HALT_BREAKDOWN) != 0;
 }
 
-// One cell: a = the swept value, c = the centre value, f = the source's (TH_START_SRC alone).  Returns the stored value; x, y
+// One cell: a = the swept value, c = the centre value, f = the source's (the SRC modes alone).  Returns the stored value; x, y
 // are the factors of the cell's product in the record.
 template <int MODE>
 __device__ __forceinline__ double theta_cell(double a, double c, double f, const ThetaCoef k, double &x, double &y) {
@@ -60,12 +68,18 @@ __device__ __forceinline__ double theta_cell(double a, double c, double f, const
         return q;
     } else {
         double t = a;
-        if constexpr (MODE == TH_START_SRC) t = step_epilogue<EPI_SOURCE>(a, f, 0.0, 0.0, 0.0);
+        if constexpr (mode_src(MODE)) t = step_epilogue<EPI_SOURCE>(a, f, 0.0, 0.0, 0.0);
         const double d = t - c;
-        const double r = k.tau * d;
-        x = r;
-        y = r;
-        return r;
+        if constexpr (!mode_dot(MODE)) {
+            x = d;
+            y = d;
+            return d;
+        } else {
+            const double r = k.tau * d;
+            x = r;
+            y = r;
+            return r;
+        }
     }
 }
 
@@ -84,21 +98,24 @@ __device__ __forceinline__ void theta_cells(DotAcc &acc, const double (&a)[N], c
         x[j] = valid[j] ? xj : 0.0;
         y[j] = valid[j] ? yj : 0.0;
     }
-    acc.cells<N>(x, y, valid);
+    if constexpr (mode_dot(MODE)) acc.cells<N>(x, y, valid);
 }
 
-// the workgroup's record into its own slot
+// the workgroup's record into its own slot (the defect modes write none)
+template <int MODE>
 __device__ __forceinline__ void finish(DotAcc &acc, ReduceRecord *__restrict__ partial) {
-    wave_reduce(acc);
-    __shared__ ReduceRecord sh[kThreads / 64];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w) acc.merge_record(sh[w]);
-        ReduceRecord r;
-        acc.to(r);
-        partial[blockIdx.x] = r;
+    if constexpr (mode_dot(MODE)) {
+        wave_reduce(acc);
+        __shared__ ReduceRecord sh[kThreads / 64];
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < kThreads / 64; ++w) acc.merge_record(sh[w]);
+            ReduceRecord r;
+            acc.to(r);
+            partial[blockIdx.x] = r;
+        }
     }
 }
 
@@ -125,12 +142,12 @@ __global__ __launch_bounds__(kThreads) void theta1d_kernel(const double *__restr
                 win[2 * q] = v.x;
                 win[2 * q + 1] = v.y;
             }
-            if constexpr (MODE == TH_START_SRC) fv = *reinterpret_cast<const d2 *>(f + i + 4);
+            if constexpr (mode_src(MODE)) fv = *reinterpret_cast<const d2 *>(f + i + 4);
         } else {  // odd tail: one point, scalar loads stay inside the padded array
 #pragma unroll
             for (int q = 0; q < 9; ++q) win[q] = in[i + q];
             win[9] = 0.0;
-            if constexpr (MODE == TH_START_SRC) fv.x = f[i + 4];
+            if constexpr (mode_src(MODE)) fv.x = f[i + 4];
         }
         double a0 = 0.0, a1 = 0.0;
 #pragma unroll
@@ -143,13 +160,13 @@ __global__ __launch_bounds__(kThreads) void theta1d_kernel(const double *__restr
         theta_cells<MODE, 2>(acc, a, c, ff, k, left >= 2 ? 2 : 1, v);
         if (left >= 2) {
             *reinterpret_cast<d2 *>(o0 + i + 4) = (d2){v[0], v[1]};
-            if constexpr (MODE != TH_SHIFT) *reinterpret_cast<d2 *>(o1 + i + 4) = (d2){v[0], v[1]};
+            if constexpr (mode_two(MODE)) *reinterpret_cast<d2 *>(o1 + i + 4) = (d2){v[0], v[1]};
         } else {
             o0[i + 4] = v[0];
-            if constexpr (MODE != TH_SHIFT) o1[i + 4] = v[0];
+            if constexpr (mode_two(MODE)) o1[i + 4] = v[0];
         }
     }
-    finish(acc, partial);
+    finish<MODE>(acc, partial);
 }
 
 // ---- 2D (kernels_cg.hip: apply_dot2d_kernel; the piece of f as kernels_residual.hip: residual2d_kernel<SRC>) ---------------
@@ -166,7 +183,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta2d_kernel(const double *__re
     constexpr int LH = TH + 6;
     constexpr int NCHUNK = LH * kChunksPerRow;
     constexpr int NIT = (NCHUNK + 255) / 256;
-    constexpr bool SRC = MODE == TH_START_SRC;
+    constexpr bool SRC = mode_src(MODE);
     constexpr int kAhead = 4;  // window rows between the load of a row's piece of f and its use (as residual2d_kernel)
     __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
     if (halted<MODE>(st)) return;
@@ -268,7 +285,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta2d_kernel(const double *__re
                     theta_cells<MODE, 2>(dacc, a, b, ff, kc, 2, v);
                     const size_t cell = (size_t) (row + 4) * ld + (col + 4);
                     *reinterpret_cast<d2 *>(o0 + cell) = (d2){v[0], v[1]};
-                    if constexpr (MODE != TH_SHIFT) *reinterpret_cast<d2 *>(o1 + cell) = (d2){v[0], v[1]};
+                    if constexpr (mode_two(MODE)) *reinterpret_cast<d2 *>(o1 + cell) = (d2){v[0], v[1]};
                 }
             }
 #pragma unroll
@@ -277,7 +294,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta2d_kernel(const double *__re
         }
         __syncthreads();  // every wave is done with the window before the next tile's is staged
     }
-    finish(dacc, partial);
+    finish<MODE>(dacc, partial);
 }
 
 // ---- 3D (kernels_cg.hip: apply_dot3d_kernel; the pieces of f at residual3d_kernel<SRC>'s addresses, loaded in the epilogue) ---
@@ -295,7 +312,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__re
     constexpr int LH = TY + 2;
     constexpr int NCHUNK = LH * kChunksPerRow;
     constexpr int NIT = (NCHUNK + 255) / 256;
-    constexpr bool SRC = MODE == TH_START_SRC;
+    constexpr bool SRC = mode_src(MODE);
     __shared__ __attribute__((aligned(16))) double tile[2][LH * kLdsW];
     if (halted<MODE>(st)) return;
 
@@ -419,7 +436,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__re
                             double v[2];
                             theta_cells<MODE, 2>(dacc, a, b, ff, kc, 2, v);
                             *reinterpret_cast<d2 *>(o0 + base + (long) r * ld) = (d2){v[0], v[1]};
-                            if constexpr (MODE != TH_SHIFT) *reinterpret_cast<d2 *>(o1 + base + (long) r * ld) = (d2){v[0], v[1]};
+                            if constexpr (mode_two(MODE)) *reinterpret_cast<d2 *>(o1 + base + (long) r * ld) = (d2){v[0], v[1]};
                         }
                     }
                 }
@@ -441,7 +458,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__re
             if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
         }
     }
-    finish(dacc, partial);
+    finish<MODE>(dacc, partial);
 }
 
 template <int MODE>
@@ -487,6 +504,15 @@ hipError_t launch_theta_start(const Plan &p, const ResidualTiles &rt, const doub
         launch_mode<TH_START_SRC>(p, rt, d_u, d_f, d_r, d_p, ThetaCoef{1.0, tau}, st, partial, s);
     else
         launch_mode<TH_START>(p, rt, d_u, nullptr, d_r, d_p, ThetaCoef{1.0, tau}, st, partial, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_defect(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double *d_out, hipStream_t s) {
+    if (!has_cg(p) || rt.groups < 1 || rt.groups > kReduceMaxGroups) return hipErrorInvalidValue;
+    if (d_f)
+        launch_mode<TH_DEFECT_SRC>(p, rt, d_u, d_f, d_out, nullptr, ThetaCoef{1.0, 1.0}, nullptr, nullptr, s);
+    else
+        launch_mode<TH_DEFECT>(p, rt, d_u, nullptr, d_out, nullptr, ThetaCoef{1.0, 1.0}, nullptr, nullptr, s);
     return hipGetLastError();
 }
 

@@ -6,7 +6,8 @@
 // Coarsening is boundary-aligned and non-nested (kernels_mg.hip has the geometry): level l + 1 has floor(n / 2) cells per axis,
 // the innermost rounded down to even, and the taps of level l rescaled by (h / H)^2 per axis.  On every level but the coarsest
 // the smoother is damped Jacobi folded into the taps of an internal plan with the level's right-hand side as its source, so a
-// smoothing application is one source sweep and the level's residual one more sweep and a subtraction.
+// smoothing application is one source sweep and the level's residual one fused defect launch (kernels_theta.hip).  The same
+// cycle for A = sigma I - tau S is the preconditioner of the PCG drivers in cg.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -100,8 +101,12 @@ struct LevelDesc {
     double d = 0.0, c = 0.0;
 };
 
-// The levels of a plan for `m`: LORA_OK, or LORA_EUNSUPPORTED for a level whose diagonal 1 - w[centre] is not positive and finite.
-int describe_levels(const Plan &p, const lora_mg *m, std::vector<LevelDesc> &out) {
+bool bad_pair(double sigma, double tau) { return !std::isfinite(sigma) || !std::isfinite(tau) || !(tau >= 0.0) || !(sigma > 0.0); }
+
+// The levels of a plan for `m` and A = sigma I - tau S: LORA_OK, or LORA_EUNSUPPORTED for a level whose diagonal
+// sigma - tau w[centre] is not positive and finite.  With sigma == tau == 1 every product with 1 is exact: the taps of I - S.
+int describe_levels(const Plan &p, const lora_mg *m, double sigma, double tau, std::vector<LevelDesc> &out) {
+#pragma clang fp contract(off)
     const int cap = m->max_levels ? (m->max_levels < kMaxLevels ? m->max_levels : kMaxLevels) : kMaxLevels;
     const int c = centre_tap(p.ndim);
     out.clear();
@@ -109,13 +114,18 @@ int describe_levels(const Plan &p, const lora_mg *m, std::vector<LevelDesc> &out
     for (int a = 0; a < p.ndim; ++a) lv.dims[a] = p.dims[a];
     std::memcpy(lv.w, p.w, sizeof(double) * p.ntaps);
     for (;;) {
-        lv.d = 1.0 - lv.w[c];
-        if (!(lv.d > 0.0) || !std::isfinite(lv.d))
-            return unsupported("a multigrid level's diagonal 1 - w[centre] is not positive and finite: damped Jacobi cannot smooth it");
-        lv.c = m->omega / lv.d;
-        for (int t = 0; t < p.ntaps; ++t) lv.s[t] = lv.c * lv.w[t];
         {
-            const double keep = 1.0 - lv.c;
+            const double tw = tau * lv.w[c];
+            lv.d = sigma - tw;
+        }
+        if (!(lv.d > 0.0) || !std::isfinite(lv.d))
+            return unsupported("a multigrid level's diagonal sigma - tau w[centre] is not positive and finite: damped Jacobi cannot smooth it");
+        lv.c = m->omega / lv.d;
+        const double ct = lv.c * tau;
+        for (int t = 0; t < p.ntaps; ++t) lv.s[t] = ct * lv.w[t];
+        {
+            const double cs = lv.c * sigma;
+            const double keep = 1.0 - cs;
             lv.s[c] = lv.s[c] + keep;
         }
         out.push_back(lv);
@@ -141,7 +151,7 @@ struct Level {
 
 struct MgHierarchy {
     std::vector<Level> levels;
-    double omega = 0.0;
+    double omega = 0.0, sigma = 1.0, tau = 1.0;
     int max_levels = 0, device = -1;
     unsigned epoch = 0;
     long launches = 0;  // of the last cycle enqueued ...
@@ -178,20 +188,23 @@ int make_plan(lora_plan **out, int shape, const int *dims, const double *taps, i
     return rc;
 }
 
-// The plan's hierarchy for `m` on the current device, built or rebuilt when the taps, the damping, the depth or the device changed.
-int ensure_hierarchy(lora_plan *plan, const lora_mg *m, bool with_source) {
+// The plan's hierarchy for `m` and (sigma, tau) on the current device, built or rebuilt when the taps, the damping, the pair, the
+// depth or the device changed.
+int ensure_hierarchy(lora_plan *plan, const lora_mg *m, double sigma, double tau, bool with_source) {
     const Plan &p = plan->p;
     int device = -1;
     if (int rc = hip_status(hipGetDevice(&device), "hipGetDevice")) return rc;
     MgHierarchy *h = plan->mg;
-    if (!(h && h->omega == m->omega && h->max_levels == m->max_levels && h->epoch == p.epoch && h->device == device)) {
+    if (!(h && h->omega == m->omega && h->sigma == sigma && h->tau == tau && h->max_levels == m->max_levels && h->epoch == p.epoch && h->device == device)) {
         mg_release(plan);
         std::vector<LevelDesc> descs;
-        if (int rc = describe_levels(p, m, descs)) return rc;
+        if (int rc = describe_levels(p, m, sigma, tau, descs)) return rc;
         h = new (std::nothrow) MgHierarchy();
         if (!h) return LORA_ENOMEM;
         plan->mg = h;
         h->omega = m->omega;
+        h->sigma = sigma;
+        h->tau = tau;
         h->max_levels = m->max_levels;
         h->epoch = p.epoch;
         h->device = device;
@@ -276,17 +289,20 @@ struct Run {
 int cycle(const Run &r, int l, Tally &tally) {
     Level &lv = r.h->levels[l];
     if (l == r.L) {
-        if (int rc = cg_fixed_iterations(lv.plain, lv.cur, r.coarse_iters, r.s, &tally.launches)) return rc;
+        if (int rc = cg_fixed_iterations(lv.plain, lv.cur, r.coarse_iters, r.h->sigma, r.h->tau, r.s, &tally.launches)) return rc;
         tally.bytes += 8.0 * lv.cells * (3.0 + 11.0 * r.coarse_iters);  // the copy and the dot; eleven grids an iteration (lora_run_host_cg)
         return LORA_OK;
     }
     Level &co = r.h->levels[l + 1];
     const Plan &sp = lv.smooth->p;
     if (int rc = smooth(lv, r.m->pre, r.s, tally)) return rc;
-    // rs = fl(S_s(x) + g - x) = c_l times the level's residual, in the level's free grid
-    if (int rc = launch_apps(sp, {1, 0, sp.dims[0]}, lv.cur, lv.other, r.s)) return rc;
-    if (int rc = hip_status(launch_mg_sub(r.ndim, lv.desc.dims, lv.other, lv.cur, r.s), "residual subtraction launch")) return rc;
-    tally.add(2, lv.cells, (sp.source ? 3.0 : 2.0) + 3.0);
+    // rs = fl(fl(S_s(x) + g) - x) = c_l times the level's residual, in the level's free grid: one launch, the source its argument
+    {
+        Plan bare = sp;
+        bare.source = nullptr;
+        if (int rc = defect_whole(bare, lv.cur, static_cast<const double *>(sp.source), lv.other, r.s)) return rc;
+    }
+    tally.add(1, lv.cells, sp.source ? 3.0 : 2.0);
     // the coarse right-hand side: scaled for the coarse smoother, unscaled for the coarsest level's CG
     const bool last = l + 1 == r.L;
     const double scale = last ? 1.0 / lv.desc.c : co.desc.c / lv.desc.c;
@@ -316,10 +332,88 @@ int admit_mg(const lora_plan *plan, const lora_mg *m) {
     if (!taps_symmetric(p.w, p.ntaps))
         return unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
     std::vector<LevelDesc> descs;
-    return describe_levels(p, m, descs);
+    return describe_levels(p, m, 1.0, 1.0, descs);
 }
 
+// the halos every level's free grid shares with its iterate below level 0, and the coarsest level's iterate
+int reset_level_halos(MgHierarchy *h, hipStream_t s) {
+    const int L = (int) h->levels.size() - 1;
+    for (int l = 1; l < L; ++l)
+        if (int rc = hip_status(launch_halo(h->levels[l].smooth->p, h->levels[l].spare.ptr, nullptr, HALO_ZERO, s), "halo reset")) return rc;
+    h->levels[L].cur = static_cast<double *>(h->levels[L].x.ptr);
+    return LORA_OK;
+}
+
+int coarse_iterations(const MgHierarchy *h, const lora_mg *m) {
+    return m->coarse_iters ? m->coarse_iters : (int) std::fmin(h->levels.back().cells, 64.0);
+}
+
+const int kPads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+
 }  // namespace
+
+bool mg_bad(const lora_mg *m, double sigma, double tau) { return bad_mg(m) || bad_pair(sigma, tau); }
+
+int mg_admit(const lora_plan *plan, const lora_mg *m, double sigma, double tau, int *levels) {
+    if (mg_bad(m, sigma, tau)) return LORA_EINVAL;
+    const Plan &p = plan->p;
+    if (!has_mg(p)) return no_mg_kernels();
+    if (!taps_symmetric(p.w, p.ntaps))
+        return unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: sigma I - tau S is not symmetric otherwise");
+    std::vector<LevelDesc> descs;
+    if (int rc = describe_levels(p, m, sigma, tau, descs)) return rc;
+    if (levels) *levels = (int) descs.size();
+    return LORA_OK;
+}
+
+int mg_prepare(lora_plan *plan, const lora_mg *m, double sigma, double tau) { return ensure_hierarchy(plan, m, sigma, tau, true); }
+
+bool mg_owns(const lora_plan *plan, const void *buf) {
+    if (!plan->mg || !buf) return false;
+    for (const Level &lv : plan->mg->levels) {
+        const void *own[] = {lv.x.ptr, lv.spare.ptr, lv.g.ptr, lv.plain ? lv.plain->cg[0].ptr : nullptr, lv.plain ? lv.plain->cg[1].ptr : nullptr,
+                             lv.plain ? lv.plain->cg[2].ptr : nullptr};
+        for (const void *o : own)
+            if (o && o == buf) return true;
+    }
+    return false;
+}
+
+void mg_cost(const lora_plan *plan, long *launches, double *bytes) {
+    *launches = plan->mg ? plan->mg->launches : 0;
+    *bytes = plan->mg ? plan->mg->bytes : 0.0;
+}
+
+// z = M r: one V-cycle for A z = r from z = 0 (lora_plan_mg_precondition has the contract); the tally counts all of it
+int mg_precondition(lora_plan *plan, const double *d_r, double *d_z, const lora_mg *m, double sigma, double tau, hipStream_t s) {
+    const Plan &p = plan->p;
+    if (int rc = ensure_hierarchy(plan, m, sigma, tau, true)) return rc;
+    MgHierarchy *h = plan->mg;
+    Level &top = h->levels[0];
+    double *spare0 = static_cast<double *>(top.spare.ptr);
+    if (int rc = lora_plan_set_source(top.smooth, top.g.ptr)) return rc;
+    Tally tally;
+    if (int rc = hip_status(launch_mg_scale(p.ndim, p.dims, static_cast<double *>(top.g.ptr), d_r, top.desc.c, s), "source scale launch")) return rc;
+    tally.add(1, top.cells, 2.0);
+    if (int rc = hip_status(hipMemsetAsync(d_z, 0, top.bytes, s), "zero start")) return rc;
+    tally.add(1, (double) top.bytes / 8.0, 1.0);
+    if (int rc = hip_status(launch_halo(p, spare0, nullptr, HALO_ZERO, s), "halo reset")) return rc;
+    if (int rc = reset_level_halos(h, s)) return rc;
+    tally.launches += (long) h->levels.size() - 1;  // (the halo resets: a grid's rim each)
+    const Run run = {plan, h, m, s, p.ndim, (int) h->levels.size() - 1, coarse_iterations(h, m)};
+    top.cur = d_z;
+    top.other = spare0;
+    if (int rc = cycle(run, 0, tally)) return rc;
+    if (top.cur != d_z) {  // an odd number of launches moved the iterate: back into the caller's grid, interior cells only
+        if (int rc = hip_status(launch_copy_interior(LORA_F64, p.ndim, p.dims, d_z, kPads[p.ndim - 1], top.cur, kPads[p.ndim - 1], s), "copy launch"))
+            return rc;
+        tally.add(1, top.cells, 2.0);
+    }
+    h->launches = tally.launches;
+    h->bytes = tally.bytes;
+    return LORA_OK;
+}
+
 }  // namespace lora
 
 using lora::Plan;
@@ -376,7 +470,18 @@ int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m) {
     if (lora_device_count() <= 0) return lora::no_device();
     lora::ReduceRecord *records = nullptr;  // (the probe folds into the plan's records: they are part of what a run needs)
     if (int rc = lora::reduction_records(plan, &records)) return rc;
-    return lora::ensure_hierarchy(plan, m, true);
+    return lora::ensure_hierarchy(plan, m, 1.0, 1.0, true);
+}
+
+int lora_plan_mg_precondition(lora_plan *plan, const void *d_r, void *d_z, const lora_mg *m, double sigma, double tau, void *stream) {
+    if (!plan || !d_r || !d_z || !m || lora::bad_mg(m) || lora::bad_pair(sigma, tau) || d_r == d_z) return LORA_EINVAL;
+    if (lora::misaligned(d_r) || lora::misaligned(d_z)) return lora::unsupported("device buffers must be 16-byte aligned");
+    if (int rc = lora::mg_admit(plan, m, sigma, tau, nullptr)) return rc;
+    if (lora_device_count() <= 0) return lora::no_device();
+    if (int rc = lora::mg_prepare(plan, m, sigma, tau)) return rc;
+    if (lora::mg_owns(plan, d_r) || lora::mg_owns(plan, d_z)) return LORA_EINVAL;
+    return lora::mg_precondition(plan, static_cast<const double *>(d_r), static_cast<double *>(d_z), m, sigma, tau,
+                                 static_cast<hipStream_t>(stream));
 }
 
 int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes) {
@@ -395,21 +500,16 @@ int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
     if (!lora::taps_symmetric(p.w, p.ntaps))
         return lora::unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
     std::vector<lora::LevelDesc> descs;
-    if (int rc = lora::describe_levels(p, m, descs)) return rc;
+    if (int rc = lora::describe_levels(p, m, 1.0, 1.0, descs)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = lora::admit_reduction(d_x, d_x, s)) return rc;
     *r = {{0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}}, 0, {{0}}};
     lora::fill_levels(descs, r);
     if (u->max_times < u->check_every) return LORA_OK;
-    if (int rc = lora::ensure_hierarchy(plan, m, d_f != nullptr)) return rc;
+    if (int rc = lora::ensure_hierarchy(plan, m, 1.0, 1.0, d_f != nullptr)) return rc;
     lora::MgHierarchy *h = plan->mg;
     const int L = (int) h->levels.size() - 1;
-    for (const lora::Level &lv : h->levels) {
-        const void *own[] = {lv.x.ptr, lv.spare.ptr, lv.g.ptr, lv.plain ? lv.plain->cg[0].ptr : nullptr, lv.plain ? lv.plain->cg[1].ptr : nullptr,
-                             lv.plain ? lv.plain->cg[2].ptr : nullptr};
-        for (const void *o : own)
-            if (o && (o == d_x || o == d_f)) return LORA_EINVAL;
-    }
+    if (lora::mg_owns(plan, d_x) || lora::mg_owns(plan, d_f)) return LORA_EINVAL;
     lora::ReduceRecord *records = nullptr;
     if (int rc = lora::reduction_records(plan, &records)) return rc;
 
@@ -423,13 +523,9 @@ int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
                                       "source scale launch"))
             return rc;
     if (int rc = lora::hip_status(lora::launch_halo(p, spare0, d_x, lora::HALO_COPY, s), "halo copy")) return rc;
-    for (int l = 1; l < L; ++l)
-        if (int rc = lora::hip_status(lora::launch_halo(h->levels[l].smooth->p, h->levels[l].spare.ptr, nullptr, lora::HALO_ZERO, s), "halo reset"))
-            return rc;
-    h->levels[L].cur = static_cast<double *>(h->levels[L].x.ptr);
+    if (int rc = lora::reset_level_halos(h, s)) return rc;
 
-    const int cells_L = (int) std::fmin(h->levels[L].cells, 64.0);
-    const lora::Run run = {plan, h, m, s, p.ndim, L, m->coarse_iters ? m->coarse_iters : cells_L};
+    const lora::Run run = {plan, h, m, s, p.ndim, L, lora::coarse_iterations(h, m)};
     // the sweep of the two-pass probe: the plan's own single sweep with f as its source (as lora_plan_run_cg_until)
     Plan with_f = p;
     with_f.source = d_f;

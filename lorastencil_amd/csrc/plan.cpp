@@ -507,6 +507,8 @@ const Option kOptions[] = {
     {"cg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_cg(q) ? 1 : 0; }},
     // whether the plan has the multigrid transfer kernels and the V-cycle driver (lora_plan_mg_restrict, lora_plan_run_mg_until)
     {"mg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_mg(q) ? 1 : 0; }},
+    // whether the plan has the multigrid-preconditioned drivers (lora_plan_mg_precondition, lora_plan_run_pcg_until): as "mg"
+    {"pcg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_mg(q) ? 1 : 0; }},
     // whether the plan carries a source (lora_plan_set_source)
     {"source", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return q.source ? 1 : 0; }},
 };

@@ -273,6 +273,16 @@ class MgResult(NamedTuple):
     level_dims: tuple
 
 
+class PcgResult(NamedTuple):
+    """What ``run_pcg_until`` returns (lora_pcg_result): the until-result counted in ITERATIONS, the extreme Ritz values of M A
+    from the run's coefficients (NaN when no iteration ran), whether PCG broke down, and the depth of the hierarchy."""
+    until: UntilResult
+    lambda_min: float
+    lambda_max: float
+    breakdown: bool
+    levels: int
+
+
 NORMS = {"max": _lib.NORM_MAX, "rms": _lib.NORM_RMS}
 
 
@@ -295,6 +305,10 @@ def _theta_result(r, iterations=()) -> ThetaResult:
 
 def _mg_result(r, nd: int) -> MgResult:
     return MgResult(_until_result(r.until), r.levels, tuple(tuple(r.level_dims[l][a] for a in range(nd)) for l in range(r.levels)))
+
+
+def _pcg_result(r) -> PcgResult:
+    return PcgResult(_until_result(r.until), r.lambda_min, r.lambda_max, bool(r.breakdown), r.levels)
 
 
 def _mg_arg(pre, post, omega, max_levels, coarse_iters):
@@ -584,6 +598,52 @@ def run_host_theta(shape, in_: np.ndarray, tau: float, steps: int, source=None, 
     check(_lib.lib().lora_run_host_theta(sid, _p(in_), None if src is None else _p(src), _p(out), pp, float(theta), float(tau), int(steps),
                                          int(max_iters), float(rtol), _dims_arg(dims), int(quiet), ctypes.byref(info), ctypes.byref(r)),
           f"lora_run_host_theta({SHAPE_NAMES.get(sid, sid)})")
+    return out, _theta_result(r), info
+
+
+def _host_arrays(shape, in_, source):
+    sid = shape_id(shape)
+    in_ = np.ascontiguousarray(in_, dtype=np.float64)
+    h = halo(sid)
+    if in_.ndim != len(h):
+        raise ValueError("in_ must be a padded array of the shape's rank")
+    src = None
+    if source is not None:
+        src = np.ascontiguousarray(source, dtype=np.float64)
+        if src.shape != in_.shape:
+            raise ValueError("source must be a padded array of in_'s size")
+    return sid, in_, src, [in_.shape[i] - 2 * h[i] for i in range(in_.ndim)]
+
+
+def run_host_pcg(shape, in_: np.ndarray, tol: float, source=None, smooth: int = 2, omega: float = 0.8, max_levels: int = 0,
+                 coarse_iters: int = 0, rtol: float = 0.0, norm="max", check_every: int = 2, max_times: int = 50, params=None,
+                 quiet: bool = True):
+    """Conjugate gradients preconditioned by one V(smooth, smooth) cycle for u = S(u) + f from the padded float64 host array
+    ``in_`` (lora_run_host_pcg): until the true residual is <= tol + rtol * max|S(u) + f|, checked every ``check_every``
+    iterations.  Returns (the iterate as a padded array, PcgResult, RunInfo)."""
+    sid, in_, src, dims = _host_arrays(shape, in_, source)
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    m, u = _mg_arg(smooth, smooth, omega, max_levels, coarse_iters), _until_arg(tol, rtol, norm, check_every, max_times)
+    r, info = _lib.PcgResult(), RunInfo()
+    check(_lib.lib().lora_run_host_pcg(sid, _p(in_), None if src is None else _p(src), _p(out), pp, ctypes.byref(m), ctypes.byref(u),
+                                       ctypes.byref(r), _dims_arg(dims), int(quiet), ctypes.byref(info)), f"lora_run_host_pcg({SHAPE_NAMES.get(sid, sid)})")
+    return out, _pcg_result(r), info
+
+
+def run_host_theta_mg(shape, in_: np.ndarray, tau: float, steps: int, source=None, theta: float = 1.0, max_iters: int = 50,
+                      rtol: float = 1e-8, smooth: int = 2, omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0,
+                      check_every: int = 2, params=None, quiet: bool = True):
+    """``run_host_theta`` with every step's solve preconditioned by one V(smooth, smooth) cycle for the step's operator
+    (lora_run_host_theta_mg); the state is read back every ``check_every`` iterations.  Returns (the last level as a padded
+    array, ThetaResult without per-step counts, RunInfo)."""
+    sid, in_, src, dims = _host_arrays(shape, in_, source)
+    out = np.zeros_like(in_)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    m, r, info = _mg_arg(smooth, smooth, omega, max_levels, coarse_iters), _lib.ThetaResult(), RunInfo()
+    check(_lib.lib().lora_run_host_theta_mg(sid, _p(in_), None if src is None else _p(src), _p(out), pp, float(theta), float(tau), int(steps),
+                                            int(max_iters), float(rtol), ctypes.byref(m), int(check_every), _dims_arg(dims), int(quiet),
+                                            ctypes.byref(info), ctypes.byref(r)), f"lora_run_host_theta_mg({SHAPE_NAMES.get(sid, sid)})")
     return out, _theta_result(r), info
 
 
@@ -972,6 +1032,51 @@ class Plan:
         n, b = ctypes.c_int(), ctypes.c_double()
         check(_lib.lib().lora_plan_mg_cycle_cost(self._h, ctypes.byref(n), ctypes.byref(b)), "lora_plan_mg_cycle_cost")
         return n.value, b.value
+
+    # -- multigrid-preconditioned CG, also for the implicit stepper's operator (plans whose option "pcg" reads 1; ``defect``: "cg")
+    def defect(self, d_u, d_f, d_out, begin: int = 0, end: int = 0, stream=None):
+        """out = (S(u) + f) - u on the interior cells of [begin, end) in one launch, each cell ``step_region``'s bits (``d_f`` may
+        be None: out = S(u) - u); no record, asynchronous (lora_plan_defect).  The halo of ``d_out`` is not touched."""
+        check(_lib.lib().lora_plan_defect(self._h, _ptr(d_u), _optr(d_f), _ptr(d_out), int(begin), int(end), _stream(stream)),
+              "lora_plan_defect")
+
+    def mg_precondition(self, d_r, d_z, sigma: float = 1.0, tau: float = 1.0, pre: int = 2, post: int = 2, omega: float = 0.8,
+                        max_levels: int = 0, coarse_iters: int = 0, stream=None):
+        """z = M r: one V(pre, post) cycle for (sigma I - tau S) z = r from z = 0 (lora_plan_mg_precondition); asynchronous.
+        ``d_z`` is zeroed over its whole padded array first; only interior cells of ``d_r`` are read."""
+        m = _mg_arg(pre, post, omega, max_levels, coarse_iters)
+        check(_lib.lib().lora_plan_mg_precondition(self._h, _ptr(d_r), _ptr(d_z), ctypes.byref(m), float(sigma), float(tau), _stream(stream)),
+              "lora_plan_mg_precondition")
+
+    def prepare_pcg(self, max_times: int, smooth: int = 2, omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0):
+        """Allocate now what ``run_pcg_until`` with the same cycle and ``max_times`` would allocate on first need."""
+        m = _mg_arg(smooth, smooth, omega, max_levels, coarse_iters)
+        check(_lib.lib().lora_plan_prepare_pcg(self._h, ctypes.byref(m), int(max_times)), "lora_plan_prepare_pcg")
+        return self
+
+    def run_pcg_until(self, d_x, d_f, tol: float, smooth: int = 2, omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0,
+                      rtol: float = 0.0, norm="max", check_every: int = 2, max_times: int = 50, pre=None, post=None,
+                      stream=None) -> PcgResult:
+        """Conjugate gradients for u = S(u) + f preconditioned by one V(smooth, smooth) cycle, in rounds of ``check_every``
+        iterations until the TRUE residual max|S(u) + f - u| is <= tol + rtol * max|S(u) + f| (lora_plan_run_pcg_until).
+        ``pre`` / ``post`` override ``smooth``; the engine refuses pre != post (the preconditioner must be symmetric)."""
+        m = _mg_arg(smooth if pre is None else pre, smooth if post is None else post, omega, max_levels, coarse_iters)
+        u, r = _until_arg(tol, rtol, norm, check_every, max_times), _lib.PcgResult()
+        check(_lib.lib().lora_plan_run_pcg_until(self._h, _ptr(d_x), _optr(d_f), ctypes.byref(m), ctypes.byref(u), ctypes.byref(r),
+                                                 _stream(stream)), "lora_plan_run_pcg_until")
+        return _pcg_result(r)
+
+    def run_theta_mg(self, d_u, d_f, tau: float, steps: int, theta: float = 1.0, max_iters: int = 50, rtol: float = 1e-8,
+                     smooth: int = 2, omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0, check_every: int = 2,
+                     stream=None) -> ThetaResult:
+        """``run_theta`` with every step's solve preconditioned by one V(smooth, smooth) cycle for the step's operator
+        (lora_plan_run_theta_mg).  The state is read back every ``check_every`` iterations; blocks there and at its end."""
+        m = _mg_arg(smooth, smooth, omega, max_levels, coarse_iters)
+        r, its = _lib.ThetaResult(), (ctypes.c_int * max(int(steps), 1))()
+        check(_lib.lib().lora_plan_run_theta_mg(self._h, _ptr(d_u), _optr(d_f), float(theta), float(tau), int(steps), int(max_iters),
+                                                float(rtol), ctypes.byref(m), int(check_every), its, ctypes.byref(r), _stream(stream)),
+              "lora_plan_run_theta_mg")
+        return _theta_result(r, its[:max(int(steps), 0)])
 
     # -- reductions on the device (these block until the result is on the host)
     def stats(self, d_buf, begin: int = 0, end: int = 0, stream=None) -> GridStats:
