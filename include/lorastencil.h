@@ -285,6 +285,10 @@ int lora_set_default_normalize(int on);
 /* Option "leap3" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_leapfrog and
  * lora_run_host_chebyshev (what lorastencil_3d's --leap3 flag sets).  Returns the previous value. */
 int lora_set_default_leap3(int on);
+/* Option "coarse1" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_mg, lora_run_host_pcg and
+ * lora_run_host_theta_mg (what the CLIs' --coarse1 flag sets); never of the internal plans of a multigrid hierarchy.  Returns
+ * the previous value. */
+int lora_set_default_coarse1(int on);
 /* Integer options.  Results never depend on them except where stated.
  *   steps_per_launch  0 auto / 1 / 2 (2D also 4 with the row-streaming kernel and 6 with the workgroup-row kernel, 3D fp64
  *                     also 3 with the plane-streaming kernel, 1D also 4, 8, 16, 32) : applications per launch in
@@ -303,6 +307,12 @@ int lora_set_default_leap3(int on);
  *                     effect on other plans, and none on the kernel name, signature or depth of the plain sweeps.  Same
  *                     bits either way.  Measured: a launch takes 0.72 - 0.89 of the time
  *                     of two single steps, a run of 120 steps 0.79 - 0.95; off until the default is decided on those figures
+ *   coarse1           0 (default) / 1 : the multigrid cycles this plan drives (lora_plan_run_mg_until, lora_plan_mg_precondition,
+ *                     lora_plan_run_pcg_until, lora_plan_run_theta_mg) run their coarsest level as ONE launch,
+ *                     lora_plan_cg_small, when that level's plan reads "cg_small" = 1; otherwise nothing changes.  The level's
+ *                     sums fold in another order than the 5 launches per iteration it replaces, so the bits of a cycle
+ *                     differ at rounding level (its own bit contract: lora_plan_cg_small).  Any non-zero value reads back as
+ *                     1; no effect on a kernel name, signature or sweep.  Measured: DESIGN 3.13
  *   stream3           3D fp64 fused launches: 1 = plane-streaming kernel (kernels_3d_planes.hip: LDS-DMA plane ring, three
  *                     applications per launch for the 7-point star, two for the box), 0 = the two-application tile kernel,
  *                     -1 (default) = by grid size: three applications from ~1.2e8 points (star), the plane-streaming
@@ -852,7 +862,8 @@ int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine
  *   At level L:  r = g_L, p = r on the interior with a zero halo, rr = lora_plan_dot(r, r).dot, then m->coarse_iters (0: min(64,
  *   cells of the coarsest interior)) conjugate-gradient iterations on x_L exactly as lora_plan_run_cg_until writes them, with the
  *   same kernels, device-resident scalars and sticky halt flag, and no probe; a residual that vanishes exactly halts the
- *   level's remaining launches harmlessly.
+ *   level's remaining launches harmlessly.  With plan option "coarse1" on and a level L whose plan reads "cg_small" = 1 the level
+ *   is instead ONE launch, lora_plan_cg_small(plan_L, x_L, g_L, iterations, sigma, tau) -- here and in the three drivers below.
  *   A cycle is enqueued with NO host wait inside it.  u->check_every and u->max_times count CYCLES, and any check_every >= 1 is
  *   legal here; the other rules of `u`, the stop rule and the fields of r->until are lora_plan_run_until's (times_done counts
  *   cycles).  After each round the run probes the true residual of the caller's problem, S(d_x) + f - d_x with the plan's own
@@ -889,7 +900,9 @@ int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
 int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m);
 /* What the last cycle the plan enqueued took (lora_plan_run_mg_until, lora_plan_mg_precondition and the drivers on it), counted
  * while it was enqueued: the number of launches (kernels and memsets; a coarsest-level iteration is five) and the bytes they
- * move when every launch reads and writes each of its grids' interiors once (a zeroing writes the padded grid).  LORA_EINVAL
+ * move when every launch reads and writes each of its grids' interiors once (a zeroing writes the padded grid).  With plan
+ * option "coarse1" on and a coarsest level that reads "cg_small" = 1 that level counts as one launch and four passes over its
+ * cells: 5 + 5 iters - 1 launches fewer.  LORA_EINVAL
  * for a null pointer or a plan on which no cycle has run. */
 int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes);
 
@@ -907,6 +920,34 @@ int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes)
  *   Status, in this order: LORA_EINVAL for a null plan, d_u or d_out, a bad range or begin, any two buffers equal;
  *   LORA_EUNSUPPORTED for a misaligned buffer, then for a plan whose option "cg" reads 0; LORA_ENODEVICE without a device. */
 int lora_plan_defect(lora_plan *plan, const void *d_u, const void *d_f, void *d_out, int begin, int end, void *stream);
+/* ---- the whole small CG in one launch (NEW).  `iters` conjugate-gradient iterations for A = sigma I - tau S
+ * on a grid small enough for ONE workgroup, in ONE launch: what the coarsest level of a V-cycle needs (plan option "coarse1").
+ * fp64, 2D and 3D shapes, any taps, zero Dirichlet halo.  d_r holds the residual b - A x of the iterate in d_x on entry.
+ *   Which plans (read-only option "cg_small": 1 or 0): plans whose option "cg" reads 1, of a 2D or 3D shape, with at most 4096
+ *   interior cells (1024 lanes, four cells each in registers) and at most 64 KiB of LDS for p inside its ring of zeros:
+ *   8 (32 + (m + 6)(n + 6)) bytes in 2D, 8 (32 + (h + 2)(m + 2)(n + 2)) in 3D.  4 x 512, 32 x 32, 64 x 64 and 12 x 12 x 12 fit,
+ *   4 x 1024 does not.
+ *   CONTRACT.  The interiors of d_x and d_r are read once, in 8-byte pieces; x, r, p, q stay in registers, p also in LDS inside a
+ *   ring of zeros as wide as the tap radius, so no halo cell of either grid is read or written and nothing outside the padded
+ *   arrays is touched; the interiors are written once, at the end.  p = r, rr = r.r, then per iteration, every named operation
+ *   its own fp64 rounding (nothing contracted):
+ *     q = fl(fl(sigma p) - fl(tau acc)), acc the sum of w[t] p[cell + offset t] as a chain of fused multiply-adds from 0 over the
+ *     non-zero taps in ascending t; with sigma == tau == 1 the plain form q = fl(p - acc);
+ *     pq = p.q;  alpha = rr / pq;  x = fl(x + fl(alpha p));  r = fl(r - fl(alpha q));
+ *     rr' = r.r;  beta = rr' / rr;  p = fl(r + fl(beta p));  rr = rr'.
+ *   A dot folds in a fixed order: with T = min(1024, cells rounded up to 64) lanes, lane t adds fl(a b) of its cells t, t + T,
+ *   t + 2 T, ... (row-major interior index) from 0 in that order; the 64 lanes of a wave fold by the butterfly of the reductions
+ *   (partner lane ^ 1, ^ 2, ... ^ 32); the waves' sums are added in wave order from wave 0's.  No atomics; every lane divides
+ *   the same two sums in IEEE fp64, so the same call gives the same bits every time.
+ *   Halting, uniform over the workgroup: rr == 0 before an iteration ends the loop as converged (halt 1); pq not finite or <= 0
+ *   ends it as a breakdown (halt 2) and leaves x and r as they were before that iteration; a non-finite rr' ends it as a
+ *   breakdown behind the update that produced it (that iteration counts).
+ *   d_info: NULL, or four device doubles {rr0, rr, iterations done, halt}, 8-byte aligned, written by plain vector stores.
+ *   ASYNCHRONOUS: one launch on `stream`, which may be capturing, like lora_plan_defect.
+ *   Status, in this order: LORA_EINVAL for a null plan, d_x or d_r, d_x == d_r, iters < 0, a sigma or tau that is not finite;
+ *   LORA_EUNSUPPORTED for a misaligned buffer, then for a plan whose option "cg_small" reads 0; then iters == 0 launches
+ *   nothing and returns LORA_OK (it needs no device); LORA_ENODEVICE without a device. */
+int lora_plan_cg_small(lora_plan *plan, void *d_x, void *d_r, int iters, double sigma, double tau, double *d_info, void *stream);
 /* The V-cycle of lora_plan_run_mg_until for A = sigma I - tau S (both finite, tau >= 0, sigma > 0).  The coarse taps stay
  * lora_mg_coarse_taps of S: A = (sigma - tau) I + tau (I - S), and only the second-order part rescales.  Per level, with w the
  * level's taps:

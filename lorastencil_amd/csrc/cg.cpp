@@ -493,6 +493,21 @@ int lora_plan_defect(lora_plan *plan, const void *d_u, const void *d_f, void *d_
                             "defect launch");
 }
 
+// ---- the whole small CG in one launch (kernels_cg_small.hip) ------------------------------------------------------
+int lora_plan_cg_small(lora_plan *plan, void *d_x, void *d_r, int iters, double sigma, double tau, double *d_info, void *stream) {
+    if (!plan || !d_x || !d_r || d_x == d_r || iters < 0 || !std::isfinite(sigma) || !std::isfinite(tau)) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_x, d_r)) return rc;
+    const Plan &p = plan->p;
+    if (!lora::has_cg_small(p))
+        return lora::unsupported("this plan has no one-launch conjugate-gradient kernel (option \"cg_small\"): it takes the 2D and 3D plans "
+                                 "with the conjugate-gradient kernels whose interior fits one workgroup");
+    if (iters == 0) return LORA_OK;  // nothing to launch: needs no device
+    if (lora_device_count() <= 0) return lora::no_device();
+    return lora::hip_status(lora::launch_cg_small(p, static_cast<double *>(d_x), static_cast<double *>(d_r), iters, sigma, tau, d_info,
+                                                  static_cast<hipStream_t>(stream)),
+                            "cg_small launch");
+}
+
 int lora_plan_prepare_theta(lora_plan *plan, int steps) {
     if (!plan || steps < 0) return LORA_EINVAL;
     if (!lora::has_cg(plan->p)) return lora::no_cg_kernels(plan->p);

@@ -42,6 +42,8 @@
 //   --precond=mg[:N]   (lorastencil_2d, lorastencil_3d, with --implicit=TAU) every step's solve preconditioned with one V(N,N)
 //                      cycle for the step's operator (lora_run_host_theta_mg; default N = 2); the state is read back every
 //                      --check-every=N iterations (any N >= 1, default 2)
+//   --coarse1          (lorastencil_2d, lorastencil_3d, with --mg, --pcg or --implicit=TAU --precond=mg) the cycles run a coarsest
+//                      level that fits one workgroup as ONE launch (lora_set_default_coarse1; plan option coarse1); same output
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -166,7 +168,7 @@ int main(int argc, char *argv[]) {
     double leapfrog_c = -1.0;
     bool chebyshev = false;
     double chebyshev_rho = 0.0;
-    bool leap3 = false;
+    bool leap3 = false, coarse1 = false;
     bool cg = false;
     bool mg = false, check_every_given = false, pcg = false, precond = false;
     int pcg_smooth = 2, precond_smooth = 2;
@@ -233,6 +235,8 @@ int main(int argc, char *argv[]) {
         }
         else if (a == "--leap3" && kDim == 3)
             leap3 = true;
+        else if (a == "--coarse1" && kDim >= 2)
+            coarse1 = true;
         else if (a == "--cg")
             cg = true;
         else if ((a == "--mg" || a.rfind("--mg=", 0) == 0) && kDim >= 2) {
@@ -429,6 +433,11 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     if (leap3) lora_set_default_leap3(1);
+    if (coarse1 && !mg && !pcg && !precond) {
+        std::cerr << "--coarse1 chooses the launches of a multigrid cycle's coarsest level: only with --mg, --pcg or --precond=mg\n";
+        return 1;
+    }
+    if (coarse1) lora_set_default_coarse1(1);
 
     if (until && (gpus_given || grid[0] > 0 || check)) {
         std::cerr << "--until runs on one GPU against its own residual: not with --gpus, --grid or --check\n";

@@ -111,6 +111,7 @@ struct Plan : Resolved {
     int lanes3 = -1;          // 3D fused launches through the register-resident kernels (kernels_3d_lanes.hip, fp64; kernels_3d_bf16_lanes.hip, bf16: four applications per launch): -1 by grid size, 0 never, 1 always (star / separable box taps, reference boundary)
     int fused_z_chunk = 0;    // 3D fused: output planes per workgroup (0 = auto: 32, shorter on small grids)
     int leap3 = 0;            // 3D fp64: leapfrog runs take the two-step launch (kernels_3d_step2.hip); no effect outside 3D
+    int coarse1 = 0;          // multigrid cycles of this plan run a coarsest level that fits as ONE launch (lora_plan_cg_small; mg.cpp)
     int spans3 = -1;          // 3D register-resident kernels: cut the (tile, plane) line into equal pieces per CU (1), equal chunks per tile (0), by region depth (-1)
     int torus = 1;            // periodic boundary: runs in fused launches on a ghost-extended grid (1), single sweeps behind a wrap each (0)
     int steps_per_launch_req = 0;  // 0 = auto, 1, 2 (2D / 3D), 3 / 4 (3D), 4 / 6 (2D), 2 .. 32 (1D)
@@ -304,6 +305,28 @@ hipError_t launch_theta_start(const Plan &p, const ResidualTiles &rt, const doub
                               double *d_p, const CgState *st, ReduceRecord *partial, hipStream_t s);
 // out = fl(fl(sweep(u) + f) - u) (f == nullptr: no addition) on those cells: no record, no fold (lora_plan_defect)
 hipError_t launch_defect(const Plan &p, const ResidualTiles &rt, const double *d_u, const double *d_f, double *d_out, hipStream_t s);
+
+// ---- the whole small CG in one launch of one workgroup (kernels_cg_small.hip; host side: cg.cpp) -----------------
+// Size admission.  A lane keeps x, r, p, q of its cells in registers: a 1024-lane workgroup has 128 VGPRs a lane, and four cells
+// (32 VGPRs of state, the addresses and a tap sum beside them) stay far from spilling -- 4096 cells.  p in its ring of zeros and
+// the waves' partial sums must fit 64 KiB of LDS, what a launch gets without asking for more and well inside the CU's 160 KiB,
+// so that a workgroup of another stream still finds room beside it.  Admits 4 x 512, 32 x 32, 12 x 12 x 12; not 4 x 1024.
+constexpr int kCgSmallCellsPerLane = 4;
+constexpr long kCgSmallMaxCells = 1024L * kCgSmallCellsPerLane;
+constexpr size_t kCgSmallMaxLds = 64 * 1024;
+inline size_t cg_small_lds_bytes(const Plan &p) {  // 2 x 16 wave sums, then p with a ring of 3 (2D) / 1 (3D) zeros per side
+    const double cells = p.ndim == 2 ? (p.dims[0] + 6.0) * (p.dims[1] + 6.0) : (p.dims[0] + 2.0) * (p.dims[1] + 2.0) * (p.dims[2] + 2.0);
+    return cells > 1e9 ? (size_t) 1 << 40 : sizeof(double) * (32 + (size_t) cells);
+}
+// Whether lora_plan_cg_small takes the plan: the CG plans of 2D / 3D shapes that fit.  Read-only option "cg_small".
+inline bool has_cg_small(const Plan &p) {
+    if (!has_cg(p) || p.ndim < 2) return false;
+    double cells = 1.0;
+    for (int a = 0; a < p.ndim; ++a) cells *= p.dims[a];
+    return cells <= (double) kCgSmallMaxCells && cg_small_lds_bytes(p) <= kCgSmallMaxLds;
+}
+// `iters` >= 1 iterations on the interiors of d_x and d_r (the residual); d_info: nullptr or {rr0, rr, iterations, halt}
+hipError_t launch_cg_small(const Plan &p, double *d_x, double *d_r, int iters, double sigma, double tau, double *d_info, hipStream_t s);
 
 // ---- geometric multigrid (kernels_mg.hip; host side: mg.cpp) ------------------------------------------------------
 // The extents of the next coarser grid (lora_mg_coarse_dims): LORA_OK, LORA_EUNSUPPORTED for 1D or an extent below 4.

@@ -174,12 +174,14 @@ void mg_release(lora_plan *plan) {
 
 namespace {
 
-// an internal plan of the hierarchy: the thread's defaults (boundary, normalised taps) must not reach it
+// an internal plan of the hierarchy: the thread's defaults (boundary, normalised taps, coarse1) must not reach it
 int make_plan(lora_plan **out, int shape, const int *dims, const double *taps, int ntaps, int boundary) {
     const int old_bc = lora_set_default_boundary(LORA_BC_REFERENCE), old_norm = lora_set_default_normalize(0);
+    const int old_c1 = lora_set_default_coarse1(0);
     int rc = lora_plan_create(out, shape, LORA_F64, dims, nullptr);
     lora_set_default_boundary(old_bc);
     lora_set_default_normalize(old_norm);
+    lora_set_default_coarse1(old_c1);
     if (rc == LORA_OK) rc = lora_plan_set_weights(*out, taps, ntaps);
     if (rc == LORA_OK) rc = lora_plan_set_boundary(*out, boundary);
     // launched directly and through two grids alone: no graph, no scratch grid (neither moves a bit)
@@ -289,6 +291,13 @@ struct Run {
 int cycle(const Run &r, int l, Tally &tally) {
     Level &lv = r.h->levels[l];
     if (l == r.L) {
+        // plan option coarse1: a coarsest level that fits one workgroup is ONE launch -- lora_plan_cg_small on the
+        // level's plain plan, from the residual the restriction put into its r
+        if (r.plan->p.coarse1 && has_cg_small(lv.plain->p)) {
+            if (int rc = lora_plan_cg_small(lv.plain, lv.cur, lv.plain->cg[0].ptr, r.coarse_iters, r.h->sigma, r.h->tau, nullptr, r.s)) return rc;
+            tally.add(1, lv.cells, 4.0);  // x and r read, x and r written (coarse_iters >= 1: coarse_iterations())
+            return LORA_OK;
+        }
         if (int rc = cg_fixed_iterations(lv.plain, lv.cur, r.coarse_iters, r.h->sigma, r.h->tau, r.s, &tally.launches)) return rc;
         tally.bytes += 8.0 * lv.cells * (3.0 + 11.0 * r.coarse_iters);  // the copy and the dot; eleven grids an iteration (lora_run_host_cg)
         return LORA_OK;

@@ -19,6 +19,7 @@ namespace lora {
 static thread_local int g_default_boundary = LORA_BC_REFERENCE;
 static thread_local int g_default_normalize = 0;
 static thread_local int g_default_leap3 = 0;
+static thread_local int g_default_coarse1 = 0;
 
 int region_granularity(const Plan &p) { return p.ndim == 1 ? 2 : 1; }  // 2D tiles and 3D chunks may start on any row / plane
 
@@ -495,6 +496,8 @@ const Option kOptions[] = {
     range("fused_z_chunk", &Plan::fused_z_chunk, 0, 4096),
     // 3D fp64 leapfrog: two steps per launch (lora_plan_leapfrog_depth reads 2); chooses no kernel of the plain sweeps
     flag("leap3", &Plan::leap3),
+    // multigrid cycles of this plan run a coarsest level that fits as one launch (lora_plan_cg_small); chooses no kernel of a sweep
+    flag("coarse1", &Plan::coarse1),
     range("spans3", &Plan::spans3, -1, 2),
     flag("torus", &Plan::torus),
     read_only("tapset", &Plan::tapset),
@@ -509,6 +512,8 @@ const Option kOptions[] = {
     {"mg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_mg(q) ? 1 : 0; }},
     // whether the plan has the multigrid-preconditioned drivers (lora_plan_mg_precondition, lora_plan_run_pcg_until): as "mg"
     {"pcg", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_mg(q) ? 1 : 0; }},
+    // whether lora_plan_cg_small takes the plan: a CG plan of a 2D / 3D shape whose cells and LDS need fit one workgroup
+    {"cg_small", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return has_cg_small(q) ? 1 : 0; }},
     // whether the plan carries a source (lora_plan_set_source)
     {"source", nullptr, nullptr, READ_ONLY, 0, {}, [](const Plan &q) { return q.source ? 1 : 0; }},
 };
@@ -592,6 +597,7 @@ int lora_plan_create(lora_plan **out, int shape, int dtype, const int *dims, con
     p.generic = odd_inner;
     p.boundary = lora::g_default_boundary;
     p.leap3 = lora::g_default_leap3;
+    p.coarse1 = lora::g_default_coarse1;
     if (nd == 3) {
         // enough workgroups to fill 256 CUs a few times over, chunks as long as that allows
         const long tiles = (long) ((dims[2] + 127) / 128) * ((dims[1] + 15) / 16);
@@ -641,6 +647,12 @@ int lora_set_default_normalize(int on) {
 int lora_set_default_leap3(int on) {
     const int old = lora::g_default_leap3;
     lora::g_default_leap3 = on ? 1 : 0;
+    return old;
+}
+
+int lora_set_default_coarse1(int on) {
+    const int old = lora::g_default_coarse1;
+    lora::g_default_coarse1 = on ? 1 : 0;
     return old;
 }
 

@@ -354,6 +354,13 @@ def set_default_leap3(on) -> int:
     return _lib.lib().lora_set_default_leap3(1 if on else 0)
 
 
+def set_default_coarse1(on) -> int:
+    """Plan option "coarse1" (multigrid cycles run a coarsest level that fits as one launch) of the plans created afterwards on
+    this thread, the ones of run_host_mg, run_host_pcg and run_host_theta_mg included (lora_set_default_coarse1).  Returns the
+    previous value."""
+    return _lib.lib().lora_set_default_coarse1(1 if on else 0)
+
+
 class _with_source:
     """set the thread's default source for one host-operator call, restore the previous one afterwards"""
 
@@ -1039,6 +1046,13 @@ class Plan:
         be None: out = S(u) - u); no record, asynchronous (lora_plan_defect).  The halo of ``d_out`` is not touched."""
         check(_lib.lib().lora_plan_defect(self._h, _ptr(d_u), _optr(d_f), _ptr(d_out), int(begin), int(end), _stream(stream)),
               "lora_plan_defect")
+
+    def cg_small(self, d_x, d_r, iters: int, sigma: float = 1.0, tau: float = 1.0, d_info=None, stream=None):
+        """``iters`` conjugate-gradient iterations for (sigma I - tau S) on a grid that fits one workgroup, in ONE launch
+        (lora_plan_cg_small; plans whose option "cg_small" reads 1); asynchronous.  ``d_r`` holds the residual of ``d_x`` on entry;
+        only the interiors of both are read and written.  ``d_info``: None or four device doubles {rr0, rr, iterations, halt}."""
+        check(_lib.lib().lora_plan_cg_small(self._h, _ptr(d_x), _ptr(d_r), int(iters), float(sigma), float(tau), _optr(d_info),
+                                            _stream(stream)), "lora_plan_cg_small")
 
     def mg_precondition(self, d_r, d_z, sigma: float = 1.0, tau: float = 1.0, pre: int = 2, post: int = 2, omega: float = 0.8,
                         max_levels: int = 0, coarse_iters: int = 0, stream=None):
