@@ -289,6 +289,10 @@ int lora_set_default_leap3(int on);
  * lora_run_host_theta_mg (what the CLIs' --coarse1 flag sets); never of the internal plans of a multigrid hierarchy.  Returns
  * the previous value. */
 int lora_set_default_coarse1(int on);
+/* Option "mgfuse" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_mg, lora_run_host_pcg and
+ * lora_run_host_theta_mg (what the CLIs' --mgfuse flag sets); never of the internal plans of a multigrid hierarchy.  Returns
+ * the previous value. */
+int lora_set_default_mgfuse(int on);
 /* Integer options.  Results never depend on them except where stated.
  *   steps_per_launch  0 auto / 1 / 2 (2D also 4 with the row-streaming kernel and 6 with the workgroup-row kernel, 3D fp64
  *                     also 3 with the plane-streaming kernel, 1D also 4, 8, 16, 32) : applications per launch in
@@ -313,6 +317,13 @@ int lora_set_default_coarse1(int on);
  *                     sums fold in another order than the 5 launches per iteration it replaces, so the bits of a cycle
  *                     differ at rounding level (its own bit contract: lora_plan_cg_small).  Any non-zero value reads back as
  *                     1; no effect on a kernel name, signature or sweep.  Measured: DESIGN 3.13
+ *   mgfuse            0 (default) / 1 : the multigrid cycles this plan drives (lora_plan_run_mg_until, lora_plan_mg_precondition,
+ *                     lora_plan_run_pcg_until, lora_plan_run_theta_mg) compute and restrict the defect of every level below
+ *                     the coarsest in ONE launch, lora_plan_mg_defect_restrict, where lora_plan_defect into the level's free
+ *                     grid and lora_plan_mg_restrict out of it stood: one launch and two passes over the level's cells fewer
+ *                     per level, the free grid not written by that step.  Same bits either way (the entry's bit contract).
+ *                     Any non-zero value reads back as 1; no effect on a kernel name, signature or sweep; independent of
+ *                     "coarse1".  Measured: DESIGN 3.14
  *   stream3           3D fp64 fused launches: 1 = plane-streaming kernel (kernels_3d_planes.hip: LDS-DMA plane ring, three
  *                     applications per launch for the 7-point star, two for the box), 0 = the two-application tile kernel,
  *                     -1 (default) = by grid size: three applications from ~1.2e8 points (star), the plane-streaming
@@ -844,6 +855,27 @@ int lora_plan_mg_restrict(lora_plan *plan, const void *d_fine, void *d_coarse, d
  * at most 2 coarse cells per axis.  Halo cells of d_coarse are selected away before any arithmetic, so a NaN there reaches
  * nothing; the halo of d_fine is not written. */
 int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine, void *stream);
+/* The defect of u = S(u) + f restricted in the launch that computes it (NEW; plan option "mgfuse").  `plan` is
+ * the FINE level's plan and carries no source: f is an argument, as with lora_plan_defect (declared below); d_f may be NULL.
+ * d_coarse has the layout of lora_mg_coarse_dims.  ASYNCHRONOUS: exactly one kernel on `stream` and nothing else -- no host
+ * wait, no allocation; it takes a capturing stream.
+ *   BIT CONTRACT.  On every interior cell of the coarse grid d_coarse holds exactly the bits of
+ *     lora_plan_defect(plan, d_u, d_f, spare, 0, 0, stream);  lora_plan_mg_restrict(plan, spare, d_coarse, scale, stream);
+ *   without the spare grid.  That fixes two orders.  The defect of a fine interior cell is fl(fl(acc + d_f) - d_u), with
+ *   d_f == NULL fl(acc - d_u), acc with the bits lora_plan_step_region stores: the chain of fused multiply-adds of the plan's
+ *   tile family from 0 over the plan's resolved tapset in its tap order.  The restriction sums as lora_plan_mg_restrict does: per
+ *   fine row the 8 cells from the pair's first (even) column in ascending order, each integer numerator times its cell, into t;
+ *   then s = s + fl(w t) over the rows inside the planes, both ascending, w the exact integer product of the outer axes'
+ *   numerators, rows with w == 0 skipped; then fl(s coef), coef = scale prod_a rho_a / (n_a + 1) rounded once on the host in
+ *   long double.  (A term with a zero numerator adds +0.0 to a sum that began at +0.0 and cannot move a bit.)  Nothing behind the
+ *   tap sum is contracted; no atomics; the same call gives the same bits every time.
+ *   Memory: pieces of at most 16 bytes; nothing outside the three padded arrays is touched.  d_u is read halo included (its halo
+ *   holds the boundary values), d_f on interior cells alone; fine cells outside the interior have no defect and contribute
+ *   nothing; the halo of d_coarse is neither read nor written; d_u and d_f are never written.
+ *   Status, in this order: LORA_EINVAL for a null plan, d_u or d_coarse; LORA_EINVAL for a non-finite scale; LORA_EINVAL for any
+ *   two buffers equal; LORA_EUNSUPPORTED for a misaligned buffer; LORA_EUNSUPPORTED for a plan whose option "mg" reads 0;
+ *   LORA_ENODEVICE without a device. */
+int lora_plan_mg_defect_restrict(lora_plan *plan, const void *d_u, const void *d_f, void *d_coarse, double scale, void *stream);
 /* V-cycles until the TRUE residual of u = S(u) + f is small.  d_x holds the start iterate, the caller's boundary values in its
  * halo; d_f may be NULL.
  *   Levels.  Level 0 is the plan's grid with its taps w_0; level l + 1 has lora_mg_coarse_dims(dims_l) and
@@ -864,6 +896,9 @@ int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine
  *   same kernels, device-resident scalars and sticky halt flag, and no probe; a residual that vanishes exactly halts the
  *   level's remaining launches harmlessly.  With plan option "coarse1" on and a level L whose plan reads "cg_small" = 1 the level
  *   is instead ONE launch, lora_plan_cg_small(plan_L, x_L, g_L, iterations, sigma, tau) -- here and in the three drivers below.
+ *   With plan option "mgfuse" on, the defect and the restriction of every level l < L are ONE launch,
+ *   lora_plan_mg_defect_restrict(x_l, g_l -> g_(l+1)) with the same scale: the same bits in g_(l+1), rs never written -- here
+ *   and in the three drivers below.
  *   A cycle is enqueued with NO host wait inside it.  u->check_every and u->max_times count CYCLES, and any check_every >= 1 is
  *   legal here; the other rules of `u`, the stop rule and the fields of r->until are lora_plan_run_until's (times_done counts
  *   cycles).  After each round the run probes the true residual of the caller's problem, S(d_x) + f - d_x with the plan's own
@@ -902,7 +937,9 @@ int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m);
  * while it was enqueued: the number of launches (kernels and memsets; a coarsest-level iteration is five) and the bytes they
  * move when every launch reads and writes each of its grids' interiors once (a zeroing writes the padded grid).  With plan
  * option "coarse1" on and a coarsest level that reads "cg_small" = 1 that level counts as one launch and four passes over its
- * cells: 5 + 5 iters - 1 launches fewer.  LORA_EINVAL
+ * cells: 5 + 5 iters - 1 launches fewer.  With plan option "mgfuse" on the defect and the restriction of a level below the
+ * coarsest count as one launch that reads the level's cells twice with a source, once without, and writes the coarse cells
+ * once: per such level one launch and exactly 16 bytes per cell of the level fewer.  LORA_EINVAL
  * for a null pointer or a plan on which no cycle has run. */
 int lora_plan_mg_cycle_cost(const lora_plan *plan, int *launches, double *bytes);
 

@@ -53,6 +53,7 @@ from .ops import (  # noqa: F401
     run_host_until,
     separable_3x3x3,
     set_default_coarse1,
+    set_default_mgfuse,
     set_default_leap3,
     set_default_source,
     stats_merge,

@@ -198,6 +198,7 @@ SIGNATURES = {
     "lora_set_default_normalize": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_leap3": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_coarse1": (ctypes.c_int, [ctypes.c_int]),
+    "lora_set_default_mgfuse": (ctypes.c_int, [ctypes.c_int]),
     "lora_plan_set_source": (ctypes.c_int, [_vp, _vp]),
     "lora_set_default_source": (_vp, [_vp]),
     "lora_plan_set_option": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
@@ -309,6 +310,7 @@ SIGNATURES = {
     "lora_run_host_mg": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(MgResult),
                                         _ip, ctypes.c_int, ctypes.POINTER(RunInfo)]),
     "lora_plan_defect": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "lora_plan_mg_defect_restrict": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
     "lora_plan_cg_small": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _vp]),
     "lora_plan_mg_precondition": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Mg), ctypes.c_double, ctypes.c_double, _vp]),
     "lora_plan_run_pcg_until": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Mg), ctypes.POINTER(Until), ctypes.POINTER(PcgResult), _vp]),

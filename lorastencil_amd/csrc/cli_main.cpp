@@ -44,6 +44,8 @@
 //                      --check-every=N iterations (any N >= 1, default 2)
 //   --coarse1          (lorastencil_2d, lorastencil_3d, with --mg, --pcg or --implicit=TAU --precond=mg) the cycles run a coarsest
 //                      level that fits one workgroup as ONE launch (lora_set_default_coarse1; plan option coarse1); same output
+//   --mgfuse           (lorastencil_2d, lorastencil_3d, with --mg, --pcg or --implicit=TAU --precond=mg) the cycles restrict every
+//                      level's defect in the launch that computes it (lora_set_default_mgfuse; plan option mgfuse); same bits
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -168,7 +170,7 @@ int main(int argc, char *argv[]) {
     double leapfrog_c = -1.0;
     bool chebyshev = false;
     double chebyshev_rho = 0.0;
-    bool leap3 = false, coarse1 = false;
+    bool leap3 = false, coarse1 = false, mgfuse = false;
     bool cg = false;
     bool mg = false, check_every_given = false, pcg = false, precond = false;
     int pcg_smooth = 2, precond_smooth = 2;
@@ -237,6 +239,8 @@ int main(int argc, char *argv[]) {
             leap3 = true;
         else if (a == "--coarse1" && kDim >= 2)
             coarse1 = true;
+        else if (a == "--mgfuse" && kDim >= 2)
+            mgfuse = true;
         else if (a == "--cg")
             cg = true;
         else if ((a == "--mg" || a.rfind("--mg=", 0) == 0) && kDim >= 2) {
@@ -438,6 +442,11 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     if (coarse1) lora_set_default_coarse1(1);
+    if (mgfuse && !mg && !pcg && !precond) {
+        std::cerr << "--mgfuse chooses the defect and restriction launches of a multigrid cycle: only with --mg, --pcg or --precond=mg\n";
+        return 1;
+    }
+    if (mgfuse) lora_set_default_mgfuse(1);
 
     if (until && (gpus_given || grid[0] > 0 || check)) {
         std::cerr << "--until runs on one GPU against its own residual: not with --gpus, --grid or --check\n";

@@ -112,6 +112,7 @@ struct Plan : Resolved {
     int fused_z_chunk = 0;    // 3D fused: output planes per workgroup (0 = auto: 32, shorter on small grids)
     int leap3 = 0;            // 3D fp64: leapfrog runs take the two-step launch (kernels_3d_step2.hip); no effect outside 3D
     int coarse1 = 0;          // multigrid cycles of this plan run a coarsest level that fits as ONE launch (lora_plan_cg_small; mg.cpp)
+    int mgfuse = 0;           // multigrid cycles of this plan restrict a level's defect in the launch that computes it (lora_plan_mg_defect_restrict; mg.cpp)
     int spans3 = -1;          // 3D register-resident kernels: cut the (tile, plane) line into equal pieces per CU (1), equal chunks per tile (0), by region depth (-1)
     int torus = 1;            // periodic boundary: runs in fused launches on a ghost-extended grid (1), single sweeps behind a wrap each (0)
     int steps_per_launch_req = 0;  // 0 = auto, 1, 2 (2D / 3D), 3 / 4 (3D), 4 / 6 (2D), 2 .. 32 (1D)
@@ -344,6 +345,10 @@ inline bool has_mg(const Plan &p) {
 //   prolong_add  fine = fl(fine + fl(coef sum_j (prod_a num_a) coarse[j])) on every interior fine cell; coef = 1 / prod_a (n_a + 1)
 hipError_t launch_mg_restrict(int ndim, const int *dims, const int *cdims, const double *d_fine, double *d_coarse, double scale, hipStream_t s);
 hipError_t launch_mg_prolong_add(int ndim, const int *dims, const int *cdims, const double *d_coarse, double *d_fine, hipStream_t s);
+// kernels_mg_fused.hip: coarse = what launch_defect of `p` (a plan with has_mg(); f may be nullptr) into a spare grid
+// and launch_mg_restrict out of it leave on the interior of d_coarse, bit for bit, in ONE launch and without the spare grid
+hipError_t launch_mg_defect_restrict(const Plan &p, const int *cdims, const double *d_u, const double *d_f, double *d_coarse, double scale,
+                                     hipStream_t s);
 // the driver's two pointwise launches over the interior of a grid of `dims`: a = fl(a - b) and a = fl(c b)
 hipError_t launch_mg_sub(int ndim, const int *dims, double *d_a, const double *d_b, hipStream_t s);
 hipError_t launch_mg_scale(int ndim, const int *dims, double *d_a, const double *d_b, double c, hipStream_t s);

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.h"
+#include "mg_geometry.h"
 
 namespace lora {
 
@@ -42,20 +43,6 @@ struct MgArgs {
     double coef;
 };
 
-// t = q N + rem, 0 <= rem < N, for t >= 0: 32-bit division whenever t allows it
-__device__ __forceinline__ void divide(long long t, int N, int &q, int &rem) {
-    if (t <= 0x7fffffffLL) {
-        const unsigned u = (unsigned) t, d = (unsigned) N;
-        const unsigned k = u / d;
-        q = (int) k;
-        rem = (int) (u - k * d);
-    } else {
-        const long long k = t / N;
-        q = (int) k;
-        rem = (int) (t - k * N);
-    }
-}
-
 // the two coarse cells around fine cell i of an axis: 0-based j and j + 1 (j may be -1), their numerators and whether each counts
 struct Pair {
     int j;
@@ -65,7 +52,7 @@ struct Pair {
 __device__ __forceinline__ Pair prolong_pair(int i, int n, int nc) {
     const int N = n + 1;
     int J, rem;
-    divide((long long) (i + 1) * (nc + 1), N, J, rem);  // J <= nc since i + 1 < N
+    mg_divide((long long) (i + 1) * (nc + 1), N, J, rem);  // J <= nc since i + 1 < N
     Pair r;
     r.j = J - 1;
     r.w0 = (double) (N - rem);
@@ -73,19 +60,6 @@ __device__ __forceinline__ Pair prolong_pair(int i, int n, int nc) {
     r.v0 = J >= 1;
     r.v1 = rem != 0 && J < nc;
     return r;
-}
-
-// the first fine cell (0-based) that may have a positive numerator for coarse cell j: floor(j N / M)
-__device__ __forceinline__ int restrict_lo(int j, int n, int nc) {
-    int q, rem;
-    divide((long long) j * (n + 1), nc + 1, q, rem);
-    return q;
-}
-// the numerator of fine cell i for coarse cell j, 0 where it is not positive or i is outside the interior
-__device__ __forceinline__ double restrict_num(int i, int j, int n, int nc) {
-    const long long N = n + 1, d = (long long) (i + 1) * (nc + 1) - (long long) (j + 1) * N;
-    const long long a = N - (d < 0 ? -d : d);
-    return (a > 0 && i < n) ? (double) a : 0.0;
 }
 
 template <bool D3>
@@ -210,20 +184,10 @@ __global__ __launch_bounds__(kThreads) void mg_pointwise_kernel(double *__restri
     }
 }
 
-// extents as z, y, x and the padded layout of lora_padded_count: 2D pads (4, 4), 3D pads (1, 2, 4)
-void side(int ndim, const int *dims, int *n, long &row, long &plane, long &off) {
-    n[0] = ndim == 3 ? dims[0] : 1;
-    n[1] = dims[ndim - 2];
-    n[2] = dims[ndim - 1];
-    row = n[2] + 8;
-    plane = ndim == 3 ? (long) (n[1] + 4) * row : 0;
-    off = ndim == 3 ? plane + 2 * row + 4 : 4 * row + 4;
-}
-
 bool fill(MgArgs &a, int ndim, const int *dims, const int *cdims) {
     if (ndim != 2 && ndim != 3) return false;
-    side(ndim, dims, a.n, a.frow, a.fplane, a.foff);
-    side(ndim, cdims ? cdims : dims, a.nc, a.crow, a.cplane, a.coff);
+    mg_side(ndim, dims, a.n, a.frow, a.fplane, a.foff);
+    mg_side(ndim, cdims ? cdims : dims, a.nc, a.crow, a.cplane, a.coff);
     for (int d = 0; d < 3; ++d)
         if (a.n[d] < 1 || a.nc[d] < 1) return false;
     return !(a.n[2] & 1) && !(a.nc[2] & 1);
@@ -239,10 +203,7 @@ dim3 grid_of(const int *n) {
 hipError_t launch_mg_restrict(int ndim, const int *dims, const int *cdims, const double *d_fine, double *d_coarse, double scale, hipStream_t s) {
     MgArgs a;
     if (!fill(a, ndim, dims, cdims)) return hipErrorInvalidValue;
-    // scale prod_a (M_a / N_a) / prod_a N_a, rounded once
-    long double c = scale;
-    for (int d = 3 - ndim; d < 3; ++d) c = c * (long double) (a.nc[d] + 1) / ((long double) (a.n[d] + 1) * (long double) (a.n[d] + 1));
-    a.coef = (double) c;
+    a.coef = restrict_coef(ndim, a.n, a.nc, scale);
     if (ndim == 3)
         hipLaunchKernelGGL(mg_restrict_kernel<true>, grid_of(a.nc), dim3(kThreads), 0, s, d_fine, d_coarse, a);
     else

@@ -6,7 +6,8 @@
 // Coarsening is boundary-aligned and non-nested (kernels_mg.hip has the geometry): level l + 1 has floor(n / 2) cells per axis,
 // the innermost rounded down to even, and the taps of level l rescaled by (h / H)^2 per axis.  On every level but the coarsest
 // the smoother is damped Jacobi folded into the taps of an internal plan with the level's right-hand side as its source, so a
-// smoothing application is one source sweep and the level's residual one fused defect launch (kernels_theta.hip).  The same
+// smoothing application is one source sweep and the level's residual one fused defect launch (kernels_theta.hip) -- with plan
+// option mgfuse one launch that also restricts it (kernels_mg_fused.hip).  The same
 // cycle for A = sigma I - tau S is the preconditioner of the PCG drivers in cg.cpp.
 #include <hip/hip_runtime.h>
 
@@ -174,14 +175,15 @@ void mg_release(lora_plan *plan) {
 
 namespace {
 
-// an internal plan of the hierarchy: the thread's defaults (boundary, normalised taps, coarse1) must not reach it
+// an internal plan of the hierarchy: the thread's defaults (boundary, normalised taps, coarse1, mgfuse) must not reach it
 int make_plan(lora_plan **out, int shape, const int *dims, const double *taps, int ntaps, int boundary) {
     const int old_bc = lora_set_default_boundary(LORA_BC_REFERENCE), old_norm = lora_set_default_normalize(0);
-    const int old_c1 = lora_set_default_coarse1(0);
+    const int old_c1 = lora_set_default_coarse1(0), old_fuse = lora_set_default_mgfuse(0);
     int rc = lora_plan_create(out, shape, LORA_F64, dims, nullptr);
     lora_set_default_boundary(old_bc);
     lora_set_default_normalize(old_norm);
     lora_set_default_coarse1(old_c1);
+    lora_set_default_mgfuse(old_fuse);
     if (rc == LORA_OK) rc = lora_plan_set_weights(*out, taps, ntaps);
     if (rc == LORA_OK) rc = lora_plan_set_boundary(*out, boundary);
     // launched directly and through two grids alone: no graph, no scratch grid (neither moves a bit)
@@ -305,19 +307,27 @@ int cycle(const Run &r, int l, Tally &tally) {
     Level &co = r.h->levels[l + 1];
     const Plan &sp = lv.smooth->p;
     if (int rc = smooth(lv, r.m->pre, r.s, tally)) return rc;
-    // rs = fl(fl(S_s(x) + g) - x) = c_l times the level's residual, in the level's free grid: one launch, the source its argument
-    {
-        Plan bare = sp;
-        bare.source = nullptr;
-        if (int rc = defect_whole(bare, lv.cur, static_cast<const double *>(sp.source), lv.other, r.s)) return rc;
-    }
-    tally.add(1, lv.cells, sp.source ? 3.0 : 2.0);
     // the coarse right-hand side: scaled for the coarse smoother, unscaled for the coarsest level's CG
     const bool last = l + 1 == r.L;
     const double scale = last ? 1.0 / lv.desc.c : co.desc.c / lv.desc.c;
     double *g = static_cast<double *>(last ? co.plain->cg[0].ptr : co.g.ptr);
-    if (int rc = hip_status(launch_mg_restrict(r.ndim, lv.desc.dims, co.desc.dims, lv.other, g, scale, r.s), "restriction launch")) return rc;
-    tally.add(1, lv.cells + co.cells, 1.0);
+    Plan bare = sp;
+    bare.source = nullptr;
+    const double *src = static_cast<const double *>(sp.source);
+    if (r.plan->p.mgfuse) {
+        // plan option mgfuse: the defect restricted in the launch that computes it, the same bits in g; the level's
+        // free grid is not written
+        if (int rc = hip_status(launch_mg_defect_restrict(bare, co.desc.dims, lv.cur, src, g, scale, r.s), "fused defect and restriction launch"))
+            return rc;
+        tally.add(1, lv.cells, src ? 2.0 : 1.0);
+        tally.add(0, co.cells, 1.0);
+    } else {
+        // rs = fl(fl(S_s(x) + g) - x) = c_l times the level's residual, in the level's free grid: one launch, the source its argument
+        if (int rc = defect_whole(bare, lv.cur, src, lv.other, r.s)) return rc;
+        tally.add(1, lv.cells, src ? 3.0 : 2.0);
+        if (int rc = hip_status(launch_mg_restrict(r.ndim, lv.desc.dims, co.desc.dims, lv.other, g, scale, r.s), "restriction launch")) return rc;
+        tally.add(1, lv.cells + co.cells, 1.0);
+    }
     co.cur = static_cast<double *>(co.x.ptr);
     co.other = static_cast<double *>(co.spare.ptr);
     if (int rc = hip_status(hipMemsetAsync(co.cur, 0, co.bytes, r.s), "coarse start")) return rc;
@@ -458,6 +468,22 @@ int lora_plan_mg_restrict(lora_plan *plan, const void *d_fine, void *d_coarse, d
     return lora::hip_status(lora::launch_mg_restrict(p.ndim, p.dims, cdims, static_cast<const double *>(d_fine), static_cast<double *>(d_coarse),
                                                      scale, static_cast<hipStream_t>(stream)),
                             "restriction launch");
+}
+
+int lora_plan_mg_defect_restrict(lora_plan *plan, const void *d_u, const void *d_f, void *d_coarse, double scale, void *stream) {
+    if (!plan || !d_u || !d_coarse) return LORA_EINVAL;
+    if (!std::isfinite(scale)) return LORA_EINVAL;
+    if (d_u == d_coarse || d_f == d_u || d_f == d_coarse) return LORA_EINVAL;
+    if (int rc = lora::check_buffers(d_u, d_coarse)) return rc;
+    if (lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
+    const Plan &p = plan->p;
+    if (!lora::has_mg(p)) return lora::no_mg_kernels();
+    if (lora_device_count() <= 0) return lora::no_device();
+    int cdims[3] = {0, 0, 0};
+    lora::mg_coarse_dims(p.ndim, p.dims, cdims);
+    return lora::hip_status(lora::launch_mg_defect_restrict(p, cdims, static_cast<const double *>(d_u), static_cast<const double *>(d_f),
+                                                            static_cast<double *>(d_coarse), scale, static_cast<hipStream_t>(stream)),
+                            "fused defect and restriction launch");
 }
 
 int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine, void *stream) {

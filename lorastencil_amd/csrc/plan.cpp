@@ -20,6 +20,7 @@ static thread_local int g_default_boundary = LORA_BC_REFERENCE;
 static thread_local int g_default_normalize = 0;
 static thread_local int g_default_leap3 = 0;
 static thread_local int g_default_coarse1 = 0;
+static thread_local int g_default_mgfuse = 0;
 
 int region_granularity(const Plan &p) { return p.ndim == 1 ? 2 : 1; }  // 2D tiles and 3D chunks may start on any row / plane
 
@@ -498,6 +499,9 @@ const Option kOptions[] = {
     flag("leap3", &Plan::leap3),
     // multigrid cycles of this plan run a coarsest level that fits as one launch (lora_plan_cg_small); chooses no kernel of a sweep
     flag("coarse1", &Plan::coarse1),
+    // multigrid cycles of this plan restrict a level's defect in the launch that computes it (lora_plan_mg_defect_restrict); chooses
+    // no kernel of a sweep
+    flag("mgfuse", &Plan::mgfuse),
     range("spans3", &Plan::spans3, -1, 2),
     flag("torus", &Plan::torus),
     read_only("tapset", &Plan::tapset),
@@ -598,6 +602,7 @@ int lora_plan_create(lora_plan **out, int shape, int dtype, const int *dims, con
     p.boundary = lora::g_default_boundary;
     p.leap3 = lora::g_default_leap3;
     p.coarse1 = lora::g_default_coarse1;
+    p.mgfuse = lora::g_default_mgfuse;
     if (nd == 3) {
         // enough workgroups to fill 256 CUs a few times over, chunks as long as that allows
         const long tiles = (long) ((dims[2] + 127) / 128) * ((dims[1] + 15) / 16);
@@ -653,6 +658,12 @@ int lora_set_default_leap3(int on) {
 int lora_set_default_coarse1(int on) {
     const int old = lora::g_default_coarse1;
     lora::g_default_coarse1 = on ? 1 : 0;
+    return old;
+}
+
+int lora_set_default_mgfuse(int on) {
+    const int old = lora::g_default_mgfuse;
+    lora::g_default_mgfuse = on ? 1 : 0;
     return old;
 }
 

@@ -361,6 +361,13 @@ def set_default_coarse1(on) -> int:
     return _lib.lib().lora_set_default_coarse1(1 if on else 0)
 
 
+def set_default_mgfuse(on) -> int:
+    """Plan option "mgfuse" (multigrid cycles restrict a level's defect in the launch that computes it) of the plans created
+    afterwards on this thread, the ones of run_host_mg, run_host_pcg and run_host_theta_mg included (lora_set_default_mgfuse).
+    Returns the previous value."""
+    return _lib.lib().lora_set_default_mgfuse(1 if on else 0)
+
+
 class _with_source:
     """set the thread's default source for one host-operator call, restore the previous one afterwards"""
 
@@ -1046,6 +1053,13 @@ class Plan:
         be None: out = S(u) - u); no record, asynchronous (lora_plan_defect).  The halo of ``d_out`` is not touched."""
         check(_lib.lib().lora_plan_defect(self._h, _ptr(d_u), _optr(d_f), _ptr(d_out), int(begin), int(end), _stream(stream)),
               "lora_plan_defect")
+
+    def mg_defect_restrict(self, d_u, d_f, d_coarse, scale: float = 1.0, stream=None):
+        """The defect S(u) + f - u of this (fine) plan restricted into ``d_coarse`` in ONE launch (lora_plan_mg_defect_restrict):
+        bit for bit ``defect`` into a spare grid followed by ``mg_restrict``, without the spare grid; asynchronous.  ``d_f`` may be
+        None; only the interior of ``d_coarse`` (layout: ``mg_coarse_dims``) is written."""
+        check(_lib.lib().lora_plan_mg_defect_restrict(self._h, _ptr(d_u), _optr(d_f), _ptr(d_coarse), float(scale), _stream(stream)),
+              "lora_plan_mg_defect_restrict")
 
     def cg_small(self, d_x, d_r, iters: int, sigma: float = 1.0, tau: float = 1.0, d_info=None, stream=None):
         """``iters`` conjugate-gradient iterations for (sigma I - tau S) on a grid that fits one workgroup, in ONE launch
