@@ -1,4 +1,4 @@
-// device_common.h -- small device helpers shared by the 2D kernels.
+// device_common.h -- small device helpers shared by the kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,6 +32,12 @@ __host__ __device__ constexpr bool tap_on(int dy, int dx) {
     const int ay = dy < 3 ? 3 - dy : dy - 3;
     const int ax = dx < 3 ? 3 - dx : dx - 3;
     return TAPSET == TAPS2D_BOX ? true : (TAPSET == TAPS2D_STAR ? (ay == 0 || ax == 0) : (ay + ax <= 3));
+}
+
+// Which of the 27 taps a 3D instantiation evaluates (dz, dy, dx in 0..2): all of the box, the seven of the star.
+template <int TAPSET>
+__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
+    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
 }
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share one, each XCD has its own L2).

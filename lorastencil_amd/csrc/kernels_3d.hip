@@ -31,11 +31,6 @@ constexpr int kTileW = 128;
 constexpr int kLdsW = kTileW + 8;
 constexpr int kChunksPerRow = kLdsW / 2;
 
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
 struct Args3D {
     const double *in;
     double *out;

@@ -54,11 +54,6 @@ struct Taps27f {
     float w[27];
 };
 
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
 __device__ __forceinline__ float bf16_lo(unsigned pair) { return __builtin_bit_cast(float, pair << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned pair) { return __builtin_bit_cast(float, pair & 0xffff0000u); }
 // element e of a window held as bf16 pairs d[e / 2]

@@ -2,9 +2,9 @@
 // is A = I - S, S the plan's raw single sweep; fp64 plans with the fused residual kernel only.
 //
 //   apply_dot     q = fl(p - acc) on every interior cell of the range and, in the same launch, the record of dot(p, q).  `acc`
-//                 has the bits lora_plan_step_region stores for p: each kernel here RESTATES the body of its family in
-//                 kernels_residual.hip (window, tile sizes, tap order, centre value re-read from the window -- see that file and
-//                 residual_tiles.h for the walk).  That kernel has a = acc and b = centre and reduces b - a; this one STORES
+//                 has the bits lora_plan_step_region stores for p: the kernels are wrappers round tile_walk.h's walk (window,
+//                 tile sizes, tap order, centre value re-read from the window), which the residual kernels run too, and supply
+//                 the row's epilogue (ApplyRow).  The residual has a = acc and b = centre and reduces b - a; this one STORES
 //                 b - a (a separate rounding, 16-byte stores at the lane's own two cells, 8 bytes for the odd tail point in 1D:
 //                 interior cells only) and accumulates b * (b - a).  p is read once, q written once, one record per workgroup.
 //   cg_update     x = fl(x + fl(alpha p)), r = fl(r - fl(alpha q)) and the record of dot(r, r) (its amax: max |r|)
@@ -30,12 +30,13 @@
 #include "device_common.h"
 #include "reduce_device.h"
 #include "residual_tiles.h"
+#include "tile_walk.h"
 
 namespace lora {
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace walk;
 
 // N cells a lane holds of one row: a = the swept values, b = the centre values, the first `nvalid` (>= 1) of them inside the
 // region.  qv = fl(b - a), what the caller stores at the valid cells; the products b * qv of those cells go into `acc`.
@@ -53,183 +54,43 @@ __device__ __forceinline__ void apply_cells(DotAcc &acc, const double (&a)[N], c
     acc.cells<N>(x, y, valid);
 }
 
-// the workgroup's record into its own slot
-__device__ __forceinline__ void finish(DotAcc &acc, ReduceRecord *__restrict__ partial) {
-    wave_reduce(acc);
-    __shared__ ReduceRecord sh[kThreads / 64];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w) acc.merge_record(sh[w]);
-        ReduceRecord r;
-        acc.to(r);
-        partial[blockIdx.x] = r;
-    }
-}
-
 __device__ __forceinline__ bool broken(const CgState *st) { return st && st->breakdown != 0; }
 
-// ---- 1D (kernels_residual.hip: residual1d_kernel) --------------------------------------------------------------------------
+// What apply_dot does with a row's tap sums: q = fl(centre - acc) stored at the row's cells inside the region, 16 bytes, or 8 for
+// the odd 1D tail point.
+struct ApplyRow {
+    static constexpr bool kSrc = false;
+    double *__restrict__ q;
+    DotAcc acc;
+    __device__ __forceinline__ void row(double a0, double a1, d2 c, d2, int nvalid, long long idx0) {
+        const double a[2] = {a0, a1}, b[2] = {c.x, c.y};
+        double qv[2];
+        apply_cells<2>(acc, a, b, nvalid, qv);
+        if (nvalid >= 2)
+            *reinterpret_cast<d2 *>(q + idx0) = (d2){qv[0], qv[1]};
+        else
+            q[idx0] = qv[0];
+    }
+};
+
 __global__ __launch_bounds__(kThreads) void apply_dot1d_kernel(const double *__restrict__ in, double *__restrict__ q, const CgState *st,
                                                                const ResidualTiles rt, const Taps9 W, ReduceRecord *__restrict__ partial) {
     if (broken(st)) return;
-    DotAcc acc;
-    acc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o[3], n[3];
-        residual_tile_box(rt, t, o, n);
-        const int i = o[2] + 2 * (int) threadIdx.x;  // even: the region begins on an even point, tiles are 512 points
-        const int left = o[2] + n[2] - i;
-        if (left <= 0) continue;
-        double win[10];
-        if (left >= 2) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const d2 v = *reinterpret_cast<const d2 *>(in + i + 2 * k);
-                win[2 * k] = v.x;
-                win[2 * k + 1] = v.y;
-            }
-        } else {  // odd tail: one point, scalar loads stay inside the padded array
-#pragma unroll
-            for (int k = 0; k < 9; ++k) win[k] = in[i + k];
-            win[9] = 0.0;
-        }
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            a0 = fma(W.w[k], win[k], a0);
-            a1 = fma(W.w[k], win[k + 1], a1);
-        }
-        const double a[2] = {a0, a1}, b[2] = {win[4], win[5]};
-        double qv[2];
-        apply_cells<2>(acc, a, b, left >= 2 ? 2 : 1, qv);
-        if (left >= 2)
-            *reinterpret_cast<d2 *>(q + i + 4) = (d2){qv[0], qv[1]};
-        else
-            q[i + 4] = qv[0];
-    }
-    finish(acc, partial);
+    ApplyRow pol{q};
+    pol.acc.init();
+    tile_walk1d(in, nullptr, rt, W, pol);
+    finish<kThreads>(pol.acc, partial);
 }
-
-// ---- 2D (kernels_residual.hip: residual2d_kernel) --------------------------------------------------------------------------
-constexpr int kTileW = 128;
-constexpr int kLdsW = kTileW + 8;
-constexpr int kChunksPerRow = kLdsW / 2;
 
 template <int TAPSET>
 __global__ __launch_bounds__(kThreads, 3) void apply_dot2d_kernel(const double *__restrict__ in, double *__restrict__ q, const CgState *st,
                                                                   const ResidualTiles rt, const Taps49 W, ReduceRecord *__restrict__ partial) {
-    constexpr int RPT = 8;
-    constexpr int TH = 4 * RPT;
-    constexpr int LH = TH + 6;
-    constexpr int NCHUNK = LH * kChunksPerRow;
-    constexpr int NIT = (NCHUNK + 255) / 256;
-    __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
+    __shared__ __attribute__((aligned(16))) double tile[kWalk2dTile];
     if (broken(st)) return;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = tid >> 6;
-    const int m = rt.dims[1], n = rt.dims[2], ld = n + 8;
-    DotAcc dacc;
-    dacc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o[3], nn[3];
-        residual_tile_box(rt, t, o, nn);
-        const int i0 = o[1], j0 = o[2], row_end = o[1] + nn[1];
-        const int col = j0 + 2 * lane;
-        // ---- stage the input window: padded rows i0+1 .. i0+TH+6, padded columns j0 .. j0+135 (clamped into the array)
-        {
-            d2 stage[NIT];
-            const int max_row = m + 7;
-            const int max_col = n + 6;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) {
-                    const int r = k / kChunksPerRow;
-                    const int c = k - r * kChunksPerRow;
-                    const int gr = min(i0 + 1 + r, max_row);
-                    const int gc = min(j0 + 2 * c, max_col);
-                    stage[it] = *reinterpret_cast<const d2 *>(in + (size_t) gr * ld + gc);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(tile + 2 * k) = stage[it];
-            }
-        }
-        __syncthreads();
-
-        // ---- compute: lane owns tile columns 2*lane+4, 2*lane+5 (window 2*lane .. 2*lane+9)
-        double acc0[RPT], acc1[RPT];
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            acc0[r] = 0.0;
-            acc1[r] = 0.0;
-        }
-        const double *strip = tile + (wv * RPT) * kLdsW + 2 * lane;
-        d2 cur[5], nxt[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) cur[k] = *reinterpret_cast<const d2 *>(strip + 2 * k);
-#pragma unroll
-        for (int j = 0; j < RPT + 6; ++j) {
-            if (j + 1 < RPT + 6) {
-#pragma unroll
-                for (int k = 0; k < 5; ++k) nxt[k] = *reinterpret_cast<const d2 *>(strip + (j + 1) * kLdsW + 2 * k);
-            }
-            double win[10];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                win[2 * k] = cur[k].x;
-                win[2 * k + 1] = cur[k].y;
-            }
-            // input row j of the strip is tap row dy = j - r of output row r
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                const int dy = j - r;
-                if (dy >= 0 && dy < 7) {
-#pragma unroll
-                    for (int dx = 0; dx < 7; ++dx) {
-                        if (tap_on<TAPSET>(dy, dx)) {
-                            const double wt = W.w[dy * 7 + dx];
-                            acc0[r] = fma(wt, win[dx + 1], acc0[r]);
-                            acc1[r] = fma(wt, win[dx + 2], acc1[r]);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                if (j - r >= 0 && j - r < 7) asm volatile("" : "+v"(acc0[r]), "+v"(acc1[r]));
-            }
-            // output row j-6 is complete: q = centre (window row r + 3, this lane's columns) - acc at the row's two own cells
-            if (j >= 6) {
-                const int r = j - 6;
-                const int row = i0 + wv * RPT + r;
-                if (col < n && row < row_end) {  // (n and col are even: both cells or none)
-                    const d2 c = *reinterpret_cast<const d2 *>(strip + (r + 3) * kLdsW + 4);
-                    const double a[2] = {acc0[r], acc1[r]}, b[2] = {c.x, c.y};
-                    double qv[2];
-                    apply_cells<2>(dacc, a, b, 2, qv);
-                    *reinterpret_cast<d2 *>(q + (size_t) (row + 4) * ld + (col + 4)) = (d2){qv[0], qv[1]};
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 5; ++k) cur[k] = nxt[k];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();  // every wave is done with the window before the next tile's is staged
-    }
-    finish(dacc, partial);
-}
-
-// ---- 3D (kernels_residual.hip: residual3d_kernel) --------------------------------------------------------------------------
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
+    ApplyRow pol{q};
+    pol.acc.init();
+    tile_walk2d<TAPSET>(tile, in, nullptr, rt, W, pol);
+    finish<kThreads>(pol.acc, partial);
 }
 
 // (bounded to three workgroups per CU like residual3d_kernel with a source: the store's address and values are as many more
@@ -237,147 +98,12 @@ __host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
 template <int TAPSET>
 __global__ __launch_bounds__(kThreads, 3) void apply_dot3d_kernel(const double *__restrict__ in, double *__restrict__ q, const CgState *st,
                                                                   const ResidualTiles rt, const Taps27 W, ReduceRecord *__restrict__ partial) {
-    constexpr int RY = 4;
-    constexpr int TY = 4 * RY;
-    constexpr int LH = TY + 2;
-    constexpr int NCHUNK = LH * kChunksPerRow;
-    constexpr int NIT = (NCHUNK + 255) / 256;
-    __shared__ __attribute__((aligned(16))) double tile[2][LH * kLdsW];
+    __shared__ __attribute__((aligned(16))) double tile[2][kWalk3dTile];
     if (broken(st)) return;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = tid >> 6;
-    const int h = rt.dims[0], m = rt.dims[1], n = rt.dims[2], ld = n + 8;
-    const long plane = (long) (m + 4) * ld;
-    DotAcc dacc;
-    dacc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o3[3], n3[3];
-        residual_tile_box(rt, t, o3, n3);
-        const int k0 = o3[0], zc = n3[0], i0 = o3[1], j0 = o3[2], row_end = o3[1] + n3[1];
-        const int nplanes = zc + 2;  // input planes: padded k0 .. k0+zc+1
-
-        long goff[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int k = tid + it * 256;
-            const int r = k / kChunksPerRow;
-            const int c = k - r * kChunksPerRow;
-            const int gr = min(i0 + 1 + r, m + 3);  // padded rows i0+1 .. i0+TY+2
-            const int gc = min(j0 + 2 * c, n + 6);
-            goff[it] = (long) gr * ld + gc;
-        }
-        d2 stage[NIT];
-        auto load_plane = [&](int p) {
-            const double *src = in + (long) min(k0 + p, h + 1) * plane;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (NCHUNK % 256 == 0 || tid + it * 256 < NCHUNK) stage[it] = *reinterpret_cast<const d2 *>(src + goff[it]);
-            }
-        };
-        auto write_plane = [&](int buf) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(&tile[buf][2 * k]) = stage[it];
-            }
-        };
-
-        double acc0[3][RY], acc1[3][RY];
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int r = 0; r < RY; ++r) {
-                acc0[s][r] = 0.0;
-                acc1[s][r] = 0.0;
-            }
-
-        const int col = j0 + 2 * lane;
-        const bool col_ok = col < n;
-        const int strip_off = (wv * RY) * kLdsW + 2 * lane + 2;  // window = tile cols 2*lane+2 .. 2*lane+7
-        const long cell0 = (long) (i0 + wv * RY + 2) * ld + (col + 4);  // this lane's first cell inside a plane
-
-        load_plane(0);
-        write_plane(0);
-        __syncthreads();
-
-        auto consume = [&](int p, auto phase_tag) {
-            constexpr int PHASE = decltype(phase_tag)::value;
-            const bool more = p + 1 < nplanes;
-            if (more) load_plane(p + 1);
-            const double *strip = &tile[p & 1][strip_off];
-#pragma unroll
-            for (int j = 0; j < RY + 2; ++j) {
-                double win[6];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const d2 v = *reinterpret_cast<const d2 *>(strip + j * kLdsW + 2 * k);
-                    win[2 * k] = v.x;
-                    win[2 * k + 1] = v.y;
-                }
-#pragma unroll
-                for (int dz = 0; dz < 3; ++dz) {
-                    const int s = (PHASE - dz + 3) % 3;
-#pragma unroll
-                    for (int r = 0; r < RY; ++r) {
-                        const int dy = j - r;
-                        if (dy >= 0 && dy < 3) {
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) {
-                                if (tap_on3<TAPSET>(dz, dy, dx)) {
-                                    const double wt = W.w[dz * 9 + dy * 3 + dx];
-                                    acc0[s][r] = fma(wt, win[dx + 1], acc0[s][r]);
-                                    acc1[s][r] = fma(wt, win[dx + 2], acc1[s][r]);
-                                }
-                            }
-                        }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-#pragma unroll
-                for (int r = 0; r < RY; ++r) asm volatile("" : "+v"(acc0[s][r]), "+v"(acc1[s][r]));
-
-            // output plane o = p - 2 is complete; its centre plane o + 1 = p - 1 is the other buffer's
-            {
-                constexpr int s = (PHASE - 2 + 3) % 3;
-                const int o = p - 2;
-                if (o >= 0 && o < zc && col_ok) {
-                    const double *centre = &tile[(p - 1) & 1][strip_off + kLdsW + 2];  // tile row wv*RY + r + 1, cols 2*lane+4, +5
-                    const long base = (long) (k0 + o + 1) * plane + cell0;
-#pragma unroll
-                    for (int r = 0; r < RY; ++r) {
-                        if (i0 + wv * RY + r < row_end) {
-                            const d2 c = *reinterpret_cast<const d2 *>(centre + r * kLdsW);
-                            const double a[2] = {acc0[s][r], acc1[s][r]}, b[2] = {c.x, c.y};
-                            double qv[2];
-                            apply_cells<2>(dacc, a, b, 2, qv);
-                            *reinterpret_cast<d2 *>(q + base + (long) r * ld) = (d2){qv[0], qv[1]};
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < RY; ++r) {
-                    acc0[s][r] = 0.0;
-                    acc1[s][r] = 0.0;
-                }
-            }
-            // (as residual3d_kernel: the refill goes into the buffer of plane p - 1, which other waves' epilogues may still read)
-            if (p >= 2) __syncthreads();
-            if (more) write_plane((p + 1) & 1);
-            __syncthreads();
-        };
-
-        for (int p = 0; p < nplanes; p += 3) {
-            consume(p, std::integral_constant<int, 0>{});
-            if (p + 1 < nplanes) consume(p + 1, std::integral_constant<int, 1>{});
-            if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
-        }
-    }
-    finish(dacc, partial);
+    ApplyRow pol{q};
+    pol.acc.init();
+    tile_walk3d<TAPSET>(tile, in, nullptr, rt, W, pol);
+    finish<kThreads>(pol.acc, partial);
 }
 
 // ---- the pointwise kernels: a walk over the interior's 16-byte pieces (ReduceArgs of the interior box, KIND_F64X2) -----------
@@ -456,7 +182,7 @@ __global__ __launch_bounds__(kThreads, 4) void cg_pointwise_kernel(double *__res
         }
         c.advance(a);
     }
-    if constexpr (OP == CG_OP_UPDATE) finish(acc, partial);
+    if constexpr (OP == CG_OP_UPDATE) finish<kThreads>(acc, partial);
 }
 
 // ---- the fold and, behind it, the one-lane update of the scalars -----------------------------------------------------------

@@ -4,7 +4,7 @@
 //
 // BITS.  On every interior coarse cell the launch stores what that pair of launches stores.  The defect of a fine cell is
 // d = fl(fl(acc + f) - u) (no f: fl(acc - u)), acc the FMA chain of the plan's tile family from 0 over the taps of the plan's
-// resolved tapset in ascending tap order -- the tile walks of theta2d_kernel / theta3d_kernel (kernels_theta.hip), restated here
+// resolved tapset in ascending tap order -- the 2D and 3D walks of tile_walk.h (theta2d_kernel / theta3d_kernel), restated here
 // with another tile height.  The restriction is mg_restrict_kernel's (kernels_mg.hip; geometry: mg_geometry.h): per fine row the
 // 8 cells from `first` in ascending order into t0, t1 of a coarse pair, then s = s + fl(w t) over ky inside kz, both ascending,
 // rows with w == 0 skipped, then fl(s coef) with the coefficient the host rounded once.  Every operation behind the tap sum is
@@ -22,7 +22,7 @@
 //      fetched by lane shuffles, so the defect itself never reaches memory of any kind.  LDS keeps t0, t1 per fine row and coarse
 //      pair, 2.2 times smaller than the defect;
 //   4. behind a barrier a lane gathers a coarse pair from the t rows with the exact integer weights and stores 16 bytes.
-// In 3D the workgroup walks z as theta3d_kernel does, two planes of u in LDS and three planes of tap sums in registers, and
+// In 3D the workgroup walks z as tile_walk3d does, two planes of u in LDS and three planes of tap sums in registers, and
 // keeps the t of the last four fine planes in a ring: a coarse plane is gathered as soon as its last fine plane is complete.
 // Fine cells outside the interior have no defect: their numerators are 0 and whatever was computed for them is selected away,
 // exactly as mg_restrict_kernel selects a cell without a numerator away.  The halo of the coarse grid is never touched.
@@ -110,7 +110,7 @@ __device__ __forceinline__ double defect_of(double acc, double f, double c) {
     }
 }
 
-// ---- 2D (the walk of theta2d_kernel with six rows per lane) -------------------------------------------------------------------
+// ---- 2D (tile_walk.h's 2D walk, as theta2d_kernel runs it, with six rows per lane) ---------------------------------------------
 template <int TAPSET, bool SRC>
 __global__ __launch_bounds__(kThreads, 3) void mg_fused2d_kernel(const double *__restrict__ in, const double *__restrict__ f,
                                                                  double *__restrict__ coarse, const FusedArgs a, const Taps49 W) {
@@ -244,12 +244,7 @@ __global__ __launch_bounds__(kThreads, 3) void mg_fused2d_kernel(const double *_
     }
 }
 
-// ---- 3D (the walk of theta3d_kernel; a ring of four planes of t) --------------------------------------------------------------
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
+// ---- 3D (tile_walk.h's 3D walk, as theta3d_kernel runs it; a ring of four planes of t) ---------------------------------------
 template <int TAPSET, bool SRC>
 __global__ __launch_bounds__(kThreads, 3) void mg_fused3d_kernel(const double *__restrict__ in, const double *__restrict__ f,
                                                                  double *__restrict__ coarse, const FusedArgs a, const Taps27 W) {
@@ -398,7 +393,7 @@ __global__ __launch_bounds__(kThreads, 3) void mg_fused3d_kernel(const double *_
                 acc1[s][r] = 0.0;
             }
         }
-        // (as theta3d_kernel: the refill goes into the buffer of plane p - 1, which other waves' epilogues may still read)
+        // (as tile_walk3d: the refill goes into the buffer of plane p - 1, which other waves' epilogues may still read)
         if (p >= 2) __syncthreads();
         if (more) write_plane((p + 1) & 1);
         __syncthreads();

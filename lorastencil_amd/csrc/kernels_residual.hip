@@ -1,16 +1,13 @@
 // kernels_residual.hip -- one sweep's change, reduced in the sweep (lora_plan_residual; host side: reduce.cpp).
 //
 // d = sweep(in) - in over the interior of a region, as the lora_grid_diff record of a = sweep(in), b = in -- without ever
-// storing the swept level: a launch reads the grid once and writes one record per workgroup.  Each kernel here RESTATES the
-// per-point arithmetic of the single-sweep kernel of its family (kernels_1d.hip, kernels_2d.hip, kernels_3d.hip,
-// kernels_3d_bf16.hip: accumulator from 0, one fused multiply-add per tap of the plan's resolved tap set, in that family's
-// tap order; bf16: fp32, the separable T / U / out form where the plan has it, one round-to-nearest-even to bf16), so `a`
-// has the bits lora_plan_step_region would have stored, and is tiled like that kernel at ONE fixed set of tile sizes:
-//   1D        a lane owns two points: five aligned 16-byte loads, the odd tail point by scalar loads
-//   2D fp64   the (32 + 6) x 136 LDS window; when output row r completes its centre values are re-read from window row r + 3
-//   3D fp64   the double-buffered (16 + 2) x 136 plane tile; when output plane o = p - 2 completes its centre plane o + 1 is
-//             still in the OTHER buffer, so the epilogue -- and a barrier behind it -- comes before that buffer is refilled
-//   3D bf16   the same on the (16 + 2) x 264 bf16 tile, four columns per lane; d = (double) a - (double) b, one rounding
+// storing the swept level: a launch reads the grid once and writes one record per workgroup.  `a` has the bits
+// lora_plan_step_region would have stored.  The three fp64 families are wrappers: the tile walk -- window, tap order, centre
+// value re-read from the window, predicates, barriers -- is tile_walk.h's, shared with kernels_cg.hip and kernels_theta.hip, and
+// this file supplies what happens to a row's tap sums (ResidualRow: reduce_cells, with_source).  The bf16 kernel has a walk of
+// its own, the 3D fp64 one on the (16 + 2) x 264 bf16 tile with four columns per lane: it RESTATES kernels_3d_bf16.hip's
+// arithmetic (fp32, the separable T / U / out form where the plan has it, one round-to-nearest-even to bf16), and
+// d = (double) a - (double) b has one rounding.
 // Tiles, workgroups and the order of the walk: residual_tiles.h.  Workgroup g walks tiles g, g + G, ... and keeps ONE
 // DiffAcc per lane across all of them.  A lane's cells of one row (2, bf16: 4) are reduced piece-first as in
 // kernels_reduce.hip: one finite test of the piece's sum of squares, the exact cell-by-cell path only when it fails.  The
@@ -29,17 +26,18 @@
 #include "reduce_device.h"
 #include "residual_tiles.h"
 #include "step_epilogue.h"
+#include "tile_walk.h"
 
 namespace lora {
 
 namespace {
 
+using namespace walk;
+
 typedef unsigned short u16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int kThreads = 256;
 
 // N cells a lane holds of one row: a = the swept values, b = the centre values, the first `nvalid` (>= 1) of them inside the
 // region; idx0 = padded linear index of cell 0.  Cells outside count as a = b = 0, which adds nothing to any result.
@@ -85,351 +83,48 @@ __device__ __forceinline__ double with_source(double acc, double f) {
     return acc;
 }
 
-// the workgroup's record into its own slot
-__device__ __forceinline__ void finish(DiffAcc &acc, ReduceRecord *__restrict__ partial) {
-    wave_reduce(acc);
-    __shared__ ReduceRecord sh[kThreads / 64];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w) acc.merge_record(sh[w]);
-        ReduceRecord r;
-        acc.to(r);
-        partial[blockIdx.x] = r;
+// What the residual does with a row's tap sums: nothing is stored, the cells go into the lane's one DiffAcc.
+template <bool SRC>
+struct ResidualRow {
+    static constexpr bool kSrc = SRC;
+    // (3D: eight more live registers through the tap loop, so SRC = true is bounded to three workgroups per CU, as the 3D source
+    // step.  The launch is still cut by residual_tiles.h's 3D cap of 1024 workgroups (four per CU of 256): with SRC a quarter of
+    // them waits for a slot when the region has that many tiles.)
+    DiffAcc acc;
+    __device__ __forceinline__ void row(double a0, double a1, d2 c, d2 f, int nvalid, long long idx0) {
+        const double a[2] = {with_source<SRC>(a0, f.x), with_source<SRC>(a1, f.y)}, b[2] = {c.x, c.y};
+        reduce_cells<2>(acc, a, b, nvalid, idx0);
     }
-}
+};
 
-// ---- 1D (kernels_1d.hip: stencil1d_kernel) -------------------------------------------------------------------------
-// SRC: f is read at the lane's own cells only -- padded index i + 4, even: one 16-byte piece, the odd tail point by one
-// 8-byte load -- under the predicate that guards reduce_cells, so no halo cell of f is ever loaded.
 template <bool SRC>
 __global__ __launch_bounds__(kThreads) void residual1d_kernel(const double *__restrict__ in, const double *__restrict__ f, const ResidualTiles rt,
                                                               const Taps9 W, ReduceRecord *__restrict__ partial) {
-    DiffAcc acc;
-    acc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o[3], n[3];
-        residual_tile_box(rt, t, o, n);
-        const int i = o[2] + 2 * (int) threadIdx.x;  // even: the region begins on an even point, tiles are 512 points
-        const int left = o[2] + n[2] - i;
-        if (left <= 0) continue;
-        double win[10];
-        d2 fv = {0.0, 0.0};
-        if (left >= 2) {
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const d2 v = *reinterpret_cast<const d2 *>(in + i + 2 * q);
-                win[2 * q] = v.x;
-                win[2 * q + 1] = v.y;
-            }
-            if constexpr (SRC) fv = *reinterpret_cast<const d2 *>(f + i + 4);
-        } else {  // odd tail: one point, scalar loads stay inside the padded array
-#pragma unroll
-            for (int q = 0; q < 9; ++q) win[q] = in[i + q];
-            win[9] = 0.0;
-            if constexpr (SRC) fv.x = f[i + 4];
-        }
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            a0 = fma(W.w[q], win[q], a0);
-            a1 = fma(W.w[q], win[q + 1], a1);
-        }
-        const double a[2] = {with_source<SRC>(a0, fv.x), with_source<SRC>(a1, fv.y)}, b[2] = {win[4], win[5]};
-        reduce_cells<2>(acc, a, b, left >= 2 ? 2 : 1, (long long) i + 4);
-    }
-    finish(acc, partial);
+    ResidualRow<SRC> pol;
+    pol.acc.init();
+    tile_walk1d(in, f, rt, W, pol);
+    finish<kThreads>(pol.acc, partial);
 }
 
-// ---- 2D fp64 (kernels_2d.hip: stencil2d_direct_kernel at RPT = 8) ---------------------------------------------------
-constexpr int kTileW = 128;
-constexpr int kLdsW = kTileW + 8;
-constexpr int kChunksPerRow = kLdsW / 2;
-
-// SRC: a lane's 16-byte piece of f of an output row (the row's two own cells) is issued four window rows before that row
-// completes, so at most four pieces are in flight; each is predicated as the reduce_cells call it feeds.
 template <int TAPSET, bool SRC>
 __global__ __launch_bounds__(kThreads, 3) void residual2d_kernel(const double *__restrict__ in, const double *__restrict__ f,
                                                                  const ResidualTiles rt, const Taps49 W, ReduceRecord *__restrict__ partial) {
-    constexpr int RPT = 8;
-    constexpr int TH = 4 * RPT;
-    constexpr int LH = TH + 6;
-    constexpr int NCHUNK = LH * kChunksPerRow;
-    constexpr int NIT = (NCHUNK + 255) / 256;
-    constexpr int kAhead = 4;  // window rows between the load of a row's piece of f and its use: 6 (and all eight up front) spill at three workgroups per CU
-    __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = tid >> 6;
-    const int m = rt.dims[1], n = rt.dims[2], ld = n + 8;
-    DiffAcc dacc;
-    dacc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o[3], nn[3];
-        residual_tile_box(rt, t, o, nn);
-        const int i0 = o[1], j0 = o[2], row_end = o[1] + nn[1];
-        const int col = j0 + 2 * lane;
-        d2 fv[SRC ? RPT : 1] = {};
-        // ---- stage the input window: padded rows i0+1 .. i0+TH+6, padded columns j0 .. j0+135 (clamped into the array)
-        {
-            d2 stage[NIT];
-            const int max_row = m + 7;
-            const int max_col = n + 6;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) {
-                    const int r = k / kChunksPerRow;
-                    const int c = k - r * kChunksPerRow;
-                    const int gr = min(i0 + 1 + r, max_row);
-                    const int gc = min(j0 + 2 * c, max_col);
-                    stage[it] = *reinterpret_cast<const d2 *>(in + (size_t) gr * ld + gc);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(tile + 2 * k) = stage[it];
-            }
-        }
-        __syncthreads();
-
-        // ---- compute: lane owns tile columns 2*lane+4, 2*lane+5 (window 2*lane .. 2*lane+9)
-        double acc0[RPT], acc1[RPT];
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            acc0[r] = 0.0;
-            acc1[r] = 0.0;
-        }
-        const double *strip = tile + (wv * RPT) * kLdsW + 2 * lane;
-        d2 cur[5], nxt[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) cur[q] = *reinterpret_cast<const d2 *>(strip + 2 * q);
-#pragma unroll
-        for (int j = 0; j < RPT + 6; ++j) {
-            if (j + 1 < RPT + 6) {
-#pragma unroll
-                for (int q = 0; q < 5; ++q) nxt[q] = *reinterpret_cast<const d2 *>(strip + (j + 1) * kLdsW + 2 * q);
-            }
-            if constexpr (SRC) {  // the piece of f of output row j - 6 + kAhead, which completes kAhead window rows from here
-                const int r = j - 6 + kAhead;
-                if (r >= 0 && r < RPT) {
-                    const int row = i0 + wv * RPT + r;
-                    if (col < n && row < row_end) fv[r] = *reinterpret_cast<const d2 *>(f + (size_t) (row + 4) * ld + (col + 4));
-                }
-            }
-            double win[10];
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                win[2 * q] = cur[q].x;
-                win[2 * q + 1] = cur[q].y;
-            }
-            // input row j of the strip is tap row dy = j - r of output row r
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                const int dy = j - r;
-                if (dy >= 0 && dy < 7) {
-#pragma unroll
-                    for (int dx = 0; dx < 7; ++dx) {
-                        if (tap_on<TAPSET>(dy, dx)) {
-                            const double wt = W.w[dy * 7 + dx];
-                            acc0[r] = fma(wt, win[dx + 1], acc0[r]);
-                            acc1[r] = fma(wt, win[dx + 2], acc1[r]);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                if (j - r >= 0 && j - r < 7) asm volatile("" : "+v"(acc0[r]), "+v"(acc1[r]));
-            }
-            // output row j-6 is complete: its change against the centre values (window row r + 3, this lane's columns)
-            if (j >= 6) {
-                const int r = j - 6;
-                const int row = i0 + wv * RPT + r;
-                if (col < n && row < row_end) {  // (n and col are even: both cells or none)
-                    const d2 c = *reinterpret_cast<const d2 *>(strip + (r + 3) * kLdsW + 4);
-                    const d2 fr = fv[SRC ? r : 0];
-                    const double a[2] = {with_source<SRC>(acc0[r], fr.x), with_source<SRC>(acc1[r], fr.y)}, b[2] = {c.x, c.y};
-                    reduce_cells<2>(dacc, a, b, 2, (long long) (row + 4) * ld + (col + 4));
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 5; ++q) cur[q] = nxt[q];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();  // every wave is done with the window before the next tile's is staged
-    }
-    finish(dacc, partial);
+    __shared__ __attribute__((aligned(16))) double tile[kWalk2dTile];
+    ResidualRow<SRC> pol;
+    pol.acc.init();
+    tile_walk2d<TAPSET>(tile, in, f, rt, W, pol);
+    finish<kThreads>(pol.acc, partial);
 }
 
-// ---- 3D fp64 (kernels_3d.hip: stencil3d_stream_kernel at RY = 4) ----------------------------------------------------
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
-// SRC: the four 16-byte pieces of f of output plane o = p - 2 (one per row of the lane, at its two own cells) are issued at
-// the head of consume(p), beside the next plane's loads, and used in its epilogue; predicated as the reduce_cells they feed.
-// Eight more live registers through the tap loop: SRC = true is bounded to three workgroups per CU, as the 3D source step.
-// The launch is still cut by residual_tiles.h's 3D cap of 1024 workgroups (four per CU of 256): with SRC a quarter of them
-// waits for a slot when the region has that many tiles.
 template <int TAPSET, bool SRC>
 __global__ __launch_bounds__(kThreads, SRC ? 3 : 4) void residual3d_kernel(const double *__restrict__ in, const double *__restrict__ f,
                                                                            const ResidualTiles rt, const Taps27 W,
                                                                            ReduceRecord *__restrict__ partial) {
-    constexpr int RY = 4;
-    constexpr int TY = 4 * RY;
-    constexpr int LH = TY + 2;
-    constexpr int NCHUNK = LH * kChunksPerRow;
-    constexpr int NIT = (NCHUNK + 255) / 256;
-    __shared__ __attribute__((aligned(16))) double tile[2][LH * kLdsW];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = tid >> 6;
-    const int h = rt.dims[0], m = rt.dims[1], n = rt.dims[2], ld = n + 8;
-    const long plane = (long) (m + 4) * ld;
-    DiffAcc dacc;
-    dacc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o3[3], n3[3];
-        residual_tile_box(rt, t, o3, n3);
-        const int k0 = o3[0], zc = n3[0], i0 = o3[1], j0 = o3[2], row_end = o3[1] + n3[1];
-        const int nplanes = zc + 2;  // input planes: padded k0 .. k0+zc+1
-
-        long goff[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int k = tid + it * 256;
-            const int r = k / kChunksPerRow;
-            const int c = k - r * kChunksPerRow;
-            const int gr = min(i0 + 1 + r, m + 3);  // padded rows i0+1 .. i0+TY+2
-            const int gc = min(j0 + 2 * c, n + 6);
-            goff[it] = (long) gr * ld + gc;
-        }
-        d2 stage[NIT];
-        auto load_plane = [&](int p) {
-            const double *src = in + (long) min(k0 + p, h + 1) * plane;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (NCHUNK % 256 == 0 || tid + it * 256 < NCHUNK) stage[it] = *reinterpret_cast<const d2 *>(src + goff[it]);
-            }
-        };
-        auto write_plane = [&](int buf) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(&tile[buf][2 * k]) = stage[it];
-            }
-        };
-
-        double acc0[3][RY], acc1[3][RY];
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int r = 0; r < RY; ++r) {
-                acc0[s][r] = 0.0;
-                acc1[s][r] = 0.0;
-            }
-
-        const int col = j0 + 2 * lane;
-        const bool col_ok = col < n;
-        const int strip_off = (wv * RY) * kLdsW + 2 * lane + 2;  // window = tile cols 2*lane+2 .. 2*lane+7
-        const long cell0 = (long) (i0 + wv * RY + 2) * ld + (col + 4);  // this lane's first cell inside a plane
-
-        load_plane(0);
-        write_plane(0);
-        __syncthreads();
-
-        auto consume = [&](int p, auto phase_tag) {
-            constexpr int PHASE = decltype(phase_tag)::value;
-            const bool more = p + 1 < nplanes;
-            if (more) load_plane(p + 1);
-            d2 fv[SRC ? RY : 1] = {};
-            if constexpr (SRC) {
-                if (p >= 2 && p - 2 < zc && col_ok) {
-                    const double *fp = f + (long) (k0 + p - 1) * plane + cell0;  // (p >= 2: a plane inside d_f)
-#pragma unroll
-                    for (int r = 0; r < RY; ++r) {
-                        if (i0 + wv * RY + r < row_end) fv[r] = *reinterpret_cast<const d2 *>(fp + (long) r * ld);
-                    }
-                }
-            }
-            const double *strip = &tile[p & 1][strip_off];
-#pragma unroll
-            for (int j = 0; j < RY + 2; ++j) {
-                double win[6];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const d2 v = *reinterpret_cast<const d2 *>(strip + j * kLdsW + 2 * q);
-                    win[2 * q] = v.x;
-                    win[2 * q + 1] = v.y;
-                }
-#pragma unroll
-                for (int dz = 0; dz < 3; ++dz) {
-                    const int s = (PHASE - dz + 3) % 3;
-#pragma unroll
-                    for (int r = 0; r < RY; ++r) {
-                        const int dy = j - r;
-                        if (dy >= 0 && dy < 3) {
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) {
-                                if (tap_on3<TAPSET>(dz, dy, dx)) {
-                                    const double wt = W.w[dz * 9 + dy * 3 + dx];
-                                    acc0[s][r] = fma(wt, win[dx + 1], acc0[s][r]);
-                                    acc1[s][r] = fma(wt, win[dx + 2], acc1[s][r]);
-                                }
-                            }
-                        }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-#pragma unroll
-                for (int r = 0; r < RY; ++r) asm volatile("" : "+v"(acc0[s][r]), "+v"(acc1[s][r]));
-
-            // output plane o = p - 2 is complete; its centre plane o + 1 = p - 1 is the other buffer's
-            {
-                constexpr int s = (PHASE - 2 + 3) % 3;
-                const int o = p - 2;
-                if (o >= 0 && o < zc && col_ok) {
-                    const double *centre = &tile[(p - 1) & 1][strip_off + kLdsW + 2];  // tile row wv*RY + r + 1, cols 2*lane+4, +5
-                    const long base = (long) (k0 + o + 1) * plane + cell0;
-#pragma unroll
-                    for (int r = 0; r < RY; ++r) {
-                        if (i0 + wv * RY + r < row_end) {
-                            const d2 c = *reinterpret_cast<const d2 *>(centre + r * kLdsW);
-                            const d2 fr = fv[SRC ? r : 0];
-                            const double a[2] = {with_source<SRC>(acc0[s][r], fr.x), with_source<SRC>(acc1[s][r], fr.y)}, b[2] = {c.x, c.y};
-                            reduce_cells<2>(dacc, a, b, 2, base + (long) r * ld);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < RY; ++r) {
-                    acc0[s][r] = 0.0;
-                    acc1[s][r] = 0.0;
-                }
-            }
-            // the refill goes into the buffer of plane p - 1, which other waves' epilogues may still be reading: one more
-            // barrier per plane than the sweep kernel, which never looks at that buffer again
-            if (p >= 2) __syncthreads();
-            if (more) write_plane((p + 1) & 1);
-            __syncthreads();
-        };
-
-        for (int p = 0; p < nplanes; p += 3) {
-            consume(p, std::integral_constant<int, 0>{});
-            if (p + 1 < nplanes) consume(p + 1, std::integral_constant<int, 1>{});
-            if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
-        }
-    }
-    finish(dacc, partial);
+    __shared__ __attribute__((aligned(16))) double tile[2][kWalk3dTile];
+    ResidualRow<SRC> pol;
+    pol.acc.init();
+    tile_walk3d<TAPSET>(tile, in, f, rt, W, pol);
+    finish<kThreads>(pol.acc, partial);
 }
 
 // ---- 3D bf16 (kernels_3d_bf16.hip: stencil3d_bf16_kernel at RY = 4, four columns per lane) -----------------------------
@@ -647,7 +342,7 @@ __global__ __launch_bounds__(kThreads, 4) void residual3d_bf16_kernel(const u16 
             if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
         }
     }
-    finish(dacc, partial);
+    finish<kThreads>(dacc, partial);
 }
 
 template <int TAPSET>

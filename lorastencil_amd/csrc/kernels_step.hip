@@ -246,11 +246,6 @@ hipError_t launch_step2d(const Plan &p, const double *in, double *out, const dou
 }
 
 // ---- 3D fp64, even innermost extent --------------------------------------------------------------------------------------
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
 constexpr int kRY = 4;      // rows per lane: columns of 16 rows x 128
 constexpr int kZChunk = 16; // output planes per workgroup
 

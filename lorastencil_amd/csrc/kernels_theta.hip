@@ -1,7 +1,9 @@
 // kernels_theta.hip -- the two stencil launches of the implicit time stepper (host side: cg.cpp) and the fused
-// defect launch of the V-cycle (mg.cpp), siblings of apply_dot in kernels_cg.hip.  All RESTATE the tile walk of their family in kernels_residual.hip exactly as apply_dot does
-// (window, tile sizes, tap order, centre value re-read from the window; residual_tiles.h for the walk), so `acc` has the bits
-// lora_plan_step_region stores; template parameter MODE picks what happens with a finished tap sum:
+// defect launch of the V-cycle (mg.cpp), siblings of apply_dot in kernels_cg.hip.  The 1D and 2D
+// kernels are wrappers round tile_walk.h's walk, as apply_dot and the residual kernels are (window, tile sizes, tap order, centre
+// value re-read from the window; residual_tiles.h for the tiles); theta3d_kernel RESTATES tile_walk3d in a body of its own (the
+// reason stands above it).  Either way `acc` has the bits lora_plan_step_region stores; template parameter MODE picks
+// what happens with a row's finished tap sums (ThetaRow):
 //
 //   TH_SHIFT      q = fl(fl(sigma c) - fl(tau acc)), c the centre value: the operator sigma I - tau S applied to p, stored at
 //                 the lane's own two cells, and the record of dot(p, q)                               (lora_plan_apply_dot_shift)
@@ -31,12 +33,13 @@
 #include "reduce_device.h"
 #include "residual_tiles.h"
 #include "step_epilogue.h"
+#include "tile_walk.h"
 
 namespace lora {
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace walk;
 
 enum { TH_SHIFT = 0, TH_START = 1, TH_START_SRC = 2, TH_DEFECT = 3, TH_DEFECT_SRC = 4 };
 
@@ -101,208 +104,57 @@ __device__ __forceinline__ void theta_cells(DotAcc &acc, const double (&a)[N], c
     if constexpr (mode_dot(MODE)) acc.cells<N>(x, y, valid);
 }
 
-// the workgroup's record into its own slot (the defect modes write none)
+// What a mode does with a row's tap sums: the stored value at the row's cells inside the region, 16 bytes, or 8 for the odd 1D
+// tail point, to o0 and, in the start modes, o1.
 template <int MODE>
-__device__ __forceinline__ void finish(DotAcc &acc, ReduceRecord *__restrict__ partial) {
-    if constexpr (mode_dot(MODE)) {
-        wave_reduce(acc);
-        __shared__ ReduceRecord sh[kThreads / 64];
-        const int wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < kThreads / 64; ++w) acc.merge_record(sh[w]);
-            ReduceRecord r;
-            acc.to(r);
-            partial[blockIdx.x] = r;
+struct ThetaRow {
+    static constexpr bool kSrc = mode_src(MODE);
+    double *__restrict__ o0, *__restrict__ o1;
+    ThetaCoef k;
+    DotAcc acc;
+    __device__ __forceinline__ void row(double a0, double a1, d2 c, d2 f, int nvalid, long long idx0) {
+        const double a[2] = {a0, a1}, b[2] = {c.x, c.y}, ff[2] = {f.x, f.y};
+        double v[2];
+        theta_cells<MODE, 2>(acc, a, b, ff, k, nvalid, v);
+        if (nvalid >= 2) {
+            *reinterpret_cast<d2 *>(o0 + idx0) = (d2){v[0], v[1]};
+            if constexpr (mode_two(MODE)) *reinterpret_cast<d2 *>(o1 + idx0) = (d2){v[0], v[1]};
+        } else {
+            o0[idx0] = v[0];
+            if constexpr (mode_two(MODE)) o1[idx0] = v[0];
         }
     }
-}
+};
 
-// ---- 1D (kernels_cg.hip: apply_dot1d_kernel) -------------------------------------------------------------------------------
+// (the defect modes write no record: no finish(), and its 192 bytes of LDS are not theirs)
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void theta1d_kernel(const double *__restrict__ in, const double *__restrict__ f, double *__restrict__ o0,
                                                            double *__restrict__ o1, const ThetaCoef k, const CgState *st, const ResidualTiles rt,
                                                            const Taps9 W, ReduceRecord *__restrict__ partial) {
     if (halted<MODE>(st)) return;
-    DotAcc acc;
-    acc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o[3], n[3];
-        residual_tile_box(rt, t, o, n);
-        const int i = o[2] + 2 * (int) threadIdx.x;  // even: the region begins on an even point, tiles are 512 points
-        const int left = o[2] + n[2] - i;
-        if (left <= 0) continue;
-        double win[10];
-        d2 fv = {0.0, 0.0};
-        if (left >= 2) {
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const d2 v = *reinterpret_cast<const d2 *>(in + i + 2 * q);
-                win[2 * q] = v.x;
-                win[2 * q + 1] = v.y;
-            }
-            if constexpr (mode_src(MODE)) fv = *reinterpret_cast<const d2 *>(f + i + 4);
-        } else {  // odd tail: one point, scalar loads stay inside the padded array
-#pragma unroll
-            for (int q = 0; q < 9; ++q) win[q] = in[i + q];
-            win[9] = 0.0;
-            if constexpr (mode_src(MODE)) fv.x = f[i + 4];
-        }
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            a0 = fma(W.w[q], win[q], a0);
-            a1 = fma(W.w[q], win[q + 1], a1);
-        }
-        const double a[2] = {a0, a1}, c[2] = {win[4], win[5]}, ff[2] = {fv.x, fv.y};
-        double v[2];
-        theta_cells<MODE, 2>(acc, a, c, ff, k, left >= 2 ? 2 : 1, v);
-        if (left >= 2) {
-            *reinterpret_cast<d2 *>(o0 + i + 4) = (d2){v[0], v[1]};
-            if constexpr (mode_two(MODE)) *reinterpret_cast<d2 *>(o1 + i + 4) = (d2){v[0], v[1]};
-        } else {
-            o0[i + 4] = v[0];
-            if constexpr (mode_two(MODE)) o1[i + 4] = v[0];
-        }
-    }
-    finish<MODE>(acc, partial);
+    ThetaRow<MODE> pol{o0, o1, k};
+    pol.acc.init();
+    tile_walk1d(in, f, rt, W, pol);
+    if constexpr (mode_dot(MODE)) finish<kThreads>(pol.acc, partial);
 }
-
-// ---- 2D (kernels_cg.hip: apply_dot2d_kernel; the piece of f as kernels_residual.hip: residual2d_kernel<SRC>) ---------------
-constexpr int kTileW = 128;
-constexpr int kLdsW = kTileW + 8;
-constexpr int kChunksPerRow = kLdsW / 2;
 
 template <int TAPSET, int MODE>
 __global__ __launch_bounds__(kThreads, 3) void theta2d_kernel(const double *__restrict__ in, const double *__restrict__ f, double *__restrict__ o0,
                                                               double *__restrict__ o1, const ThetaCoef kc, const CgState *st,
                                                               const ResidualTiles rt, const Taps49 W, ReduceRecord *__restrict__ partial) {
-    constexpr int RPT = 8;
-    constexpr int TH = 4 * RPT;
-    constexpr int LH = TH + 6;
-    constexpr int NCHUNK = LH * kChunksPerRow;
-    constexpr int NIT = (NCHUNK + 255) / 256;
-    constexpr bool SRC = mode_src(MODE);
-    constexpr int kAhead = 4;  // window rows between the load of a row's piece of f and its use (as residual2d_kernel)
-    __shared__ __attribute__((aligned(16))) double tile[LH * kLdsW];
+    __shared__ __attribute__((aligned(16))) double tile[kWalk2dTile];
     if (halted<MODE>(st)) return;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = tid >> 6;
-    const int m = rt.dims[1], n = rt.dims[2], ld = n + 8;
-    DotAcc dacc;
-    dacc.init();
-    for (long t = blockIdx.x; t < rt.tiles; t += gridDim.x) {
-        int o[3], nn[3];
-        residual_tile_box(rt, t, o, nn);
-        const int i0 = o[1], j0 = o[2], row_end = o[1] + nn[1];
-        const int col = j0 + 2 * lane;
-        d2 fv[SRC ? RPT : 1] = {};
-        // ---- stage the input window: padded rows i0+1 .. i0+TH+6, padded columns j0 .. j0+135 (clamped into the array)
-        {
-            d2 stage[NIT];
-            const int max_row = m + 7;
-            const int max_col = n + 6;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) {
-                    const int r = k / kChunksPerRow;
-                    const int c = k - r * kChunksPerRow;
-                    const int gr = min(i0 + 1 + r, max_row);
-                    const int gc = min(j0 + 2 * c, max_col);
-                    stage[it] = *reinterpret_cast<const d2 *>(in + (size_t) gr * ld + gc);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int k = tid + it * 256;
-                if (NCHUNK % 256 == 0 || k < NCHUNK) *reinterpret_cast<d2 *>(tile + 2 * k) = stage[it];
-            }
-        }
-        __syncthreads();
-
-        // ---- compute: lane owns tile columns 2*lane+4, 2*lane+5 (window 2*lane .. 2*lane+9)
-        double acc0[RPT], acc1[RPT];
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            acc0[r] = 0.0;
-            acc1[r] = 0.0;
-        }
-        const double *strip = tile + (wv * RPT) * kLdsW + 2 * lane;
-        d2 cur[5], nxt[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) cur[q] = *reinterpret_cast<const d2 *>(strip + 2 * q);
-#pragma unroll
-        for (int j = 0; j < RPT + 6; ++j) {
-            if (j + 1 < RPT + 6) {
-#pragma unroll
-                for (int q = 0; q < 5; ++q) nxt[q] = *reinterpret_cast<const d2 *>(strip + (j + 1) * kLdsW + 2 * q);
-            }
-            if constexpr (SRC) {  // the piece of f of output row j - 6 + kAhead, which completes kAhead window rows from here
-                const int r = j - 6 + kAhead;
-                if (r >= 0 && r < RPT) {
-                    const int row = i0 + wv * RPT + r;
-                    if (col < n && row < row_end) fv[r] = *reinterpret_cast<const d2 *>(f + (size_t) (row + 4) * ld + (col + 4));
-                }
-            }
-            double win[10];
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                win[2 * q] = cur[q].x;
-                win[2 * q + 1] = cur[q].y;
-            }
-            // input row j of the strip is tap row dy = j - r of output row r
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                const int dy = j - r;
-                if (dy >= 0 && dy < 7) {
-#pragma unroll
-                    for (int dx = 0; dx < 7; ++dx) {
-                        if (tap_on<TAPSET>(dy, dx)) {
-                            const double wt = W.w[dy * 7 + dx];
-                            acc0[r] = fma(wt, win[dx + 1], acc0[r]);
-                            acc1[r] = fma(wt, win[dx + 2], acc1[r]);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                if (j - r >= 0 && j - r < 7) asm volatile("" : "+v"(acc0[r]), "+v"(acc1[r]));
-            }
-            // output row j-6 is complete: its centre values are window row r + 3, this lane's columns
-            if (j >= 6) {
-                const int r = j - 6;
-                const int row = i0 + wv * RPT + r;
-                if (col < n && row < row_end) {  // (n and col are even: both cells or none)
-                    const d2 c = *reinterpret_cast<const d2 *>(strip + (r + 3) * kLdsW + 4);
-                    const d2 fr = fv[SRC ? r : 0];
-                    const double a[2] = {acc0[r], acc1[r]}, b[2] = {c.x, c.y}, ff[2] = {fr.x, fr.y};
-                    double v[2];
-                    theta_cells<MODE, 2>(dacc, a, b, ff, kc, 2, v);
-                    const size_t cell = (size_t) (row + 4) * ld + (col + 4);
-                    *reinterpret_cast<d2 *>(o0 + cell) = (d2){v[0], v[1]};
-                    if constexpr (mode_two(MODE)) *reinterpret_cast<d2 *>(o1 + cell) = (d2){v[0], v[1]};
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 5; ++q) cur[q] = nxt[q];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();  // every wave is done with the window before the next tile's is staged
-    }
-    finish<MODE>(dacc, partial);
+    ThetaRow<MODE> pol{o0, o1, kc};
+    pol.acc.init();
+    tile_walk2d<TAPSET>(tile, in, f, rt, W, pol);
+    if constexpr (mode_dot(MODE)) finish<kThreads>(pol.acc, partial);
 }
 
-// ---- 3D (kernels_cg.hip: apply_dot3d_kernel; the pieces of f at residual3d_kernel<SRC>'s addresses, loaded in the epilogue) ---
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
+// ---- 3D: NOT on tile_walk.h.  This is tile_walk3d's walk RESTATED (geometry, staging, tap order, pins, barriers), with the pieces
+// of f loaded in the epilogue, behind the tap loop, so that they are not live through it: the stores' addresses already are.  On
+// the shared walk the box's DEFECT kernel kept its registers and waves but reloaded 58 more SGPRs from VGPR lanes and
+// lora_plan_defect lost 2 -- 4 % on box3d1r 256^3 ("The tile-walk fold, checked"); no spelling of the walk's
+// parameters gave the allocation back, so the body stays here until one does.  A fix to tile_walk3d belongs here too.
 template <int TAPSET, int MODE>
 __global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__restrict__ in, const double *__restrict__ f, double *__restrict__ o0,
                                                               double *__restrict__ o1, const ThetaCoef kc, const CgState *st,
@@ -446,7 +298,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__re
                     acc1[s][r] = 0.0;
                 }
             }
-            // (as residual3d_kernel: the refill goes into the buffer of plane p - 1, which other waves' epilogues may still read)
+            // (as tile_walk3d: the refill goes into the buffer of plane p - 1, which other waves' epilogues may still read)
             if (p >= 2) __syncthreads();
             if (more) write_plane((p + 1) & 1);
             __syncthreads();
@@ -458,7 +310,7 @@ __global__ __launch_bounds__(kThreads, 3) void theta3d_kernel(const double *__re
             if (p + 2 < nplanes) consume(p + 2, std::integral_constant<int, 2>{});
         }
     }
-    finish<MODE>(dacc, partial);
+    if constexpr (mode_dot(MODE)) finish<kThreads>(dacc, partial);
 }
 
 template <int MODE>

@@ -11,11 +11,6 @@
 
 namespace lora {
 
-template <int TAPSET>
-__host__ __device__ constexpr bool tap_on3(int dz, int dy, int dx) {
-    return TAPSET == TAPS3D_BOX ? true : (((dz != 1) + (dy != 1) + (dx != 1)) <= 1);
-}
-
 // first tap (in application order) of the dz = 0 group: the tap that opens a result plane's accumulation
 template <int TAPSET>
 __host__ __device__ constexpr int first_tap3() {

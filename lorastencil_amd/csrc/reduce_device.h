@@ -1,6 +1,6 @@
-// reduce_device.h -- device pieces the reductions share (kernels_reduce.hip, kernels_residual.hip, kernels_cg.hip): the states
-// of a difference and of a product reduction, their merge rules, the walk over a box's pieces, and the fixed orders in which
-// lanes and waves are folded.
+// reduce_device.h -- device pieces the reductions share (kernels_reduce.hip, kernels_residual.hip, kernels_cg.hip,
+// kernels_theta.hip): the states of a difference and of a product reduction, their merge rules, the walk over a box's pieces,
+// the fixed orders in which lanes and waves are folded, and finish(), which writes a workgroup's record.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -128,6 +128,25 @@ template <typename ACC>
 __device__ __forceinline__ void wave_reduce(ACC &acc) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) acc.merge_lane(m);
+}
+
+// the record of a workgroup into its own slot: lanes by wave_reduce, the waves through LDS in wave order.  THREADS is the
+// launch's block size: the number of waves folded is fixed at compile time, so a caller names it
+template <int THREADS, typename ACC>
+__device__ __forceinline__ void finish(ACC &acc, ReduceRecord *__restrict__ partial) {
+    static_assert(THREADS % 64 == 0, "whole waves");
+    constexpr int kWaves = THREADS / 64;
+    wave_reduce(acc);
+    __shared__ ReduceRecord sh[kWaves];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) acc.to(sh[wave]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kWaves; ++w) acc.merge_record(sh[w]);
+        ReduceRecord r;
+        acc.to(r);
+        partial[blockIdx.x] = r;
+    }
 }
 
 }  // namespace lora

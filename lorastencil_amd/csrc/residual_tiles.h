@@ -1,4 +1,5 @@
-// residual_tiles.h -- how a launch of the fused residual kernels (kernels_residual.hip) is cut: tile -> workgroup -> cells.
+// residual_tiles.h -- how a launch of the fused residual kernels (kernels_residual.hip) and of the other kernels on tile_walk.h's
+// walks (kernels_cg.hip, kernels_theta.hip) is cut: tile -> workgroup -> cells.
 //
 // The interior range [begin, end) of the outermost dimension (times the whole inner dimensions) is cut into TILES of fixed
 // extents per kernel family -- the tiles of the single-sweep kernels they mirror, at one fixed set of sizes:

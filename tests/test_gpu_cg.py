@@ -7,8 +7,9 @@ rho for the solver.
 
 Grids: the fp64 cases of tests/test_gpu_residual.py with their regions -- the smallest that reach every path of the tile walk
 apply_dot inherits (one cell; a partial tile and two tiles per direction; regions that begin and end inside a tile; the empty
-one; 1027 = 2 x 512 + 3: the odd tail point).  Taps are set explicitly: small symmetric integers, and non-negative symmetric
-taps divided by their sum.  Buffers are carved by tests/arena.py at offsets 16 and 240, the guard bands NaN.
+one; 1027 = 2 x 512 + 3: the odd tail point; 33 x 130: one row and one column pair in second tiles; 70 x 258 with [5, 37); 34 x
+18 x 130 whole and with regions of 1, 2 and 3 planes, which end the plane ring in each of its three phases).  Taps are set
+explicitly: small symmetric integers, and non-negative symmetric taps divided by their sum.  Buffers are carved by tests/arena.py at offsets 16 and 240, the guard bands NaN.
 """
 import functools
 import math
@@ -32,6 +33,15 @@ CASES = [
     ("star3d1r", (1, 1, 2), [(0, 0)]),
     ("box3d1r", (35, 17, 130), [(0, 0), (1, 34), (33, 35), (9, 9)]),
     ("star3d1r", (35, 17, 130), [(0, 0), (1, 34)]),
+    # the edges of the shared walk (csrc/tile_walk.h), as in tests/test_gpu_residual.py
+    ("star2d1r", (33, 130), [(0, 0)]),
+    ("star2d3r", (33, 130), [(0, 0)]),
+    ("box2d3r", (33, 130), [(0, 0)]),
+    ("star2d1r", (70, 258), [(5, 37)]),
+    ("star2d3r", (70, 258), [(5, 37)]),
+    ("box2d3r", (70, 258), [(5, 37)]),
+    ("box3d1r", (34, 18, 130), [(0, 0), (3, 4), (3, 5), (3, 6)]),
+    ("star3d1r", (34, 18, 130), [(0, 0), (3, 4), (3, 5), (3, 6)]),
 ]
 IDS = [f"{s}-{'x'.join(map(str, d))}" for s, d, _ in CASES]
 SEVERAL = [c for c in CASES if c[1] in ((1027,), (70, 260), (35, 17, 130))]
@@ -168,7 +178,7 @@ def check_apply(g, p, begin, end, what):
 @pytest.mark.parametrize("shape,dims,regions", CASES, ids=IDS)
 def test_apply_dot_integer_data(L, shape, dims, regions):
     """integers 0..99 and integer taps 1..3: |acc| <= 49 x 3 x 99, every product below 1.5e6 x 99 and their sum over at most
-    77350 cells below 2**53 -- exact in any order"""
+    79560 cells below 2**53 -- exact in any order"""
     ints = host_data(shape, dims)[0]
     p = make_plan(L, shape, dims, "int")
     for off in OFFSETS:

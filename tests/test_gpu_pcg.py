@@ -151,6 +151,17 @@ DEFECT_CASES = [
     ("box3d1r", (35, 17, 130), (1, 34)),     # two plane tiles, two row tiles, two column tiles
 ]
 DEFECT_IDS = [f"{s}-{'x'.join(map(str, d))}" for s, d, _ in DEFECT_CASES]
+DEFECT_EDGES = [  # the edges of the shared walk (csrc/tile_walk.h), as in tests/test_gpu_residual.py
+    ("1d2r", (1027,), (510, 1027)),          # two full tiles and one of three points: the odd tail point in the last piece
+    ("star2d1r", (33, 130), (1, 33)),        # one row and one column pair in second tiles
+    ("star2d3r", (33, 130), (1, 33)),
+    ("box2d3r", (33, 130), (1, 33)),
+    ("star2d1r", (70, 258), (5, 37)),        # a region that begins and ends inside a tile
+    ("star2d3r", (70, 258), (5, 37)),
+    ("box2d3r", (70, 258), (5, 37)),
+] + [(s, (34, 18, 130), (3, 3 + k)) for s in ("box3d1r", "star3d1r") for k in (1, 2, 3)]  # the plane ring ends in each of its phases
+DEFECT_IDS += [f"{s}-{'x'.join(map(str, d))}-{b}-{e}" for s, d, (b, e) in DEFECT_EDGES]
+DEFECT_CASES += DEFECT_EDGES
 
 
 @pytest.mark.parametrize("shape,dims,sub", DEFECT_CASES, ids=DEFECT_IDS)

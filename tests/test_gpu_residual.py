@@ -17,6 +17,11 @@ tiles g, g + G, ...  Per family, the smallest grids that reach each path:
   more tiles than workgroups, so that some workgroup walks a second tile
                                             (2**19 + 515,): 1026 tiles     (801, 3970): 26 x 32 = 832 tiles, 25.7 MB
                                             (3, 16401, 2) and (3, 16401, 8): 1026 tiles of one or two rows' width
+  the edges of the fp64 walk that the solvers' kernels share (csrc/tile_walk.h)
+                                            (33, 130): one row and one column pair spill into second tiles
+                                            (70, 258) with [5, 37): a region that begins and ends inside a tile
+                                            (34, 18, 130), whole and with regions of 1, 2 and 3 planes: the last consume() falls
+                                            in each of the three phases; with one plane the p >= 2 barrier is the only one reached
 Tap sets: 2D diamond / star / box through star2d1r / star2d3r / box2d3r; 3D fp64 star / box; bf16 star, separable box and the
 27-tap box (option separable = 0, and taps that do not factor) -- test_cases_reach_every_tap_set asserts it.
 """
@@ -53,6 +58,15 @@ CASES = [
     ("box3d1r", "bf16", (35, 17, 264), [(0, 0), (33, 35)], "sep0"),
     ("box3d1r", "bf16", (35, 17, 264), [(0, 0)], "nosep"),
     ("box3d1r", "bf16", (3, 16401, 8), [(0, 0)], ""),
+    # the edges of the fp64 walk the solvers' kernels share (csrc/tile_walk.h); appended, so that the indices above stay
+    ("star2d1r", "f64", (33, 130), [(0, 0)], ""),
+    ("star2d3r", "f64", (33, 130), [(0, 0)], ""),
+    ("box2d3r", "f64", (33, 130), [(0, 0)], ""),
+    ("star2d1r", "f64", (70, 258), [(5, 37)], ""),
+    ("star2d3r", "f64", (70, 258), [(5, 37)], ""),
+    ("box2d3r", "f64", (70, 258), [(5, 37)], ""),
+    ("box3d1r", "f64", (34, 18, 130), [(0, 0), (3, 4), (3, 5), (3, 6)], ""),
+    ("star3d1r", "f64", (34, 18, 130), [(0, 0), (3, 4), (3, 5), (3, 6)], ""),
 ]
 IDS = [f"{s}-{t}-{'x'.join(map(str, d))}{'-' + k if k else ''}" for s, t, d, _, k in CASES]
 SEVERAL_TILES = [c for c in CASES if c[2] in ((1027,), (70, 260), (35, 17, 130), (35, 17, 264))]

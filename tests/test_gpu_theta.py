@@ -74,7 +74,7 @@ def check_shift(g, p, sigma, tau, begin, end, what):
 @pytest.mark.parametrize("shape,dims,regions", CASES, ids=IDS)
 def test_apply_dot_shift_bits_and_records(L, shape, dims, regions):
     """integer data with the integer pairs: p <= 99, |q| <= 9 x 99 + 8 x 49 x 3 x 99, every product below 1.2e7 and their sum over
-    at most 77350 cells below 2**53 -- exact in any order; real data and (1.37, 0.61): the bound of test_gpu_cg.check_record"""
+    at most 79560 cells below 2**53 -- exact in any order; real data and (1.37, 0.61): the bound of test_gpu_cg.check_record"""
     ints, real = host_data(shape, dims)[:2]
     for kind, data in (("int", ints), ("normalised", real)):
         p = make_plan(L, shape, dims, kind)
@@ -107,7 +107,7 @@ def test_apply_dot_shift_bits_and_records(L, shape, dims, regions):
 def test_theta_start_bits_and_records(L, shape, dims, regions):
     """grids: 0 = u (its halo holds values: the stencil reads it), 1 = f with a NaN halo, 2 = r, 3 = p, both NaN everywhere
     before each call.  The yardstick sweeps with a clean copy of f as a plan's source.  Integer data, tau = 8: |r| <= 8 x (49 x
-    3 x 99 + 99), r squared below 1.4e10 and the sum over 77350 cells below 2**53; real data: check_record's bound."""
+    3 x 99 + 99), r squared below 1.4e10 and the sum over 79560 cells below 2**53; real data: check_record's bound."""
     import torch
 
     ints, real, real2 = host_data(shape, dims)[:3]

@@ -56,7 +56,7 @@ def kernels(shape, dims, reps, k_iter):
     p = torch.rand(L.padded_shape(shape, dims), device="cuda", dtype=torch.float64) * 2 - 1
     q, spare = torch.zeros_like(p), torch.zeros_like(p)
     what = {"residual": lambda: plan.residual(p), "apply_dot": lambda: plan.apply_dot(p, q), "single_sweep": lambda: plan.step(p, spare),
-            "dot": lambda: plan.dot(p, q)}
+            "dot": lambda: plan.dot(p, q), "apply_dot_again": lambda: plan.apply_dot(p, q)}  # (again: the spread of two identical calls)
     for fn in what.values():  # warm-up: code objects, the plan's record buffer
         for _ in range(3):
             fn()
@@ -68,6 +68,7 @@ def kernels(shape, dims, reps, k_iter):
     row = {"shape": shape, "dims": list(dims), "reps": reps}
     for k in what:
         row[k] = {"median_us": round(statistics.median(us[k]), 1), "min_us": round(min(us[k]), 1), "max_us": round(max(us[k]), 1)}
+    row["spread"] = round(abs(row["apply_dot_again"]["median_us"] / row["apply_dot"]["median_us"] - 1.0), 3)
     row["apply_dot_over_residual"] = round(row["apply_dot"]["median_us"] / row["residual"]["median_us"], 3)
     row["apply_dot_over_residual_plus_sweep"] = round(
         row["apply_dot"]["median_us"] / (row["residual"]["median_us"] + row["single_sweep"]["median_us"]), 3)

@@ -6,8 +6,9 @@ One process, its own plans; normalised taps.  Per grid (star2d1r 4096^2 and 1638
   1. lora_plan_theta_start (with f) beside what it stands for -- a source sweep (lora_plan_step of a plan that carries f), a
      pointwise pass the size of lora_plan_diff (two grids read; a subtraction, a scale and a copy are three such passes, each
      with a store on top) and lora_plan_dot -- and lora_plan_apply_dot_shift(9, 8) beside lora_plan_apply_dot, whose kernels
-     this change leaves as the parent commit has them.  `reps` rounds that ALTERNATE the entries, each between two device events
-     of its own; medians.  The entries with a record block, so their event pairs also hold the fold launch, the copy-back of the
+     this change leaves as the parent commit has them; lora_plan_theta_start once more (`spread`: what two identical calls differ
+     by) and lora_plan_defect with and without f, the latter twice (`defect_spread`: the launch does not block).  `reps` rounds
+     that ALTERNATE the entries, each between two device events of its own; medians.  The entries with a record block, so their event pairs also hold the fold launch, the copy-back of the
      record and the host's round trip.
 Then on star2d1r 2048^2 (u0 = the lowest eigenmode of the zero-boundary problem plus 1 % noise, f = 0):
   2. the cost of a launch that exits early: the same 8 steps at tau = 64 with max_iters = K, the largest count a step needs, and
@@ -68,7 +69,11 @@ def kernels(shape, dims, reps):
     with_f = L.Plan(shape, dims).set_weights(w).set_source(f)
     what = {"theta_start": lambda: plan.theta_start(u, f, 8.0, r, p), "source_sweep": lambda: with_f.step(u, spare),
             "diff_sized_pass": lambda: plan.diff(u, f), "dot": lambda: plan.dot(u, f),
-            "apply_dot_shift": lambda: plan.apply_dot_shift(u, spare, 9.0, 8.0), "apply_dot": lambda: plan.apply_dot(u, spare)}
+            "apply_dot_shift": lambda: plan.apply_dot_shift(u, spare, 9.0, 8.0), "apply_dot": lambda: plan.apply_dot(u, spare),
+            # the same call once more: the spread a comparison of two builds has to allow for; and the V-cycle's defect launch
+            "theta_start_again": lambda: plan.theta_start(u, f, 8.0, r, p),
+            "defect_src": lambda: plan.defect(u, f, spare), "defect": lambda: plan.defect(u, None, spare),
+            "defect_again": lambda: plan.defect(u, None, spare)}  # (does not block: a spread of its own)
     for fn in what.values():  # warm-up: code objects, the plans' record buffers
         for _ in range(3):
             fn()
@@ -85,6 +90,8 @@ def kernels(shape, dims, reps):
     row["theta_start_over_replaced"] = round(med("theta_start") / row["replaced_sweep_3_passes_dot_us"], 3)
     row["theta_start_over_source_sweep"] = round(med("theta_start") / med("source_sweep"), 3)
     row["apply_dot_shift_over_apply_dot"] = round(med("apply_dot_shift") / med("apply_dot"), 3)
+    row["spread"] = round(abs(med("theta_start_again") / med("theta_start") - 1.0), 3)
+    row["defect_spread"] = round(abs(med("defect_again") / med("defect") - 1.0), 3)
     return row
 
 
