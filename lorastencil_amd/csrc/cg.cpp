@@ -10,6 +10,11 @@
 //
 // At the end the preconditioned drivers: conjugate gradients with z = M r, M one V-cycle of mg.cpp, for u = S(u) + f
 // and for the stepper's operator, the fused defect launch's public entry, and their host-buffer operators.
+//
+// One place per idea (the second anonymous namespace): reduced_entry is the tail of the four public entries that return a
+// record; cg_rounds the round loop, stop rule, breakdown rule, history and spectrum of both CG drivers (the probe itself:
+// true_residual of reduce.cpp); bad_theta_args and theta_read_back the argument check and the read-back of the steppers.  The
+// four host-buffer operators are HostRun's open_solver / ready / timed (hostrun.cpp) round their own prepare, warm-up and call.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,13 +30,6 @@ namespace {
 int no_cg_kernels(const Plan &p) {
     return unsupported(p.source ? "a plan with a source has no conjugate-gradient kernels: the source of a CG run is a call argument"
                                 : "this plan has no conjugate-gradient kernels (bf16, the 2D matrix-pipe variant, or an odd innermost extent)");
-}
-
-// A = I - S is symmetric when the taps are point-symmetric
-bool taps_symmetric(const Plan &p) {
-    for (int t = 0; t < p.ntaps; ++t)
-        if (p.w[t] != p.w[p.ntaps - 1 - t]) return false;
-    return true;
 }
 
 // The launches of the three kernels over [begin, end) (a proper range) -- the ONE place both the public entries and the driver
@@ -169,8 +167,7 @@ int cg_fixed_iterations(lora_plan *plan, void *d_x, int iters, double sigma, dou
     CgLaunch L(p, records, s);
     if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
     // p = r on the interior, with a zero halo; rr = r.r
-    static const int pads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
-    const int *pad = pads[p.ndim - 1];
+    const int *pad = interior_pads(p.ndim);
     if (int rc = hip_status(launch_halo(p, d_p, nullptr, HALO_ZERO, s), "halo launch")) return rc;
     if (int rc = hip_status(launch_copy_interior(p.dtype, p.ndim, p.dims, d_p, pad, d_r, pad, s), "copy launch")) return rc;
     if (int rc = hip_status(launch_reduce_dot(L.a, L.kind, L.groups, d_r, d_r, records, s), "reduction kernel launch")) return rc;
@@ -192,10 +189,9 @@ int defect_whole(const Plan &p, const double *d_u, const double *d_f, double *d_
     return hip_status(launch_defect(p, rt, d_u, d_f, d_out, s), "defect launch");
 }
 
-// ---- the preconditioned drivers' shared pieces ------------------------------------------------------------------
+// ---- what the entries below share: the preconditioned drivers' pieces, the reduced public entries' tail, the
+// round loop of the two CG drivers, the steppers' argument check and read-back ------------------------------------------------
 namespace {
-
-const int kPads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
 
 // the drivers need a symmetric preconditioner: as many smoothing applications behind the coarse correction as before it
 bool asymmetric(const lora_mg *m) { return m->pre != m->post || m->pre < 1; }
@@ -214,7 +210,8 @@ int pcg_first_direction(lora_plan *plan, const CgLaunch &L, const lora_mg *m, do
     double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr);
     double *d_z = static_cast<double *>(plan->pcg_z.ptr);
     if (int rc = mg_precondition(plan, d_r, d_z, m, sigma, tau, L.s)) return rc;
-    if (int rc = hip_status(launch_copy_interior(p.dtype, p.ndim, p.dims, d_p, kPads[p.ndim - 1], d_z, kPads[p.ndim - 1], L.s), "copy launch")) return rc;
+    const int *pad = interior_pads(p.ndim);
+    if (int rc = hip_status(launch_copy_interior(p.dtype, p.ndim, p.dims, d_p, pad, d_z, pad, L.s), "copy launch")) return rc;
     return L.dot_rz(d_r, d_z, st, true);
 }
 
@@ -225,6 +222,108 @@ int pcg_next_direction(lora_plan *plan, const CgLaunch &L, const lora_mg *m, dou
     if (int rc = mg_precondition(plan, d_r, d_z, m, sigma, tau, L.s)) return rc;
     if (int rc = L.dot_rz(d_r, d_z, st, false)) return rc;
     return L.direction(d_p, d_z, 0.0, st);
+}
+
+// The tail of lora_plan_apply_dot, _cg_update, _apply_dot_shift and _theta_start, behind their own argument checks: the plan's
+// kernels, the reduction's admission of (d_a, d_b), the empty record, the launches of `call` (one member of CgLaunch) over
+// [begin, end) and the folded record (blocks).  some: reduction_range's answer.
+template <class Call>
+int reduced_entry(lora_plan *plan, const void *d_a, const void *d_b, int some, int begin, int end, lora_grid_dot *out, void *stream, Call call) {
+    const Plan &p = plan->p;
+    if (!has_cg(p)) return no_cg_kernels(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = admit_reduction(d_a, d_b, s)) return rc;
+    *out = {0.0, 0.0, 0, 0};
+    if (!some) return LORA_OK;
+    ReduceRecord *records = nullptr;
+    if (int rc = reduction_records(plan, &records)) return rc;
+    CgLaunch L(p, records, s);
+    if (!L.setup(begin, end)) return LORA_EINVAL;
+    if (int rc = call(L)) return rc;
+    return L.result(out);
+}
+
+// The rounds of lora_plan_run_cg_until and, with `m` (whose V-cycle then gives every next direction), lora_plan_run_pcg_until,
+// behind the entry's start-up, into r->until, r->breakdown, r->lambda_min and r->lambda_max.  A round: check_every iterations
+// through L, the state back in the probe's wait, the true residual (fused under the max norm, where every deciding field is bit
+// for bit the two-pass probe's; else two passes through the plan's q), the stop rule; a breakdown ends the run, as diverged
+// unless that check converged.  Then the run's coefficients, the extreme Ritz values of their Lanczos tridiagonal and, where
+// lora_cg_spectrum took them, *rho_estimate (the CG result's: nullptr = none, the Ritz values of M A bound no radius of S).
+// Nothing is allocated before the history: on small grids the enqueue is the critical path.
+template <class Result>
+int cg_rounds(lora_plan *plan, const CgLaunch &L, const lora_mg *m, void *d_x, const void *d_f, const lora_until *u, Result *r, double *rho_estimate) {
+    void *d_r = plan->cg[0].ptr, *d_p = plan->cg[1].ptr, *d_q = plan->cg[2].ptr;
+    CgState *st = static_cast<CgState *>(plan->cg_state.ptr);
+    const int cap = plan->cg_cap;
+    const bool fused = u->norm == LORA_NORM_MAX;
+    CgState now = {};
+    lora_until_result &ur = r->until;
+    while (ur.times_done + u->check_every <= u->max_times) {
+        for (int i = 0; i < u->check_every; ++i) {
+            if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
+            if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
+            if (int rc = m ? pcg_next_direction(plan, L, m, 1.0, 1.0, st) : L.direction(d_p, d_r, 0.0, st)) return rc;
+        }
+        // the scalars come back in the probe's wait
+        if (int rc = hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, L.s), "state download")) return rc;
+        if (int rc = true_residual(plan, d_x, d_f, d_q, fused, &ur.last, L.s)) return rc;
+        ur.times_done = (int) now.iteration;
+        bool stop = until_decide(u, &ur);
+        if (now.breakdown) {
+            r->breakdown = 1;
+            if (!ur.converged) ur.diverged = 1;
+            stop = true;
+        }
+        if (stop) break;
+    }
+    const int n = ur.times_done;
+    if (n > 0) {
+        // n alphas and the n - 1 betas between them: lora_cg_spectrum reads no more, so the last beta stays on the device
+        std::vector<double> hist(2 * (size_t) n);
+        const double *d_hist = reinterpret_cast<const double *>(st + 1);
+        if (int rc = hip_status(hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * n, hipMemcpyDeviceToHost, L.s), "history download")) return rc;
+        if (n > 1)
+            if (int rc = hip_status(hipMemcpyAsync(hist.data() + n, d_hist + cap, sizeof(double) * (n - 1), hipMemcpyDeviceToHost, L.s), "history download"))
+                return rc;
+        if (int rc = hip_status(hipStreamSynchronize(L.s), "history download")) return rc;
+        if (lora_cg_spectrum(hist.data(), hist.data() + n, n, &r->lambda_min, &r->lambda_max) == LORA_OK && rho_estimate)
+            *rho_estimate = std::fmax(std::fabs(1.0 - r->lambda_min), std::fabs(1.0 - r->lambda_max));
+    }
+    return LORA_OK;
+}
+
+// what all four stepper entries refuse alike (a NaN fails every comparison)
+bool bad_theta_args(double theta, double tau, int steps, int max_iters, double rtol) {
+    return !(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) || !std::isfinite(rtol);
+}
+
+// The end of lora_plan_run_theta and lora_plan_run_theta_mg, behind their enqueue loops: the two states and the per-step history
+// come back behind the steady-state probe's synchronise, then *r and iterations[] (nullptr = not asked for).
+int theta_read_back(lora_plan *plan, const void *d_u, const void *d_f, int steps, int *iterations, lora_theta_result *r, hipStream_t s) {
+    const CgState *st = static_cast<const CgState *>(plan->cg_state.ptr);
+    const ThetaState *ts = static_cast<const ThetaState *>(plan->theta_state.ptr);
+    CgState now = {};
+    ThetaState tnow = {};
+    std::vector<long long> hist((size_t) steps);
+    if (int rc = hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
+    if (int rc = hip_status(hipMemcpyAsync(&tnow, ts, sizeof tnow, hipMemcpyDeviceToHost, s), "state download")) return rc;
+    if (int rc = hip_status(hipMemcpyAsync(hist.data(), ts + 1, sizeof(long long) * steps, hipMemcpyDeviceToHost, s), "history download")) return rc;
+    if (int rc = residual_whole(plan, d_u, d_f, &r->steady, s)) return rc;
+    r->steps_done = (int) tnow.steps_done;
+    r->breakdown = (now.breakdown & CG_HALT_BREAKDOWN) ? 1 : 0;
+    r->unconverged_steps = (int) tnow.unconverged;
+    r->last_rr0 = tnow.rr0;
+    r->last_rr = now.rr;
+    for (int step = 0; step < steps; ++step) {
+        // a step the breakdown interrupted reports the iterations applied before it; the steps behind it never ran
+        const int k = step < r->steps_done ? (int) hist[step] : (step == r->steps_done ? (int) now.iteration : 0);
+        if (iterations) iterations[step] = k;
+        if (step < r->steps_done) {
+            r->iterations_total += k;
+            if (k > r->iterations_max) r->iterations_max = k;
+        }
+    }
+    return LORA_OK;
 }
 
 }  // namespace
@@ -241,17 +340,7 @@ int lora_plan_apply_dot(lora_plan *plan, const void *d_p, void *d_q, int begin, 
     const int some = lora::reduction_range(p, begin, end);
     if (some < 0 || begin % lora::region_granularity(p) || d_p == d_q) return LORA_EINVAL;
     if (int rc = lora::check_buffers(d_p, d_q)) return rc;
-    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = lora::admit_reduction(d_p, d_q, s)) return rc;
-    *out = {0.0, 0.0, 0, 0};
-    if (!some) return LORA_OK;
-    lora::ReduceRecord *records = nullptr;
-    if (int rc = lora::reduction_records(plan, &records)) return rc;
-    CgLaunch L(p, records, s);
-    if (!L.setup(begin, end)) return LORA_EINVAL;
-    if (int rc = L.apply_dot(d_p, d_q, nullptr, 0)) return rc;
-    return L.result(out);
+    return lora::reduced_entry(plan, d_p, d_q, some, begin, end, out, stream, [&](const CgLaunch &L) { return L.apply_dot(d_p, d_q, nullptr, 0); });
 }
 
 int lora_plan_cg_update(lora_plan *plan, void *d_x, void *d_r, const void *d_p, const void *d_q, double alpha, int begin, int end,
@@ -263,17 +352,8 @@ int lora_plan_cg_update(lora_plan *plan, void *d_x, void *d_r, const void *d_p, 
     if (d_x == d_r || d_x == d_p || d_x == d_q || d_r == d_p || d_r == d_q || d_p == d_q) return LORA_EINVAL;
     if (int rc = lora::check_buffers(d_x, d_r)) return rc;
     if (int rc = lora::check_buffers(d_p, d_q)) return rc;
-    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = lora::admit_reduction(d_x, d_r, s)) return rc;
-    *out_rr = {0.0, 0.0, 0, 0};
-    if (!some) return LORA_OK;
-    lora::ReduceRecord *records = nullptr;
-    if (int rc = lora::reduction_records(plan, &records)) return rc;
-    CgLaunch L(p, records, s);
-    if (!L.setup(begin, end)) return LORA_EINVAL;
-    if (int rc = L.update(d_x, d_r, d_p, d_q, alpha, nullptr, 0)) return rc;
-    return L.result(out_rr);
+    return lora::reduced_entry(plan, d_x, d_r, some, begin, end, out_rr, stream,
+                               [&](const CgLaunch &L) { return L.update(d_x, d_r, d_p, d_q, alpha, nullptr, 0); });
 }
 
 int lora_plan_cg_direction(lora_plan *plan, void *d_p, const void *d_r, double beta, int begin, int end, void *stream) {
@@ -302,7 +382,7 @@ int lora_plan_run_cg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
     if (lora::misaligned(d_x) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
     const Plan &p = plan->p;
     if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
-    if (!lora::taps_symmetric(p))
+    if (!lora::taps_symmetric(p.w, p.ntaps))
         return lora::unsupported("conjugate gradients need point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = lora::admit_reduction(d_x, d_x, s)) return rc;
@@ -319,57 +399,14 @@ int lora_plan_run_cg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
     CgLaunch L(p, records, s);
     if (!L.setup(0, p.dims[0])) return LORA_EINVAL;
 
-    // the sweep of the start-up and of the two-pass probe: the plan's own single sweep with f as its source -- a copy of the
-    // plan's resolved state, as in lora_plan_run_chebyshev_until
-    Plan with_f = p;
-    with_f.source = d_f;
-    const lora::Apps whole = {1, 0, p.dims[0]};
     // r = fl(fl(S(x) + f) - x), p = r with a zero halo, rr = r.r -- nothing read before this run wrote it, on this stream
-    if (int rc = lora::launch_apps(with_f, whole, d_x, d_r, s)) return rc;
+    if (int rc = lora::sweep_with_source(p, d_f, d_x, d_r, s)) return rc;
     if (int rc = lora::hip_status(lora::launch_halo(p, d_p, nullptr, lora::HALO_ZERO, s), "halo launch")) return rc;
     if (int rc = L.start(d_r, d_p, d_x)) return rc;
     if (int rc = lora::hip_status(lora::launch_reduce_dot(L.a, L.kind, L.groups, d_r, d_r, records, s), "reduction kernel launch")) return rc;
     if (int rc = lora::hip_status(lora::launch_cg_fold(records, L.groups, st, lora::CG_FOLD_START, cap, s), "fold launch")) return rc;
 
-    // under the max norm every deciding field of the fused residual is bit for bit the two-pass probe's (see there)
-    const bool fused = u->norm == LORA_NORM_MAX;
-    lora::CgState now = {};
-    lora_until_result &ur = r->until;
-    while (ur.times_done + u->check_every <= u->max_times) {
-        for (int i = 0; i < u->check_every; ++i) {
-            if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
-            if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
-            if (int rc = L.direction(d_p, d_r, 0.0, st)) return rc;
-        }
-        // the scalars come back in the probe's wait
-        if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
-        if (fused) {
-            if (int rc = lora::residual_whole(plan, d_x, d_f, &ur.last, s)) return rc;
-        } else {
-            if (int rc = lora::launch_apps(with_f, whole, d_x, d_q, s)) return rc;
-            if (int rc = lora::diff_whole(plan, d_q, d_x, &ur.last, s)) return rc;
-        }
-        ur.times_done = (int) now.iteration;
-        bool stop = lora::until_decide(u, &ur);
-        if (now.breakdown) {
-            r->breakdown = 1;
-            if (!ur.converged) ur.diverged = 1;
-            stop = true;
-        }
-        if (stop) break;
-    }
-    const int n = ur.times_done;
-    if (n > 0) {
-        std::vector<double> hist(2 * (size_t) n);
-        const double *d_hist = reinterpret_cast<const double *>(st + 1);
-        if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * n, hipMemcpyDeviceToHost, s), "history download")) return rc;
-        if (int rc = lora::hip_status(hipMemcpyAsync(hist.data() + n, d_hist + cap, sizeof(double) * n, hipMemcpyDeviceToHost, s), "history download"))
-            return rc;
-        if (int rc = lora::hip_status(hipStreamSynchronize(s), "history download")) return rc;
-        if (lora_cg_spectrum(hist.data(), hist.data() + n, n, &r->lambda_min, &r->lambda_max) == LORA_OK)
-            r->rho_estimate = std::fmax(std::fabs(1.0 - r->lambda_min), std::fabs(1.0 - r->lambda_max));
-    }
-    return LORA_OK;
+    return lora::cg_rounds(plan, L, nullptr, d_x, d_f, u, r, &r->rho_estimate);
 }
 
 int lora_cg_spectrum(const double *alpha, const double *beta, int n, double *lambda_min, double *lambda_max) {
@@ -407,27 +444,16 @@ int lora_run_host_cg(int shape, const double *in, const double *source, double *
     if (!in || !out || !dims || !u || !r || lora::bad_until(u)) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("a conjugate-gradient run (its source is an argument)")) return rc;
     lora::HostRun g;
-    int rc = g.open(shape, LORA_F64, dims, params);
-    if (rc != LORA_OK) return rc;
+    if (int rc = g.open_solver(shape, dims, params, in, source)) return rc;
     lora_plan *plan = g.plan;
-    const size_t bytes = g.bytes;
-    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
     void *d_x = g.b[0], *d_f = g.b[1];
-    if ((rc = lora::hip_status(hipMemcpy(d_x, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
-    if (source)
-        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the plan's grids and state, and one warm-up application into the plan's own q
-    if ((rc = lora_plan_prepare_cg(plan, u->max_times))) return rc;
+    if (int rc = lora_plan_prepare_cg(plan, u->max_times)) return rc;
     lora_grid_dot warm;
-    if ((rc = lora_plan_apply_dot(plan, d_x, plan->cg[2].ptr, 0, 0, &warm, nullptr))) return rc;
-    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
-    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
-
-    g.tic();
-    if ((rc = lora_plan_run_cg_until(plan, d_x, d_f, u, r, g.s))) return rc;
-    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
-    g.toc();  // the start-up, the iterations and their probes
-    if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    if (int rc = lora_plan_apply_dot(plan, d_x, plan->cg[2].ptr, 0, 0, &warm, nullptr)) return rc;
+    if (int rc = g.ready()) return rc;
+    // timed: the start-up, the iterations and their probes
+    if (int rc = g.timed(out, [&] { return lora_plan_run_cg_until(plan, d_x, d_f, u, r, g.s); })) return rc;
     // per iteration: p read, q written; x, r, p, q read, x, r written; r, p read, p written
     return g.finish(r->until.times_done, 11.0, 1, quiet, info);
 }
@@ -440,17 +466,8 @@ int lora_plan_apply_dot_shift(lora_plan *plan, const void *d_p, void *d_q, doubl
     const int some = lora::reduction_range(p, begin, end);
     if (some < 0 || begin % lora::region_granularity(p) || d_p == d_q || !std::isfinite(sigma) || !std::isfinite(tau)) return LORA_EINVAL;
     if (int rc = lora::check_buffers(d_p, d_q)) return rc;
-    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = lora::admit_reduction(d_p, d_q, s)) return rc;
-    *out = {0.0, 0.0, 0, 0};
-    if (!some) return LORA_OK;
-    lora::ReduceRecord *records = nullptr;
-    if (int rc = lora::reduction_records(plan, &records)) return rc;
-    CgLaunch L(p, records, s);
-    if (!L.setup(begin, end)) return LORA_EINVAL;
-    if (int rc = L.apply_dot_shift(d_p, d_q, sigma, tau, nullptr)) return rc;
-    return L.result(out);
+    return lora::reduced_entry(plan, d_p, d_q, some, begin, end, out, stream,
+                               [&](const CgLaunch &L) { return L.apply_dot_shift(d_p, d_q, sigma, tau, nullptr); });
 }
 
 int lora_plan_theta_start(lora_plan *plan, const void *d_u, const void *d_f, double tau, void *d_r, void *d_p, int begin, int end,
@@ -462,17 +479,8 @@ int lora_plan_theta_start(lora_plan *plan, const void *d_u, const void *d_f, dou
     if (d_u == d_r || d_u == d_p || d_r == d_p || d_f == d_u || d_f == d_r || d_f == d_p) return LORA_EINVAL;
     if (int rc = lora::check_buffers(d_u, d_r)) return rc;
     if (int rc = lora::check_buffers(d_p, d_f ? d_f : d_p)) return rc;
-    if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = lora::admit_reduction(d_u, d_r, s)) return rc;
-    *out_rr = {0.0, 0.0, 0, 0};
-    if (!some) return LORA_OK;
-    lora::ReduceRecord *records = nullptr;
-    if (int rc = lora::reduction_records(plan, &records)) return rc;
-    CgLaunch L(p, records, s);
-    if (!L.setup(begin, end)) return LORA_EINVAL;
-    if (int rc = L.theta_start(d_u, d_f, tau, d_r, d_p, nullptr, nullptr)) return rc;
-    return L.result(out_rr);
+    return lora::reduced_entry(plan, d_u, d_r, some, begin, end, out_rr, stream,
+                               [&](const CgLaunch &L) { return L.theta_start(d_u, d_f, tau, d_r, d_p, nullptr, nullptr); });
 }
 
 int lora_plan_defect(lora_plan *plan, const void *d_u, const void *d_f, void *d_out, int begin, int end, void *stream) {
@@ -519,14 +527,11 @@ int lora_plan_prepare_theta(lora_plan *plan, int steps) {
 
 int lora_plan_run_theta(lora_plan *plan, void *d_u, const void *d_f, double theta, double tau, int steps, int max_iters, double rtol,
                         int *iterations, lora_theta_result *r, void *stream) {
-    if (!plan || !d_u || !r || d_f == d_u) return LORA_EINVAL;
-    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
-        !std::isfinite(rtol))
-        return LORA_EINVAL;
+    if (!plan || !d_u || !r || d_f == d_u || lora::bad_theta_args(theta, tau, steps, max_iters, rtol)) return LORA_EINVAL;
     if (lora::misaligned(d_u) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
     const Plan &p = plan->p;
     if (!lora::has_cg(p)) return lora::no_cg_kernels(p);
-    if (!lora::taps_symmetric(p))
+    if (!lora::taps_symmetric(p.w, p.ntaps))
         return lora::unsupported("the implicit stepper needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: sigma I - tau S is not symmetric otherwise");
     *r = {0, 0, 0, 0, 0, lora::kNaN, lora::kNaN, {0.0, 0.0, 0.0, -1, 0, 0}};
     if (steps == 0) return LORA_OK;
@@ -557,61 +562,24 @@ int lora_plan_run_theta(lora_plan *plan, void *d_u, const void *d_f, double thet
             if (int rc = L.direction(d_p, d_r, 0.0, st)) return rc;
         }
     }
-    // the one wait: the two states and the history come back behind the steady-state probe's synchronise
-    lora::CgState now = {};
-    lora::ThetaState tnow = {};
-    std::vector<long long> hist((size_t) steps);
-    if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
-    if (int rc = lora::hip_status(hipMemcpyAsync(&tnow, ts, sizeof tnow, hipMemcpyDeviceToHost, s), "state download")) return rc;
-    if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), ts + 1, sizeof(long long) * steps, hipMemcpyDeviceToHost, s), "history download"))
-        return rc;
-    if (int rc = lora::residual_whole(plan, d_u, d_f, &r->steady, s)) return rc;
-    r->steps_done = (int) tnow.steps_done;
-    r->breakdown = (now.breakdown & lora::CG_HALT_BREAKDOWN) ? 1 : 0;
-    r->unconverged_steps = (int) tnow.unconverged;
-    r->last_rr0 = tnow.rr0;
-    r->last_rr = now.rr;
-    for (int step = 0; step < steps; ++step) {
-        // a step the breakdown interrupted reports the iterations applied before it; the steps behind it never ran
-        const int k = step < r->steps_done ? (int) hist[step] : (step == r->steps_done ? (int) now.iteration : 0);
-        if (iterations) iterations[step] = k;
-        if (step < r->steps_done) {
-            r->iterations_total += k;
-            if (k > r->iterations_max) r->iterations_max = k;
-        }
-    }
-    return LORA_OK;
+    return lora::theta_read_back(plan, d_u, d_f, steps, iterations, r, s);  // the one wait
 }
 
 int lora_run_host_theta(int shape, const double *in, const double *source, double *out, const double *params, double theta, double tau,
                         int steps, int max_iters, double rtol, const int *dims, int quiet, lora_run_info *info, lora_theta_result *result) {
-    if (!in || !out || !dims || !result) return LORA_EINVAL;
-    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
-        !std::isfinite(rtol))
-        return LORA_EINVAL;
+    if (!in || !out || !dims || !result || lora::bad_theta_args(theta, tau, steps, max_iters, rtol)) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("an implicit run (its source is an argument)")) return rc;
     lora::HostRun g;
-    int rc = g.open(shape, LORA_F64, dims, params);
-    if (rc != LORA_OK) return rc;
+    if (int rc = g.open_solver(shape, dims, params, in, source)) return rc;
     lora_plan *plan = g.plan;
-    const size_t bytes = g.bytes;
-    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
     void *d_u = g.b[0], *d_f = g.b[1];
-    if ((rc = lora::hip_status(hipMemcpy(d_u, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
-    if (source)
-        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the plan's grids and states, and one warm-up application into the plan's own q
-    if ((rc = lora_plan_prepare_theta(plan, steps))) return rc;
+    if (int rc = lora_plan_prepare_theta(plan, steps)) return rc;
     lora_grid_dot warm;
-    if ((rc = lora_plan_apply_dot_shift(plan, d_u, plan->cg[2].ptr, 1.0, 1.0, 0, 0, &warm, nullptr))) return rc;
-    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
-    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
-
-    g.tic();
-    if ((rc = lora_plan_run_theta(plan, d_u, d_f, theta, tau, steps, max_iters, rtol, nullptr, result, g.s))) return rc;
-    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
-    g.toc();  // every step's start and iterations, and the steady-state probe
-    if ((rc = lora::hip_status(hipMemcpy(out, d_u, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    if (int rc = lora_plan_apply_dot_shift(plan, d_u, plan->cg[2].ptr, 1.0, 1.0, 0, 0, &warm, nullptr)) return rc;
+    if (int rc = g.ready()) return rc;
+    // timed: every step's start and iterations, and the steady-state probe
+    if (int rc = g.timed(out, [&] { return lora_plan_run_theta(plan, d_u, d_f, theta, tau, steps, max_iters, rtol, nullptr, result, g.s); })) return rc;
     // per step: u (and f) read, r and p written; per iteration the eleven grids of a CG iteration (lora_run_host_cg)
     const double per_step = (source ? 4.0 : 3.0) + (steps > 0 ? 11.0 * (double) result->iterations_total / steps : 0.0);
     return g.finish(steps, per_step, 1, quiet, info);
@@ -644,7 +612,7 @@ int lora_plan_run_pcg_until(lora_plan *plan, void *d_x, const void *d_f, const l
     if (!plan->pcg_z.ensure(lora_plan_padded_bytes(plan))) return LORA_ENOMEM;
     if (int rc = lora::mg_prepare(plan, m, 1.0, 1.0)) return rc;
     if (lora::owned(plan, d_x) || lora::owned(plan, d_f)) return LORA_EINVAL;
-    double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr), *d_q = static_cast<double *>(plan->cg[2].ptr);
+    double *d_r = static_cast<double *>(plan->cg[0].ptr), *d_p = static_cast<double *>(plan->cg[1].ptr);
     lora::CgState *st = static_cast<lora::CgState *>(plan->cg_state.ptr);
     const int cap = plan->cg_cap;
     lora::ReduceRecord *records = nullptr;
@@ -659,55 +627,13 @@ int lora_plan_run_pcg_until(lora_plan *plan, void *d_x, const void *d_f, const l
     if (int rc = lora::hip_status(lora::launch_halo(p, d_p, nullptr, lora::HALO_ZERO, s), "halo launch")) return rc;
     if (int rc = lora::pcg_first_direction(plan, L, m, 1.0, 1.0, st)) return rc;
 
-    Plan with_f = p;  // the sweep of the two-pass probe (as lora_plan_run_cg_until)
-    with_f.source = d_f;
-    const lora::Apps whole = {1, 0, p.dims[0]};
-    const bool fused = u->norm == LORA_NORM_MAX;
-    lora::CgState now = {};
-    lora_until_result &ur = r->until;
-    while (ur.times_done + u->check_every <= u->max_times) {
-        for (int i = 0; i < u->check_every; ++i) {
-            if (int rc = L.apply_dot(d_p, d_q, st, cap)) return rc;
-            if (int rc = L.update(d_x, d_r, d_p, d_q, 0.0, st, cap)) return rc;
-            if (int rc = lora::pcg_next_direction(plan, L, m, 1.0, 1.0, st)) return rc;
-        }
-        // the scalars come back in the probe's wait
-        if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
-        if (fused) {
-            if (int rc = lora::residual_whole(plan, d_x, d_f, &ur.last, s)) return rc;
-        } else {
-            if (int rc = lora::launch_apps(with_f, whole, d_x, d_q, s)) return rc;
-            if (int rc = lora::diff_whole(plan, d_q, d_x, &ur.last, s)) return rc;
-        }
-        ur.times_done = (int) now.iteration;
-        bool stop = lora::until_decide(u, &ur);
-        if (now.breakdown) {
-            r->breakdown = 1;
-            if (!ur.converged) ur.diverged = 1;
-            stop = true;
-        }
-        if (stop) break;
-    }
-    const int n = ur.times_done;
-    if (n > 0) {
-        std::vector<double> hist(2 * (size_t) n);
-        const double *d_hist = reinterpret_cast<const double *>(st + 1);
-        if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * n, hipMemcpyDeviceToHost, s), "history download")) return rc;
-        if (n > 1)
-            if (int rc = lora::hip_status(hipMemcpyAsync(hist.data() + n, d_hist + cap, sizeof(double) * (n - 1), hipMemcpyDeviceToHost, s), "history download"))
-                return rc;
-        if (int rc = lora::hip_status(hipStreamSynchronize(s), "history download")) return rc;
-        lora_cg_spectrum(hist.data(), hist.data() + n, n, &r->lambda_min, &r->lambda_max);
-    }
-    return LORA_OK;
+    return lora::cg_rounds(plan, L, m, d_x, d_f, u, r, nullptr);
 }
 
 int lora_plan_run_theta_mg(lora_plan *plan, void *d_u, const void *d_f, double theta, double tau, int steps, int max_iters, double rtol,
                            const lora_mg *m, int check_every, int *iterations, lora_theta_result *r, void *stream) {
     if (!plan || !d_u || !r || !m || d_f == d_u) return LORA_EINVAL;
-    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
-        !std::isfinite(rtol) || check_every < 1)
-        return LORA_EINVAL;
+    if (lora::bad_theta_args(theta, tau, steps, max_iters, rtol) || check_every < 1) return LORA_EINVAL;
     // the operator of the step and the stop rule's factor, each operation its own rounding
     const double tt = theta * tau, sigma = 1.0 + tt, rtol2 = rtol * rtol;
     if (lora::mg_bad(m, sigma, tt) || lora::asymmetric(m)) return LORA_EINVAL;
@@ -754,27 +680,7 @@ int lora_plan_run_theta_mg(lora_plan *plan, void *d_u, const void *d_f, double t
         }
         if (now.breakdown & lora::CG_HALT_BREAKDOWN) break;
     }
-    lora::ThetaState tnow = {};
-    std::vector<long long> hist((size_t) steps);
-    if (int rc = lora::hip_status(hipMemcpyAsync(&now, st, sizeof now, hipMemcpyDeviceToHost, s), "state download")) return rc;
-    if (int rc = lora::hip_status(hipMemcpyAsync(&tnow, ts, sizeof tnow, hipMemcpyDeviceToHost, s), "state download")) return rc;
-    if (int rc = lora::hip_status(hipMemcpyAsync(hist.data(), ts + 1, sizeof(long long) * steps, hipMemcpyDeviceToHost, s), "history download"))
-        return rc;
-    if (int rc = lora::residual_whole(plan, d_u, d_f, &r->steady, s)) return rc;
-    r->steps_done = (int) tnow.steps_done;
-    r->breakdown = (now.breakdown & lora::CG_HALT_BREAKDOWN) ? 1 : 0;
-    r->unconverged_steps = (int) tnow.unconverged;
-    r->last_rr0 = tnow.rr0;
-    r->last_rr = now.rr;
-    for (int step = 0; step < steps; ++step) {
-        const int k = step < r->steps_done ? (int) hist[step] : (step == r->steps_done ? (int) now.iteration : 0);
-        if (iterations) iterations[step] = k;
-        if (step < r->steps_done) {
-            r->iterations_total += k;
-            if (k > r->iterations_max) r->iterations_max = k;
-        }
-    }
-    return LORA_OK;
+    return lora::theta_read_back(plan, d_u, d_f, steps, iterations, r, s);
 }
 
 int lora_run_host_pcg(int shape, const double *in, const double *source, double *out, const double *params, const lora_mg *m,
@@ -782,27 +688,16 @@ int lora_run_host_pcg(int shape, const double *in, const double *source, double 
     if (!in || !out || !dims || !m || !u || !r || lora::bad_until(u) || lora::mg_bad(m, 1.0, 1.0) || lora::asymmetric(m)) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("a preconditioned conjugate-gradient run (its source is an argument)")) return rc;
     lora::HostRun g;
-    int rc = g.open(shape, LORA_F64, dims, params);
-    if (rc != LORA_OK) return rc;
+    if (int rc = g.open_solver(shape, dims, params, in, source)) return rc;
     lora_plan *plan = g.plan;
-    const size_t bytes = g.bytes;
-    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
     void *d_x = g.b[0], *d_f = g.b[1];
-    if ((rc = lora::hip_status(hipMemcpy(d_x, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
-    if (source)
-        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the grids, the state, the hierarchy, and one probe as a warm-up (it writes no grid)
-    if ((rc = lora_plan_prepare_pcg(plan, m, u->max_times))) return rc;
+    if (int rc = lora_plan_prepare_pcg(plan, m, u->max_times)) return rc;
     lora_grid_diff warm;
-    if ((rc = lora_plan_residual_src(plan, d_x, d_f, 0, 0, &warm, nullptr))) return rc;
-    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
-    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
-
-    g.tic();
-    if ((rc = lora_plan_run_pcg_until(plan, d_x, d_f, m, u, r, g.s))) return rc;
-    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
-    g.toc();  // the start-up, the iterations and their probes
-    if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    if (int rc = lora_plan_residual_src(plan, d_x, d_f, 0, 0, &warm, nullptr)) return rc;
+    if (int rc = g.ready()) return rc;
+    // timed: the start-up, the iterations and their probes
+    if (int rc = g.timed(out, [&] { return lora_plan_run_pcg_until(plan, d_x, d_f, m, u, r, g.s); })) return rc;
     // per iteration: the cycle's tally in grids of the fine level, and the CG passes -- p read, q written; x, r, p, q read, x, r
     // written; r, z read; z, p read, p written
     long launches = 0;
@@ -815,38 +710,26 @@ int lora_run_host_theta_mg(int shape, const double *in, const double *source, do
                            int steps, int max_iters, double rtol, const lora_mg *m, int check_every, const int *dims, int quiet,
                            lora_run_info *info, lora_theta_result *result) {
     if (!in || !out || !dims || !result || !m) return LORA_EINVAL;
-    if (!(theta >= 0.0 && theta <= 1.0) || !(tau > 0.0) || !std::isfinite(tau) || steps < 0 || max_iters < 1 || !(rtol >= 0.0) ||
-        !std::isfinite(rtol) || check_every < 1)
-        return LORA_EINVAL;
+    if (lora::bad_theta_args(theta, tau, steps, max_iters, rtol) || check_every < 1) return LORA_EINVAL;
     const double tt = theta * tau, sigma = 1.0 + tt;
     if (lora::mg_bad(m, sigma, tt) || lora::asymmetric(m)) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("an implicit run (its source is an argument)")) return rc;
     lora::HostRun g;
-    int rc = g.open(shape, LORA_F64, dims, params);
-    if (rc != LORA_OK) return rc;
+    if (int rc = g.open_solver(shape, dims, params, in, source)) return rc;
     lora_plan *plan = g.plan;
-    const size_t bytes = g.bytes;
-    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
     void *d_u = g.b[0], *d_f = g.b[1];
-    if ((rc = lora::hip_status(hipMemcpy(d_u, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
-    if (source)
-        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the plan's grids and states, the hierarchy for (sigma, tau'), and one warm-up application
     // into the plan's own q
-    if ((rc = lora::mg_admit(plan, m, sigma, tt, nullptr))) return rc;
-    if ((rc = lora_plan_prepare_theta(plan, steps))) return rc;
-    if (!plan->pcg_z.ensure(bytes)) return LORA_ENOMEM;
-    if ((rc = lora::mg_prepare(plan, m, sigma, tt))) return rc;
+    if (int rc = lora::mg_admit(plan, m, sigma, tt, nullptr)) return rc;
+    if (int rc = lora_plan_prepare_theta(plan, steps)) return rc;
+    if (!plan->pcg_z.ensure(g.bytes)) return LORA_ENOMEM;
+    if (int rc = lora::mg_prepare(plan, m, sigma, tt)) return rc;
     lora_grid_dot warm;
-    if ((rc = lora_plan_apply_dot_shift(plan, d_u, plan->cg[2].ptr, 1.0, 1.0, 0, 0, &warm, nullptr))) return rc;
-    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
-    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
-
-    g.tic();
-    if ((rc = lora_plan_run_theta_mg(plan, d_u, d_f, theta, tau, steps, max_iters, rtol, m, check_every, nullptr, result, g.s))) return rc;
-    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
-    g.toc();  // every step's start, cycles and iterations, the state read-backs, and the steady-state probe
-    if ((rc = lora::hip_status(hipMemcpy(out, d_u, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    if (int rc = lora_plan_apply_dot_shift(plan, d_u, plan->cg[2].ptr, 1.0, 1.0, 0, 0, &warm, nullptr)) return rc;
+    if (int rc = g.ready()) return rc;
+    // timed: every step's start, cycles and iterations, the state read-backs, and the steady-state probe
+    if (int rc = g.timed(out, [&] { return lora_plan_run_theta_mg(plan, d_u, d_f, theta, tau, steps, max_iters, rtol, m, check_every, nullptr, result, g.s); }))
+        return rc;
     // per step: u (and f) read, r and z written, one cycle, the copy and the dot; per iteration a cycle and the thirteen grids of
     // lora_run_host_pcg (the iterations enqueued past a step's last are not counted)
     long launches = 0;

@@ -1,8 +1,9 @@
 // chebyshev.cpp -- the Chebyshev semi-iteration on top of the scaled leapfrog step with a source (leapfrog.cpp:
 // lora_plan_run_leapfrog_src):   u(k+1) = w(k+1) (S(u(k)) + f) + (1 - w(k+1)) u(k-1)
 // solves u = S(u) + f in O(N) steps on an N-wide grid where Jacobi (lora_plan_run_until with a source) needs O(N^2).
-// The coefficient schedule (host only), the run-until driver with a true-residual probe (its grid: lora_plan::cheb_probe), and
-// the host-buffer operator (its skeleton: hostrun.cpp).
+// The coefficient schedule (host only), the run-until driver with the solvers' true-residual probe (reduce.cpp: true_residual;
+// its grid here: lora_plan::cheb_probe, allocated only for the two-pass form), and the host-buffer operator (HostRun of
+// hostrun.cpp; with its three grids and a warm-up that writes one of them it keeps its own uploads and download).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -72,10 +73,6 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
     }
     (void) lora_plan_prepare_leapfrog(plan, u->check_every);
 
-    // the two-pass probe's sweep (unused by the fused one): the plan's own single sweep with f as its source -- a copy of
-    // the plan's resolved state, so the caller's plan keeps its options, kernel name, signature and leapfrog depth
-    Plan probe = p;
-    if (!fused) probe.source = d_f;
     lora::Omega om(rho);
     std::vector<double> a(u->check_every), c(u->check_every);
     while (r->times_done + u->check_every <= u->max_times) {
@@ -88,12 +85,7 @@ int lora_plan_run_chebyshev_until(lora_plan *plan, void *d_prev, void *d_cur, co
         r->times_done += u->check_every;
         // the TRUE residual S(u) + f - u of that level, d_prev and d_cur untouched: reduced inside one sweep where the plan has
         // that kernel, else one sweep into the probe grid and one difference
-        if (fused) {
-            if (int rc = lora::residual_whole(plan, d_cur, d_f, &r->last, s)) return rc;
-        } else {
-            if (int rc = lora::launch_apps(probe, {1, 0, p.dims[0]}, d_cur, plan->cheb_probe.ptr, s)) return rc;
-            if (int rc = lora::diff_whole(plan, plan->cheb_probe.ptr, d_cur, &r->last, s)) return rc;
-        }
+        if (int rc = lora::true_residual(plan, d_cur, d_f, plan->cheb_probe.ptr, fused, &r->last, s)) return rc;
         if (lora::until_decide(u, r)) break;
     }
     return LORA_OK;

@@ -457,6 +457,14 @@ bool interior_geometry(const Plan &p, int begin, int end, ReduceArgs &a, int &ki
 int folded_record(const ReduceRecord *records, ReduceRecord &rec, hipStream_t s);  // reduce.cpp: the folded record back on the host (blocks)
 int residual_whole(lora_plan *plan,const void *d_in, const void *d_f, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_residual_src over the whole interior, unchecked (blocks)
 int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s);  // reduce.cpp: lora_plan_diff over the whole interior, unchecked (blocks)
+// reduce.cpp: the plan's own single sweep with d_f (nullptr = none) as its source, d_out = fl(S(d_in) + f), on a copy of the plan's
+// resolved state -- the caller's plan keeps its options, kernel name, signature and leapfrog depth
+int sweep_with_source(const Plan &p, const void *d_f, const void *d_in, void *d_out, hipStream_t s);
+// reduce.cpp: the probe of the CG, PCG, multigrid and Chebyshev drivers, the TRUE residual S(u) + f - u of the whole interior
+// (blocks).  fused: residual_whole, no grid written; else sweep_with_source into d_scratch and diff_whole of it against d_u.
+// Under the max norm every deciding field of the fused record is bit for bit the two-pass one's; sum_sq -- the RMS norm's -- is
+// summed in another order there, so the callers keep the two passes for that norm.
+int true_residual(lora_plan *plan, const void *d_u, const void *d_f, void *d_scratch, bool fused, lora_grid_diff *out, hipStream_t s);
 int check_buffers(const void *a, const void *b);    // capi.cpp: LORA_EINVAL for a null buffer, LORA_EUNSUPPORTED for a misaligned one
 int default_source_refused(const char *who);       // capi.cpp: LORA_EUNSUPPORTED while the thread has a default source (drivers that take none)
 int attach_default_source(lora_plan *plan, size_t bytes, void **d_source);  // capi.cpp: upload the thread's default source (if any) and set it on the plan; *d_source is the caller's to hipFree, whatever the status
@@ -464,6 +472,17 @@ const char *run_label(int shape);                  // hostrun.cpp: the operator'
 
 // ---- what the entries of capi.cpp, leapfrog.cpp, chebyshev.cpp and reduce.cpp refuse and report alike ----------------------
 inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+// the halo widths of a padded grid of `ndim` dimensions, outermost first: the pads launch_copy_interior takes for a plan's grid
+inline const int *interior_pads(int ndim) {
+    static const int pads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+    return pads[ndim - 1];
+}
+// I - S and sigma I - tau S are symmetric when the taps are point-symmetric (what CG and multigrid need)
+inline bool taps_symmetric(const double *w, int ntaps) {
+    for (int t = 0; t < ntaps; ++t)
+        if (w[t] != w[ntaps - 1 - t]) return false;
+    return true;
+}
 inline int unsupported(const char *text) {
     set_last_error_text(text);
     return LORA_EUNSUPPORTED;
@@ -499,9 +518,11 @@ struct DeviceGrid {
     void release();
 };
 
-// ---- what the four host-buffer operators share (hostrun.cpp): the device check, the plan, N padded grids, a stream of the
-// operator's own, the two clocks, the run info and the reference's three stdout lines.  The operator keeps its checks, uploads,
-// warm-up, prepare call, the timed call between tic() and toc(), and its download.
+// ---- what the host-buffer operators share (hostrun.cpp): the device check, the plan, N padded grids, a stream of the
+// operator's own, the two clocks, the run info and the reference's three stdout lines.  lora_run_host_dtype, _until, _leapfrog
+// and _chebyshev keep their uploads, warm-up, prepare call, the timed call between tic() and toc(), and their download.  The
+// five source solvers (lora_run_host_cg, _theta, _pcg, _theta_mg, _mg) go through open_solver(), ready() and timed(), and
+// keep their checks, their prepare and warm-up lines between the first two, the driver call and the grids-moved figure.
 struct HostRun {
     lora_plan *plan = nullptr;
     void *b[3] = {nullptr, nullptr, nullptr};  // alloc(): padded grids
@@ -516,6 +537,18 @@ struct HostRun {
     void toc();
     // after the download: `steps` steps that each moved `grids_moved` grids; LORA_OK
     int finish(int steps, double grids_moved, int steps_per_launch, int quiet, lora_run_info *info);
+    // a source solver's start: open() as fp64, alloc() of the iterate's grid b[0] and, with a source, its grid b[1], both uploaded
+    int open_solver(int shape, const int *dims, const double *params, const double *in, const double *source);
+    // behind the operator's prepare and warm-up (whose launches go to the null stream): stream(), then a device synchronise
+    int ready();
+    // the timed region: tic(), `run` (the driver call on `s`), a stream synchronise, toc(); then b[0] into `out`
+    template <class Run>
+    int timed(double *out, Run run) {
+        tic();
+        if (int rc = run()) return rc;
+        return timed_end(out);
+    }
+    int timed_end(double *out);
     int shape = 0;
     double points = 1.0;              // interior points
     long long ticks[3] = {0, 0, 0};  // steady_clock: alloc(), tic(), toc()

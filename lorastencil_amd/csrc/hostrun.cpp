@@ -1,6 +1,7 @@
 // hostrun.cpp -- lora::HostRun (engine.h): the skeleton of the host-buffer operators that stand in for the reference's gpu_*()
 // functions -- lora_run_host_dtype (capi.cpp), lora_run_host_until (reduce.cpp), lora_run_host_leapfrog (leapfrog.cpp),
-// lora_run_host_chebyshev (chebyshev.cpp), lora_run_host_cg and lora_run_host_theta (cg.cpp).
+// lora_run_host_chebyshev (chebyshev.cpp) -- and, through open_solver / ready / timed, the whole sequence of the five source
+// solvers: lora_run_host_cg, _theta, _pcg, _theta_mg (cg.cpp) and lora_run_host_mg (mg.cpp).
 //
 // Reference behaviour followed (file:line under the reference's src/):
 //   timing = steady_clock around the launch loop + one device sync
@@ -74,6 +75,24 @@ hipError_t HostRun::alloc(int n) {
 hipError_t HostRun::stream() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 void HostRun::tic() { ticks[1] = now(); }
 void HostRun::toc() { ticks[2] = now(); }
+
+int HostRun::open_solver(int shape, const int *dims, const double *params, const double *in, const double *source) {
+    if (int rc = open(shape, LORA_F64, dims, params)) return rc;
+    if (alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
+    if (int rc = hip_status(hipMemcpy(b[0], in, bytes, hipMemcpyHostToDevice), "upload")) return rc;
+    return source ? hip_status(hipMemcpy(b[1], source, bytes, hipMemcpyHostToDevice), "upload") : LORA_OK;
+}
+
+int HostRun::ready() {
+    if (int rc = hip_status(stream(), "stream")) return rc;
+    return hip_status(hipDeviceSynchronize(), "upload");
+}
+
+int HostRun::timed_end(double *out) {
+    if (int rc = hip_status(hipStreamSynchronize(s), "run")) return rc;
+    toc();
+    return hip_status(hipMemcpy(out, b[0], bytes, hipMemcpyDeviceToHost), "download");
+}
 
 int HostRun::finish(int steps, double grids_moved, int steps_per_launch, int quiet, lora_run_info *info) {
     const clock::duration sweep(ticks[2] - ticks[1]), total(now() - ticks[0]);

@@ -1,7 +1,9 @@
 // mg.cpp -- geometric multigrid for u = S(u) + f (kernels: kernels_mg.hip, the smoother: the source sweeps, the
 // coarsest level: the CG launches of cg.cpp).  The host-only geometry (coarse extents, coarse taps), the public entries of the
-// two transfer kernels, the level hierarchy a plan owns (lora_plan::mg), the V-cycle driver with the true-residual probe of the
-// CG driver, and the host-buffer operator (its skeleton: hostrun.cpp).
+// two transfer kernels, the level hierarchy a plan owns (lora_plan::mg), the V-cycle driver with the solvers' true-residual
+// probe (reduce.cpp: true_residual), and the host-buffer operator (its skeleton: hostrun.cpp).  Shared by every entry here and
+// by the PCG entries of cg.cpp: one admission (admit; mg_admit for cg.cpp) and one "cycle into the caller's grid" (cycle_into:
+// the driver's cycles and mg_precondition).
 //
 // Coarsening is boundary-aligned and non-nested (kernels_mg.hip has the geometry): level l + 1 has floor(n / 2) cells per axis,
 // the innermost rounded down to even, and the taps of level l rescaled by (h / H)^2 per axis.  On every level but the coarsest
@@ -70,12 +72,6 @@ void coarse_taps(int ndim, const double *w, const int *dims, const int *cdims, d
         others += wc[t];
     }
     wc[c] = sum - others;
-}
-
-bool taps_symmetric(const double *w, int ntaps) {
-    for (int t = 0; t < ntaps; ++t)
-        if (w[t] != w[ntaps - 1 - t]) return false;
-    return true;
 }
 
 // any check_every >= 1 counts cycles; the other rules are lora_plan_run_until's
@@ -344,14 +340,15 @@ void fill_levels(const std::vector<LevelDesc> &descs, lora_mg_result *r) {
         for (int a = 0; a < 3; ++a) r->level_dims[l][a] = l < (int) descs.size() ? descs[l].dims[a] : 0;
 }
 
-// what both the run and the prepare call refuse before a device is asked for
-int admit_mg(const lora_plan *plan, const lora_mg *m) {
+// What every multigrid entry refuses before a device is asked for, behind its LORA_EINVAL checks: a plan without the kernels,
+// taps that are not point-symmetric (`op` names the entry's operator in that text), a level whose diagonal cannot be smoothed.
+// descs: the levels of the hierarchy for (m, sigma, tau).
+int admit(const lora_plan *plan, const lora_mg *m, double sigma, double tau, const char *op, std::vector<LevelDesc> &descs) {
     const Plan &p = plan->p;
     if (!has_mg(p)) return no_mg_kernels();
     if (!taps_symmetric(p.w, p.ntaps))
-        return unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
-    std::vector<LevelDesc> descs;
-    return describe_levels(p, m, 1.0, 1.0, descs);
+        return unsupported((std::string("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: ") + op + " is not symmetric otherwise").c_str());
+    return describe_levels(p, m, sigma, tau, descs);
 }
 
 // the halos every level's free grid shares with its iterate below level 0, and the coarsest level's iterate
@@ -367,7 +364,23 @@ int coarse_iterations(const MgHierarchy *h, const lora_mg *m) {
     return m->coarse_iters ? m->coarse_iters : (int) std::fmin(h->levels.back().cells, 64.0);
 }
 
-const int kPads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+// One V-cycle of level 0 from the iterate in `dst` (the level's free grid: `spare`) that leaves the iterate in `dst`; `tally`
+// (what the caller enqueued in front of the cycle) plus the cycle's launches becomes the hierarchy's cost of a cycle.
+int cycle_into(const Run &r, double *dst, double *spare, Tally tally = Tally()) {
+    const Plan &p = r.plan->p;
+    Level &top = r.h->levels[0];
+    top.cur = dst;
+    top.other = spare;
+    if (int rc = cycle(r, 0, tally)) return rc;
+    if (top.cur != dst) {  // an odd number of launches moved the iterate: back into the caller's grid, interior cells only
+        const int *pad = interior_pads(p.ndim);
+        if (int rc = hip_status(launch_copy_interior(LORA_F64, p.ndim, p.dims, dst, pad, top.cur, pad, r.s), "copy launch")) return rc;
+        tally.add(1, top.cells, 2.0);
+    }
+    r.h->launches = tally.launches;
+    r.h->bytes = tally.bytes;
+    return LORA_OK;
+}
 
 }  // namespace
 
@@ -375,12 +388,8 @@ bool mg_bad(const lora_mg *m, double sigma, double tau) { return bad_mg(m) || ba
 
 int mg_admit(const lora_plan *plan, const lora_mg *m, double sigma, double tau, int *levels) {
     if (mg_bad(m, sigma, tau)) return LORA_EINVAL;
-    const Plan &p = plan->p;
-    if (!has_mg(p)) return no_mg_kernels();
-    if (!taps_symmetric(p.w, p.ntaps))
-        return unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: sigma I - tau S is not symmetric otherwise");
     std::vector<LevelDesc> descs;
-    if (int rc = describe_levels(p, m, sigma, tau, descs)) return rc;
+    if (int rc = admit(plan, m, sigma, tau, "sigma I - tau S", descs)) return rc;
     if (levels) *levels = (int) descs.size();
     return LORA_OK;
 }
@@ -420,17 +429,7 @@ int mg_precondition(lora_plan *plan, const double *d_r, double *d_z, const lora_
     if (int rc = reset_level_halos(h, s)) return rc;
     tally.launches += (long) h->levels.size() - 1;  // (the halo resets: a grid's rim each)
     const Run run = {plan, h, m, s, p.ndim, (int) h->levels.size() - 1, coarse_iterations(h, m)};
-    top.cur = d_z;
-    top.other = spare0;
-    if (int rc = cycle(run, 0, tally)) return rc;
-    if (top.cur != d_z) {  // an odd number of launches moved the iterate: back into the caller's grid, interior cells only
-        if (int rc = hip_status(launch_copy_interior(LORA_F64, p.ndim, p.dims, d_z, kPads[p.ndim - 1], top.cur, kPads[p.ndim - 1], s), "copy launch"))
-            return rc;
-        tally.add(1, top.cells, 2.0);
-    }
-    h->launches = tally.launches;
-    h->bytes = tally.bytes;
-    return LORA_OK;
+    return cycle_into(run, d_z, spare0, tally);
 }
 
 }  // namespace lora
@@ -501,7 +500,8 @@ int lora_plan_mg_prolong_add(lora_plan *plan, const void *d_coarse, void *d_fine
 
 int lora_plan_prepare_mg(lora_plan *plan, const lora_mg *m) {
     if (!plan || !m || lora::bad_mg(m)) return LORA_EINVAL;
-    if (int rc = lora::admit_mg(plan, m)) return rc;
+    std::vector<lora::LevelDesc> descs;
+    if (int rc = lora::admit(plan, m, 1.0, 1.0, "I - S", descs)) return rc;
     if (lora_device_count() <= 0) return lora::no_device();
     lora::ReduceRecord *records = nullptr;  // (the probe folds into the plan's records: they are part of what a run needs)
     if (int rc = lora::reduction_records(plan, &records)) return rc;
@@ -531,11 +531,8 @@ int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
     if (!plan || !d_x || !m || !u || !r || lora::bad_mg_until(u) || lora::bad_mg(m) || d_f == d_x) return LORA_EINVAL;
     if (lora::misaligned(d_x) || lora::misaligned(d_f)) return lora::unsupported("device buffers must be 16-byte aligned");
     const Plan &p = plan->p;
-    if (!lora::has_mg(p)) return lora::no_mg_kernels();
-    if (!lora::taps_symmetric(p.w, p.ntaps))
-        return lora::unsupported("multigrid needs point-symmetric taps, w[t] == w[ntaps - 1 - t]: I - S is not symmetric otherwise");
     std::vector<lora::LevelDesc> descs;
-    if (int rc = lora::describe_levels(p, m, 1.0, 1.0, descs)) return rc;
+    if (int rc = lora::admit(plan, m, 1.0, 1.0, "I - S", descs)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = lora::admit_reduction(d_x, d_x, s)) return rc;
     *r = {{0, 0, 0, 0, HUGE_VAL, {0.0, 0.0, 0.0, -1, 0, 0}}, 0, {{0}}};
@@ -561,34 +558,13 @@ int lora_plan_run_mg_until(lora_plan *plan, void *d_x, const void *d_f, const lo
     if (int rc = lora::reset_level_halos(h, s)) return rc;
 
     const lora::Run run = {plan, h, m, s, p.ndim, L, lora::coarse_iterations(h, m)};
-    // the sweep of the two-pass probe: the plan's own single sweep with f as its source (as lora_plan_run_cg_until)
-    Plan with_f = p;
-    with_f.source = d_f;
-    const lora::Apps whole = {1, 0, p.dims[0]};
-    static const int pads[3][3] = {{4, 0, 0}, {4, 4, 0}, {1, 2, 4}};
+    // the probe (as lora_plan_run_cg_until): fused under the max norm, else two passes through level 0's free grid
     const bool fused = u->norm == LORA_NORM_MAX;
     lora_until_result &ur = r->until;
     while (ur.times_done + u->check_every <= u->max_times) {
-        for (int i = 0; i < u->check_every; ++i) {
-            lora::Tally tally;
-            top.cur = x0;
-            top.other = spare0;
-            if (int rc = lora::cycle(run, 0, tally)) return rc;
-            if (top.cur != x0) {  // an odd number of launches moved the iterate: back into the caller's grid, interior cells only
-                if (int rc = lora::hip_status(lora::launch_copy_interior(LORA_F64, p.ndim, p.dims, x0, pads[p.ndim - 1], top.cur, pads[p.ndim - 1], s),
-                                              "copy launch"))
-                    return rc;
-                tally.add(1, top.cells, 2.0);
-            }
-            h->launches = tally.launches;
-            h->bytes = tally.bytes;
-        }
-        if (fused) {
-            if (int rc = lora::residual_whole(plan, d_x, d_f, &ur.last, s)) return rc;
-        } else {
-            if (int rc = lora::launch_apps(with_f, whole, d_x, spare0, s)) return rc;
-            if (int rc = lora::diff_whole(plan, spare0, d_x, &ur.last, s)) return rc;
-        }
+        for (int i = 0; i < u->check_every; ++i)
+            if (int rc = lora::cycle_into(run, x0, spare0)) return rc;
+        if (int rc = lora::true_residual(plan, d_x, d_f, spare0, fused, &ur.last, s)) return rc;
         ur.times_done += u->check_every;
         if (lora::until_decide(u, &ur)) break;
     }
@@ -600,27 +576,16 @@ int lora_run_host_mg(int shape, const double *in, const double *source, double *
     if (!in || !out || !dims || !m || !u || !r || lora::bad_mg_until(u) || lora::bad_mg(m)) return LORA_EINVAL;
     if (int rc = lora::default_source_refused("a multigrid run (its source is an argument)")) return rc;
     lora::HostRun g;
-    int rc = g.open(shape, LORA_F64, dims, params);
-    if (rc != LORA_OK) return rc;
+    if (int rc = g.open_solver(shape, dims, params, in, source)) return rc;
     lora_plan *plan = g.plan;
-    const size_t bytes = g.bytes;
-    if (g.alloc(source ? 2 : 1) != hipSuccess) return LORA_ENOMEM;
     void *d_x = g.b[0], *d_f = g.b[1];
-    if ((rc = lora::hip_status(hipMemcpy(d_x, in, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
-    if (source)
-        if ((rc = lora::hip_status(hipMemcpy(d_f, source, bytes, hipMemcpyHostToDevice), "upload"))) return rc;
     // set-up outside the timed region: the hierarchy, and one probe as a warm-up (it writes no grid)
-    if ((rc = lora_plan_prepare_mg(plan, m))) return rc;
+    if (int rc = lora_plan_prepare_mg(plan, m)) return rc;
     lora_grid_diff warm;
-    if ((rc = lora_plan_residual_src(plan, d_x, d_f, 0, 0, &warm, nullptr))) return rc;
-    if ((rc = lora::hip_status(g.stream(), "stream"))) return rc;
-    if ((rc = lora::hip_status(hipDeviceSynchronize(), "upload"))) return rc;
-
-    g.tic();
-    if ((rc = lora_plan_run_mg_until(plan, d_x, d_f, m, u, r, g.s))) return rc;
-    if ((rc = lora::hip_status(hipStreamSynchronize(g.s), "run"))) return rc;
-    g.toc();  // the cycles and their probes
-    if ((rc = lora::hip_status(hipMemcpy(out, d_x, bytes, hipMemcpyDeviceToHost), "download"))) return rc;
+    if (int rc = lora_plan_residual_src(plan, d_x, d_f, 0, 0, &warm, nullptr)) return rc;
+    if (int rc = g.ready()) return rc;
+    // timed: the cycles and their probes
+    if (int rc = g.timed(out, [&] { return lora_plan_run_mg_until(plan, d_x, d_f, m, u, r, g.s); })) return rc;
     // per cycle: the bytes its launches move (lora_plan_mg_cycle_cost), in grids of the fine level
     const double per_cycle = plan->mg && plan->mg->launches ? plan->mg->bytes / (8.0 * g.points) : 0.0;
     return g.finish(r->until.times_done, per_cycle, 1, quiet, info);

@@ -1,7 +1,8 @@
 // reduce.cpp -- host side of the device-side reductions (kernels_reduce.hip; their records: lora_plan::records) and what is
 // built on them: lora_plan_stats, lora_plan_diff, lora_plan_dot, lora_plan_residual and lora_plan_residual_src (kernels_residual.hip),
-// lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until, what it shares with the Chebyshev one (bad_until,
-// until_decide) and its group-A form (its skeleton: hostrun.cpp).
+// lora_grid_stats_merge, the run-until-steady driver lora_plan_run_until, what it shares with the solver drivers (bad_until,
+// until_decide), their true-residual probe (true_residual: the CG, PCG, multigrid and Chebyshev drivers) and its group-A form
+// (its skeleton: hostrun.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,15 +21,10 @@ namespace lora {
         }                                     \
     } while (0)
 
-static const int *halo_widths(int ndim) {
-    static const int h1[1] = {4}, h2[2] = {4, 4}, h3[3] = {1, 2, 4};
-    return ndim == 1 ? h1 : (ndim == 2 ? h2 : h3);
-}
-
 // Launch geometry of a box: everything here follows from the dtype, the extents and the box, never from the device or from
 // an earlier call -- which is what makes a reduction return the same bits every time.
 bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a, int &kind, int &groups) {
-    const int *hw = halo_widths(p.ndim);
+    const int *hw = interior_pads(p.ndim);
     long P[3] = {1, 1, 1};
     int l[3] = {0, 0, 0}, h[3] = {1, 1, 1};
     for (int d = 0; d < 3; ++d) {
@@ -68,7 +64,7 @@ bool reduce_geometry(const Plan &p, const int *lo, const int *hi, ReduceArgs &a,
 
 // the interior box of the outermost range [begin, end): its launch geometry and its number of cells
 bool interior_geometry(const Plan &p, int begin, int end, ReduceArgs &a, int &kind, int &groups, long long &count) {
-    const int *hw = halo_widths(p.ndim);
+    const int *hw = interior_pads(p.ndim);
     int lo[3], hi[3];
     count = 1;
     for (int d = 0; d < p.ndim; ++d) {
@@ -221,6 +217,16 @@ int residual_whole(lora_plan *plan, const void *d_in, const void *d_f, lora_grid
 int diff_whole(lora_plan *plan, const void *d_a, const void *d_b, lora_grid_diff *out, hipStream_t s) {
     return diff_range(plan, d_a, d_b, 0, plan->p.dims[0], out, s);
 }
+int sweep_with_source(const Plan &p, const void *d_f, const void *d_in, void *d_out, hipStream_t s) {
+    Plan with_f = p;
+    with_f.source = d_f;
+    return launch_apps(with_f, {1, 0, p.dims[0]}, d_in, d_out, s);
+}
+int true_residual(lora_plan *plan, const void *d_u, const void *d_f, void *d_scratch, bool fused, lora_grid_diff *out, hipStream_t s) {
+    if (fused) return residual_whole(plan, d_u, d_f, out, s);
+    if (int rc = sweep_with_source(plan->p, d_f, d_u, d_scratch, s)) return rc;
+    return diff_whole(plan, d_scratch, d_u, out, s);
+}
 
 }  // namespace lora
 
@@ -318,7 +324,7 @@ int lora_debug_residual_cover(const lora_plan *plan, int begin, int end, int *co
     if (workgroups) *workgroups = 0;
     lora::ResidualTiles rt;
     if (!some || !lora::residual_tiles_setup(rt, p, begin, end)) return LORA_OK;
-    const int *hw = lora::halo_widths(p.ndim);
+    const int *hw = lora::interior_pads(p.ndim);
     int halo[3] = {0, 0, 0};
     long P[3] = {1, 1, 1};
     for (int d = 3 - p.ndim; d < 3; ++d) {

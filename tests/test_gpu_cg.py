@@ -12,6 +12,7 @@ one; 1027 = 2 x 512 + 3: the odd tail point; 33 x 130: one row and one column pa
 explicitly: small symmetric integers, and non-negative symmetric taps divided by their sum.  Buffers are carved by tests/arena.py at offsets 16 and 240, the guard bands NaN.
 """
 import functools
+import itertools
 import math
 import zlib
 
@@ -329,14 +330,17 @@ def padded_with_interior(L, shape, dims, interior, halo=0.0):
     return a
 
 
-def cg_by_public_entries(L, plan, w, shape, dims, g, iterations):
-    """grids of g: 0 = x, 1 = f; the loop of the header's bit contract.  Returns the true residual record of the result."""
+def cg_by_public_entries(L, plan, w, shape, dims, g, iterations, with_f=True, norm="max"):
+    """grids of g: 0 = x, 1 = f; the loop of the header's bit contract.  Returns the true residual record of the result as the
+    driver's probe takes it: in one pass under the max norm, by a source sweep and a difference under the RMS norm."""
     import torch
 
-    x, f = g.v[0], g.v[1]
+    x, f = g.v[0], g.v[1] if with_f else None
     r, p, q = torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x)
-    with_f = L.Plan(shape, dims).set_weights(w).set_source(f)
-    with_f.step(x, r)  # fl(S(x) + f)
+    sweep = L.Plan(shape, dims).set_weights(w)
+    if with_f:
+        sweep.set_source(f)
+    sweep.step(x, r)  # fl(S(x) + f)
     torch.cuda.synchronize()
     inner = lambda t: L.interior(shape, t)
     inner(r).copy_(inner(r) - inner(x))
@@ -349,32 +353,39 @@ def cg_by_public_entries(L, plan, w, shape, dims, g, iterations):
         beta = rr_new / rr
         plan.cg_direction(p, r, beta)
         rr = rr_new
-    return plan.residual_src(x, f)
+    if norm == "max":
+        return plan.residual_src(x, f)
+    sweep.step(x, q)
+    return plan.diff(q, x)
 
 
 @pytest.mark.parametrize("shape,dims,regions", SEVERAL, ids=SEVERAL_IDS)
 def test_driver_equals_the_composition_of_the_public_entries(L, shape, dims, regions):
+    """every combination of the probe's two forms (the max norm: fused; the RMS norm: two passes) with and without f"""
     import torch
 
     _, x0, f0 = host_data(shape, dims)[:3]
     w = symmetric_taps(L, shape, "normalised")
     plan = make_plan(L, shape, dims, "normalised")
-    for off, iterations in zip((16, 240, 16), (2, 4, 6)):
-        g = Grids(L, shape, dims, off, [x0, f0])
-        before_f, halo = g.bits(1), ~g.region(0, plan.dims[0]).clone()
-        before_x = g.bits(0)
-        res = plan.run_cg_until(g.v[0], g.v[1], tol=0.0, check_every=2, max_times=iterations)
-        g.guards(f"{shape} {dims} run_cg_until x{iterations}")
-        assert torch.equal(g.arena.bits(1), before_f), "d_f was written"
-        assert torch.equal(g.arena.bits(0)[halo], before_x[halo]), "a halo cell of d_x was written"
-        got_x = g.v[0].clone()
-        g.v[0].copy_(torch.from_numpy(np.array(x0)))
-        last = cg_by_public_entries(L, plan, w, shape, dims, g, iterations)
-        assert same_bits(got_x, g.v[0]), f"{shape} {dims}: x after {iterations} iterations differs from the loop over the public entries"
-        assert res.until.times_done == iterations and res.until.checks == iterations // 2 and not res.breakdown
-        assert tuple(map(fbits, res.until.last)) == tuple(map(fbits, last))
-        assert not res.until.converged and not res.until.diverged
-        assert res.lambda_min > 0 and res.lambda_max >= res.lambda_min and res.rho_estimate == max(abs(1 - res.lambda_min), abs(1 - res.lambda_max))
+    for norm, with_f in itertools.product(("max", "rms"), (True, False)):
+        for off, iterations in zip((16, 240, 16), (2, 4, 6)):
+            what = f"{shape} {dims} run_cg_until x{iterations} norm {norm} f {with_f}"
+            g = Grids(L, shape, dims, off, [x0, f0])
+            before_f, halo = g.bits(1), ~g.region(0, plan.dims[0]).clone()
+            before_x = g.bits(0)
+            res = plan.run_cg_until(g.v[0], g.v[1] if with_f else None, tol=0.0, norm=norm, check_every=2, max_times=iterations)
+            g.guards(what)
+            assert torch.equal(g.arena.bits(1), before_f), what + ": d_f was written"
+            assert torch.equal(g.arena.bits(0)[halo], before_x[halo]), what + ": a halo cell of d_x was written"
+            got_x = g.v[0].clone()
+            g.v[0].copy_(torch.from_numpy(np.array(x0)))
+            last = cg_by_public_entries(L, plan, w, shape, dims, g, iterations, with_f, norm)
+            assert same_bits(got_x, g.v[0]), what + ": x differs from the loop over the public entries"
+            assert res.until.times_done == iterations and res.until.checks == iterations // 2 and not res.breakdown
+            assert tuple(map(fbits, res.until.last)) == tuple(map(fbits, last)), what
+            assert fbits(res.until.residual) == fbits(last.max_abs if norm == "max" else math.sqrt(last.sum_sq / last.count)), what
+            assert not res.until.converged and not res.until.diverged
+            assert res.lambda_min > 0 and res.lambda_max >= res.lambda_min and res.rho_estimate == max(abs(1 - res.lambda_min), abs(1 - res.lambda_max))
 
 
 def jacobi(L, dims):

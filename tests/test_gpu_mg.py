@@ -17,6 +17,7 @@ with a tenfold margin, factor = 1 + 10 (measured - 1), computed in the test from
 figures above).  It was fixed before the engine was run and is never taken from the engine's output.
 """
 import functools
+import itertools
 import math
 import os
 import subprocess
@@ -378,11 +379,13 @@ def test_driver_equals_the_composition_of_the_public_entries(L, shape, dims, lev
     plan = L.Plan(shape, dims).set_weights(w)
     ref = PublicCycle(L, shape, dims, w, omega, pre, post, with_f)
     assert len(ref.tab) == levels
-    for off, cycles in zip(OFFSETS, (1, 2)):
+    # both forms of the probe: fused under the max norm, a source sweep and a difference under the RMS norm
+    for (off, cycles), norm in itertools.product(zip(OFFSETS, (1, 2)), ("max", "rms")):
         g = Grids(L, shape, dims, off, [x0, f])
         before_x, before_f, halo = g.bits(0), g.bits(1), ~g.interior_mask()
-        res = plan.run_mg_until(g.v[0], g.v[1] if with_f else None, tol=0.0, pre=pre, post=post, omega=omega, check_every=1, max_times=cycles)
-        g.guards(f"{shape} {dims} run_mg_until x{cycles}")
+        res = plan.run_mg_until(g.v[0], g.v[1] if with_f else None, tol=0.0, pre=pre, post=post, omega=omega, norm=norm, check_every=1,
+                                max_times=cycles)
+        g.guards(f"{shape} {dims} run_mg_until x{cycles} norm {norm}")
         assert torch.equal(g.arena.bits(1), before_f), "d_f was written"
         assert torch.equal(g.arena.bits(0)[halo], before_x[halo]), "a halo cell of d_x was written"
         assert res.levels == levels and res.level_dims == tuple(t[0] for t in ref.tab)
@@ -391,7 +394,16 @@ def test_driver_equals_the_composition_of_the_public_entries(L, shape, dims, lev
         assert same_bits(g.v[0], expect), f"{shape} {dims}: d_x after {cycles} cycle(s) differs from the loop over the public entries"
         # the probe is the true residual of the caller's problem
         last = plan.residual_src(g.v[0], g.v[1] if with_f else None)
-        assert res.until.residual == last.max_abs and res.until.last.argmax == last.argmax
+        assert res.until.last.max_abs == last.max_abs
+        if norm == "rms":
+            sweep, q = L.Plan(shape, dims).set_weights(w), torch.zeros_like(g.v[0])
+            if with_f:
+                sweep.set_source(g.v[1])
+            sweep.step(g.v[0], q)
+            two_pass = plan.diff(q, g.v[0])
+            assert res.until.last == two_pass and res.until.residual == math.sqrt(two_pass.sum_sq / two_pass.count)
+        else:
+            assert res.until.last == last and res.until.residual == last.max_abs
         launches, nbytes = plan.mg_cycle_cost()
         print(shape, dims, "launches per cycle", launches, "bytes per cycle", nbytes)
         assert launches > 5 * ref.iters and nbytes > 0

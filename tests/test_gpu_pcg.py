@@ -13,6 +13,7 @@ in the test and never taken from the engine's output (the scheme of tests/test_g
 Buffers are carved by tests/arena.py at offsets 16 and 240, the guard bands NaN.
 """
 import functools
+import itertools
 import math
 import os
 import subprocess
@@ -519,13 +520,14 @@ def test_pcg_driver_equals_the_host_loop(L, shape, dims, with_f):
     x0 = rng.standard_normal(ps)  # non-zero halo values: the boundary
     f0 = rng.standard_normal(ps) if with_f else None
     plan = L.Plan(shape, dims).set_weights(w)
-    for off, smooth in zip(OFFSETS, (1, 2)):
+    # both forms of the probe: fused under the max norm, a source sweep and a difference under the RMS norm
+    for (off, smooth), norm in itertools.product(zip(OFFSETS, (1, 2)), ("max", "rms")):
         g = Grids(L, shape, dims, off, [x0, f0])
         halo = ~g.interior_mask()
         before_x, before_f = g.bits(0), g.bits(1)
         f = g.v[1] if with_f else None
-        res = plan.run_pcg_until(g.v[0], f, tol=0.0, smooth=smooth, check_every=2, max_times=4)
-        what = f"{shape} {dims} V({smooth},{smooth}) f {with_f}"
+        res = plan.run_pcg_until(g.v[0], f, tol=0.0, smooth=smooth, norm=norm, check_every=2, max_times=4)
+        what = f"{shape} {dims} V({smooth},{smooth}) f {with_f} norm {norm}"
         g.guards(what)
         assert torch.equal(g.arena.bits(1), before_f), what + ": d_f was written"
         assert torch.equal(g.arena.bits(0)[halo], before_x[halo]), what + ": a halo cell of d_x was written"
@@ -537,7 +539,16 @@ def test_pcg_driver_equals_the_host_loop(L, shape, dims, with_f):
         pcg_by_public_entries(L, L.Plan(shape, dims).set_weights(w), shape, expect, f, 4, smooth)
         assert same_bits(g.v[0], expect), what + ": d_x after 4 iterations differs from the host loop over the public entries"
         last = plan.residual_src(g.v[0], f)
-        assert res.until.residual == last.max_abs
+        if norm == "rms":
+            sweep, q = L.Plan(shape, dims).set_weights(w), torch.zeros_like(g.v[0])
+            if with_f:
+                sweep.set_source(f)
+            sweep.step(g.v[0], q)
+            two_pass = plan.diff(q, g.v[0])
+            assert res.until.last == two_pass and res.until.residual == math.sqrt(two_pass.sum_sq / two_pass.count), what
+        else:
+            assert res.until.last == last, what
+        assert res.until.last.max_abs == last.max_abs and (norm == "rms" or res.until.residual == last.max_abs)
 
 
 def dense_operator(L, shape, dims, w, x):
