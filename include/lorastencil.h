@@ -406,11 +406,29 @@ int lora_plan_stepn_region(lora_plan *plan, int napps, const void *d_in, void *d
  * kernels), two launches otherwise; an empty range is skipped. */
 int lora_plan_stepn_region2(lora_plan *plan, int napps, const void *d_in, void *d_out, int begin0, int end0, int begin1, int end1,
                             void *stream);
-/* Test support, no device needed: replays on the host the decode the register-resident 3D kernels run for a launch cut into
+/* Test support, no device needed: walks every workgroup of a launch with the decode the register-resident 3D kernels run (the
+ * same code, compiled for the host), for a launch cut into
  * spans (team = 0), team spans (team = 1) or team spans with the rim columns cut finer (team = 2; csrc/spans.h) over tiles_x x tiles_y tiles and `depth` planes on `slots`
  * resident workgroups with S steps of start per segment.  cover[(ty * tiles_x + tx) * depth + z] is incremented once per
  * segment that sweeps the pair (the caller zeroes it): every entry must come out 1. */
 int lora_debug_span_cover(int tiles_x, int tiles_y, int depth, int S, int slots, int team, int *cover, int *workgroups, int *max_steps);
+/* The same for the cut the launcher of the fp64 (kernel = 0) or bf16 (1) register-resident kernel itself chooses for a launch
+ * of K = 2 or 4 applications over planes [begin, end) (and [begin2, end2), empty if end2 <= begin2) of h, on tiles_x x tiles_y
+ * tiles and `slots` resident workgroups under plan options fused_z_chunk and spans3: cover[(ty * tiles_x + tx) * h + z] counts
+ * the segments that sweep plane z of the tile (every entry inside the ranges must come out 1, every other 0), *kind is the
+ * layout chosen; where two apply, the later of the list. */
+enum lora_cut_kind {
+    LORA_CUT_FIXED = 1,    /* chunks of fused_z_chunk planes */
+    LORA_CUT_MODEL,        /* equal chunks by the model of rounds of workgroups */
+    LORA_CUT_RANGES2,      /* chunks over two ranges of planes */
+    LORA_CUT_SLOW,         /* fp64: chunks, one more for the slow rim tiles */
+    LORA_CUT_DEALT,        /* fp64: chunks dealt to the resident workgroups */
+    LORA_CUT_SPANS,
+    LORA_CUT_TEAMS,
+    LORA_CUT_TEAMS_FINER   /* bf16: team spans with the rim columns cut finer */
+};
+int lora_debug_cut_cover(int kernel, int K, int tiles_x, int tiles_y, int h, int begin, int end, int begin2, int end2, int slots,
+                         int fused_z_chunk, int spans3, int *cover, int *workgroups, int *max_steps, int *kind);
 /* Halo cells of a padded device array (every cell outside the interior, any shape / dtype of the plan): copied from
  * d_src (LORA_HALO_COPY), zeroed (LORA_HALO_ZERO) or wrapped from d_dst's own opposite interior edges
  * (LORA_HALO_WRAP, periodic; LORA_EUNSUPPORTED if an extent is smaller than its halo).  What lora_plan_run uses for

@@ -380,92 +380,41 @@ struct RunMarks {  // lora_plan_run_profiled: events around the fused and the si
     int fused_launches = 0, two_launches = 0, single_launches = 0;
 };
 
-// Test support (no device): replay, on the host, the decode the register-resident 3D kernels run for a launch cut into spans
-// (team = 0) or team spans (team = 1) -- csrc/spans.h -- and count how often each (tile, plane) pair is swept.
-// cover[(ty * tiles_x + tx) * depth + z] += 1 per workgroup segment that holds the pair; *workgroups = the launch's size,
-// *max_steps = the busiest workgroup's steps (S per segment + its planes).  Every count must be 1.
+// Test support (no device): the cuts of the register-resident 3D kernels' launches, walked on the host (spans.h: cut3_walk).
+// A region of `depth` planes cut into spans (team = 0), team spans as the fp64 kernel launches them (1) or as the bf16
+// kernel does (2: column lines with weighted rim rows, the rim columns cut finer), whatever S.
 int lora_debug_span_cover(int tiles_x, int tiles_y, int depth, int S, int slots, int team, int *cover, int *workgroups, int *max_steps) {
     if (tiles_x < 1 || tiles_y < 1 || depth < 1 || S < 1 || slots < 1 || !cover) return LORA_EINVAL;
-    lora::Spans sp{};
-    long wgs;
-    if (team == 2) {
-        // team spans as the bf16 kernel launches them: column lines with weighted rim rows, the rim columns cut finer
-        if (tiles_x > slots) return LORA_EUNSUPPORTED;
-        lora::Spans sp2{};
-        long ni, nr;
-        lora::team_pieces(tiles_x, slots, true, &ni, &nr);
-        const bool weigh = tiles_x >= 3;
-        const long ti = ni > 0 ? lora::spans_setup_column(sp, tiles_y, depth, S, ni, weigh ? 19 : 1, weigh ? 18 : 1) : 0;
-        const long tr = nr > 0 ? lora::spans_setup_column(sp2, tiles_y, depth, S, nr, 1, 1) : 0;
-        if (ti <= 0 || tr < ti) return LORA_EUNSUPPORTED;
-        const long team_nr = tiles_x >= 3 ? tr : ti;
-        wgs = tiles_x >= 3 ? ti * (tiles_x - 2) + 2 * tr : ti * tiles_x;
-        int busiest2 = 0;
-        for (long lin = 0; lin < wgs; ++lin) {
-            long j;
-            int col;
-            if (lin < (long) tiles_x * ti) {
-                j = lin / tiles_x;
-                col = (int) (lin - j * tiles_x);
-            } else {
-                const long r = lin - (long) tiles_x * ti;
-                j = ti + (r >> 1);
-                col = (r & 1) ? tiles_x - 1 : 0;
-            }
-            const bool rim_col = team_nr != ti && (col == 0 || col == tiles_x - 1);
-            const lora::Spans &t = rim_col ? sp2 : sp;
-            unsigned v0, v1;
-            lora::span_range(t, (int) j, v0, v1);
-            int steps = 0;
-            for (bool more = true; more;) {
-                int t0, ty, z0, zc;
-                const bool any = lora::span_next(t, S, v0, v1, 1, tiles_y, t0, ty, z0, zc);
-                ty = lora::column_line_row(ty, tiles_y);
-                more = v0 < v1;
-                if (!any) continue;
-                if (ty < 0 || ty >= tiles_y || z0 < 0 || z0 + zc > depth) return LORA_EHIP;  // (out of range: a bug)
-                for (int z = z0; z < z0 + zc; ++z) cover[((long) ty * tiles_x + col) * depth + z] += 1;
-                steps += S + zc;
-            }
-            busiest2 = std::max(busiest2, steps);
-        }
-        if (workgroups) *workgroups = (int) wgs;
-        if (max_steps) *max_steps = busiest2;
-        return LORA_OK;
-    }
-    if (team) {
-        if (tiles_x > slots) return LORA_EUNSUPPORTED;
-        wgs = lora::spans_setup(sp, 1, tiles_y, depth, S, slots / tiles_x, 1, 1) * tiles_x;
-    } else {
-        wgs = lora::spans_setup(sp, tiles_x, tiles_y, depth, S, slots, 10, 9);
-    }
+    if (team && tiles_x > slots) return LORA_EUNSUPPORTED;
+    constexpr unsigned kTeams2 = lora::bf16_lanes_rules(4).decodes;
+    lora::Cut3 c{};
+    c.z_end = depth;
+    c.tiles_x = tiles_x;
+    c.tiles_y = tiles_y;
+    const long wgs = team ? lora::cut3_set_teams(c, depth, S, slots, team == 2 ? kTeams2 : 0u) : lora::cut3_set_spans(c, depth, S, slots);
     if (wgs <= 0) return LORA_EUNSUPPORTED;
-    int busiest = 0;
-    for (long lin = 0; lin < wgs; ++lin) {
-        unsigned v0, v1;
-        lora::span_range(sp, (int) (team ? lin / tiles_x : lin), v0, v1);
-        int steps = 0;
-        for (bool more = true; more;) {
-            int tx, ty, z0, zc;
-            bool any;
-            if (team) {
-                int t0;
-                any = lora::span_next(sp, S, v0, v1, 1, tiles_y, t0, ty, z0, zc);
-                tx = (int) (lin % tiles_x);
-            } else {
-                any = lora::span_next(sp, S, v0, v1, tiles_x, tiles_y, tx, ty, z0, zc);
-            }
-            more = v0 < v1;
-            if (!any) continue;
-            if (tx < 0 || tx >= tiles_x || ty < 0 || ty >= tiles_y || z0 < 0 || z0 + zc > depth) return LORA_EHIP;  // (out of range: a bug)
-            for (int z = z0; z < z0 + zc; ++z) cover[((long) ty * tiles_x + tx) * depth + z] += 1;
-            steps += S + zc;
-        }
-        busiest = std::max(busiest, steps);
-    }
     if (workgroups) *workgroups = (int) wgs;
-    if (max_steps) *max_steps = busiest;
-    return LORA_OK;
+    const bool ok = team == 2 ? lora::cut3_walk<kTeams2>(c, S, wgs, depth, cover, max_steps) : lora::cut3_walk<0u>(c, S, wgs, depth, cover, max_steps);
+    return ok ? LORA_OK : LORA_EHIP;  // (a segment out of range: a bug)
+}
+
+// The cut the fp64 (kernel = 0) or bf16 (1) register-resident kernel's launcher chooses for K applications over planes
+// [begin, end) and [begin2, end2) of h, walked the same way; *kind = the layout (enum lora_cut_kind).
+int lora_debug_cut_cover(int kernel, int K, int tiles_x, int tiles_y, int h, int begin, int end, int begin2, int end2, int slots,
+                         int fused_z_chunk, int spans3, int *cover, int *workgroups, int *max_steps, int *kind) {
+    static_assert(LORA_CUT_FIXED == lora::CUT3_KIND_FIXED && LORA_CUT_TEAMS_FINER == lora::CUT3_KIND_TEAMS_FINER, "one list of layouts");
+    if ((kernel != 0 && kernel != 1) || (K != 2 && K != 4) || tiles_x < 1 || tiles_y < 1 || slots < 1 || !cover) return LORA_EINVAL;
+    if (begin < 0 || end > h || end < begin || (end2 > begin2 && (begin2 < 0 || end2 > h)) || (end == begin && end2 <= begin2)) return LORA_EINVAL;
+    const lora::CutRules R = kernel ? lora::bf16_lanes_rules(K) : lora::lanes3_rules(K);
+    // (the largest grid of these tiles: 120 output columns and 4 NW - 2 K rows a tile, NW = 8 / 16 waves)
+    const long plane = ((long) tiles_y * ((kernel ? 64 : 32) - 2 * K) + 4) * (120L * tiles_x + 8);
+    lora::Cut3 c;
+    const long wgs = lora::cut3_plan(R, tiles_x, tiles_y, plane, begin, end, begin2, end2, slots, fused_z_chunk, spans3, c, kind);
+    if (wgs <= 0) return LORA_EUNSUPPORTED;
+    if (workgroups) *workgroups = (int) wgs;
+    const bool ok = kernel ? lora::cut3_walk<lora::bf16_lanes_rules(4).decodes>(c, R.S, wgs, h, cover, max_steps)
+                           : lora::cut3_walk<lora::lanes3_rules(4).decodes>(c, R.S, wgs, h, cover, max_steps);
+    return ok ? LORA_OK : LORA_EHIP;
 }
 
 // Two ranges of planes / rows in one call: the two end regions a slab or block driver sweeps behind its deferred wait.

@@ -94,16 +94,7 @@ struct ArgsBL {
     int h, m, n;
     int ld;
     long plane;
-    int z_begin, z_end;
-    int z_begin2, z_end2;  // a second range of planes in the same launch (chunks only): the two end regions of a slab
-    int zc;
-    int tiles_x, tiles_y;
-    Spans sp;  // zc == 0: spans (spans.h)
-    int team;  // zc == 0: 0 = a span per workgroup over all tiles; TX = a span per TEAM of the TX workgroups of a tile row
-    // team spans: the first / last tile COLUMN (rim tiles: EDGE steps, 5 % longer each) is cut into team_nr pieces (Spans sp2),
-    // the columns between into team_ni (Spans sp); team_nr == team_ni: whole teams in lockstep
-    int team_ni, team_nr;
-    Spans sp2;
+    Cut3 cut;  // how the launch is cut along z (spans.h)
 #if LORA_BL_STAMP
     long long *stamps;  // [workgroup][wave][2]: cycles of the stamped phase, steps
 #endif
@@ -303,57 +294,13 @@ __global__ __launch_bounds__(NW * 64, 4) void stencil3d_bf16_lanes_kernel(const 
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lin = xcd_contiguous(blockIdx.x, gridDim.x);
-    const int TX = a.tiles_x, TY = a.tiles_y;
-    // Spans (a.zc == 0, spans.h): the workgroup owns a range of the line of all (tile, plane) pairs and runs one SEGMENT per
-    // tile the range touches; chunks (option fused_z_chunk / spans3 = 0): one segment, chunk `lin / tiles` of its tile.
-    unsigned v0 = 0, v1 = 0;
-    int team_col = 0;  // team spans: this workgroup's tile column
-    if (a.zc == 0 && a.team) {
-        // workgroups 0 .. TX team_ni - 1: piece lin / TX of column lin mod TX (x-neighbours side by side: one L2); the rest:
-        // the extra pieces of the two rim columns
-        int j;
-        if (lin < a.team * a.team_ni) {
-            j = lin / a.team;
-            team_col = lin - j * a.team;
-        } else {
-            const int r = lin - a.team * a.team_ni;
-            j = a.team_ni + (r >> 1);
-            team_col = (r & 1) ? a.team - 1 : 0;
-        }
-        const bool rim_col = a.team_nr != a.team_ni && (team_col == 0 || team_col == a.team - 1);
-        if (rim_col)
-            span_range(a.sp2, j, v0, v1);
-        else
-            span_range(a.sp, j, v0, v1);
-    } else if (a.zc == 0) {
-        span_range(a.sp, lin, v0, v1);
-    }
-    const Spans &tsp = (a.team && a.team_nr != a.team_ni && (team_col == 0 || team_col == a.team - 1)) ? a.sp2 : a.sp;
+    // The workgroup's segments (spans.h): one chunk of a tile, or the tiles its span (or its team column's span) touches
+    constexpr CutRules rules = bf16_lanes_rules(K, LORA_BL_ABLATE);
+    Cut3Cursor cur;
+    cut3_begin<rules.decodes>(a.cut, lin, cur);
     for (bool more = true, first = true; more; first = false) {
     int tx, ty, k0, zc;
-    if (a.zc == 0) {
-        int z0;
-        bool any;
-        if (a.team) {  // the line runs over tile ROWS; this workgroup is column lin mod TX of its team's row
-            int t0;
-            any = span_next(tsp, 3 * K - 1, v0, v1, 1, TY, t0, ty, z0, zc);
-            ty = column_line_row(ty, TY);
-            tx = team_col;
-        } else {
-            any = span_next(a.sp, 3 * K - 1, v0, v1, TX, TY, tx, ty, z0, zc);
-        }
-        more = v0 < v1;
-        if (!any) continue;
-        k0 = a.z_begin + z0;
-    } else {
-        int chunk;
-        const int c0 = (a.z_end - a.z_begin + a.zc - 1) / a.zc, c1 = (a.z_end2 - a.z_begin2 + a.zc - 1) / a.zc;
-        chunk_of(lin, c0 + c1, TX, TY, chunk, tx, ty);
-        const int zb = chunk < c0 ? a.z_begin : a.z_begin2, ze = chunk < c0 ? a.z_end : a.z_end2;
-        k0 = zb + (chunk < c0 ? chunk : chunk - c0) * a.zc;
-        zc = min(a.zc, ze - k0);
-        more = false;
-    }
+    if (!cut3_next<rules.decodes>(a.cut, rules.S, (int) gridDim.x, cur, tx, ty, k0, zc, more)) continue;
     // (the segment before is done with the rows in LDS when its slowest wave is)
     if (!first) __builtin_amdgcn_s_barrier();
 #ifdef LORA_BL_TIMELINE
@@ -727,22 +674,8 @@ template <int K, int NW>
 hipError_t launch_t(const Plan &p, const void *in, void *out, int begin, int end, int begin2, int end2, hipStream_t s) {
     constexpr int OH = 4 * NW - 2 * K;
     auto kernel = stencil3d_bf16_lanes_kernel<K, NW>;
-    static int per_cu[64] = {0};  // resolved once per device (and with it the kernel itself: lora_plan_create's share)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (per_cu[dev] == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, NW * 64, 0) != hipSuccess || nb < 1) {
-            (void) hipGetLastError();
-            nb = -1;  // no workgroup of this kernel fits a CU of this device (it wants the whole 160 KB of LDS)
-        }
-        per_cu[dev] = nb;
-    }
-    if (per_cu[dev] < 0) return hipErrorLaunchOutOfResources;
+    const long slots = resident_slots<stencil3d_bf16_lanes_kernel<K, NW>>(NW * 64);  // (it wants the whole 160 KB of LDS)
+    if (slots < 0) return hipErrorLaunchOutOfResources;
     if (end <= begin && end2 <= begin2) return hipSuccess;  // prepare_3d_bf16_lanes()
     ArgsBL a{};
     a.in = static_cast<const u16 *>(in);
@@ -753,53 +686,9 @@ hipError_t launch_t(const Plan &p, const void *in, void *out, int begin, int end
     a.ld = a.n + 8;
     a.plane = (long) (a.m + 4) * (a.n + 8);
     if (a.plane * 2 >= (1L << 31)) return hipErrorInvalidValue;  // 32-bit byte offsets inside a plane
-    a.z_begin = begin;
-    a.z_end = end;
-    a.tiles_x = (a.n + kOutW - 1) / kOutW;
-    a.tiles_y = (a.m + OH - 1) / OH;
-    const long tiles = (long) a.tiles_x * a.tiles_y;
-    // How the launch is cut along z (spans.h): chunks of option fused_z_chunk; else spans (option spans3 = 1, or by itself
-    // where they pay: spans_pay); else equal chunks by the model of rounds of workgroups.
-    const long slots = (long) std::max(per_cu[dev], 1) * cus, depth = end - begin, depth2 = std::max(end2 - begin2, 0);
-    constexpr int S = 3 * K - 1;
-    long nblocks = 0;
-    a.zc = 0;
-    a.z_begin2 = begin2;
-    a.z_end2 = begin2 + (int) depth2;
-    if (p.fused_z_chunk > 0) {
-        a.zc = std::min((long) p.fused_z_chunk, std::max(depth, depth2));
-    } else if (depth2 > 0) {  // two ranges (a slab's end regions): chunks, as many workgroups as two ranges of the longer depth
-        a.zc = chunk_model(2 * tiles, std::max(depth, depth2), S, slots, 4 * K, nullptr);
-    } else {
-        const int zc_model = chunk_model(tiles, depth, S, slots, 4 * K, nullptr);
-        const bool spans = p.spans3 >= 1 || (p.spans3 < 0 && spans_pay(tiles, depth, S, slots, zc_model, 2.0 * (double) a.plane * (double) depth, 256.0e6));
-        const bool teams = p.spans3 == 2 || (p.spans3 < 0 && !spans && teams_pay(a.tiles_x, a.tiles_y, depth, S, slots, zc_model));
-        if (teams && a.tiles_x <= slots) {
-            // TEAM spans: the line runs over tile rows and is cut into one piece per team of tiles_x workgroups, one per
-            // tile of the row -- x-neighbours stay at the same depth (and, dealt out contiguously, in the same XCD's L2)
-            // The rim columns' tiles run EDGE steps, ~5 % longer each (tools/probes/bf16_lanes_timeline.hip: 2.47 against 2.34
-            // us per step; with equal pieces the launch ended with the rim columns' workgroups at 775 us, the others at
-            // 734).  So the rim columns are cut into more, shorter pieces than the columns between -- 38 and 36 at 768^3, which
-            // also uses all 256 CUs instead of 252.  The columns between stay in lockstep with one another.
-            long ni, nr;
-            team_pieces(a.tiles_x, slots, !(LORA_BL_ABLATE & 512), &ni, &nr);
-            // (and within a column between them the first and last tile ROW are rim tiles too: their planes weigh 19 : 18)
-            const bool weigh = a.tiles_x >= 3 && !(LORA_BL_ABLATE & 512);
-            const long ti = ni > 0 ? spans_setup_column(a.sp, a.tiles_y, depth, S, ni, weigh ? 19 : 1, weigh ? 18 : 1) : 0;
-            const long tr = nr > 0 ? spans_setup_column(a.sp2, a.tiles_y, depth, S, nr, 1, 1) : 0;
-            if (ti > 0 && tr >= ti) {
-                a.team = a.tiles_x;
-                a.team_ni = (int) ti;
-                a.team_nr = (int) (a.tiles_x >= 3 ? tr : ti);
-                nblocks = a.tiles_x >= 3 ? ti * (a.tiles_x - 2) + 2 * tr : ti * a.tiles_x;
-            }
-        } else if (spans) {
-            nblocks = spans_setup(a.sp, a.tiles_x, a.tiles_y, depth, S, slots, 10, 9);
-        }
-        if (nblocks == 0) a.zc = zc_model;  // (or a line that does not fit 31 bits of cost units)
-    }
-    if (a.zc > 0) nblocks = tiles * ((depth + a.zc - 1) / a.zc + (depth2 + a.zc - 1) / a.zc);
-    if (nblocks > 0x7fffffffL) return hipErrorInvalidValue;
+    const long nblocks = cut3_plan(bf16_lanes_rules(K, LORA_BL_ABLATE), (a.n + kOutW - 1) / kOutW, (a.m + OH - 1) / OH, a.plane, begin, end,
+                                   begin2, end2, slots, p.fused_z_chunk, p.spans3, a.cut);
+    if (nblocks < 0) return hipErrorInvalidValue;
     TapsSep w;
     for (int k = 0; k < 3; ++k) {
         w.c[k] = p.sep[k];

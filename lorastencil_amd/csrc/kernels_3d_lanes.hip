@@ -68,17 +68,10 @@ struct ArgsL3 {
     int h, m, n;
     int ld;
     long plane;
-    int z_begin, z_end;
-    int z_begin2, z_end2;  // a second range of planes in the same launch (chunks only): the two end regions of a slab
-    int zc;
-    int tiles_x, tiles_y;
 #ifdef LORA_L3_STAMP
     long long *stamps;  // probe builds: per workgroup {start, end} on the 100 MHz clock, {tile x | y << 16 | rim << 31, first plane}
 #endif
-    int deal;  // chunks, more workgroups' worth than slots: the launch is `slots` workgroups and chunk j goes to workgroup j mod slots (0: off)
-    int slow_c, slow_zc;  // chunks, one round with slots to spare: the tiles of the first tile column and row get slow_c chunks of slow_zc planes (0: off)
-    Spans sp;  // zc == 0: spans (spans.h)
-    int team;  // zc == 0: 0 = a span per workgroup over all tiles; TX = a span per TEAM of the TX workgroups of a tile row
+    Cut3 cut;  // how the launch is cut along z (spans.h)
 };
 
 __device__ __forceinline__ double lane_below(double v) {  // the value lane i - 1 holds (0 in lane 0)
@@ -109,66 +102,13 @@ __global__ __launch_bounds__(NW * 64, 2) void stencil3d_lanes_kernel(const ArgsL
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lin = xcd_contiguous(blockIdx.x, gridDim.x);
-    const int TX = a.tiles_x, TY = a.tiles_y;
-    // Spans (a.zc == 0, spans.h): the workgroup owns a range of the line of all (tile, plane) pairs and runs one SEGMENT per
-    // tile the range touches.  Chunks: one segment, chunk `lin / tiles` of its tile -- the tiles on the rim of the grid first
-    // (they run the slower EDGE steps throughout, and with the long workgroups dispatched first the short ones even out
-    // the end of the launch).
-    unsigned v0 = 0, v1 = 0;
-    if (a.zc == 0) span_range(a.sp, a.team ? lin / a.team : lin, v0, v1);
-    int job = lin;  // chunks dealt out (a.deal): this workgroup's next chunk
+    // The workgroup's segments (spans.h): one chunk of a tile, several when the chunks are dealt, or the tiles its span touches
+    constexpr CutRules rules = lanes3_rules(K, LORA_L3_ABLATE);
+    Cut3Cursor cur;
+    cut3_begin<rules.decodes>(a.cut, lin, cur);
     for (bool more = true, first = true; more; first = false) {
     int tx, ty, k0, zc;
-    if (a.zc == 0) {
-        int z0;
-        bool any;
-        if (a.team) {  // the line runs over tile ROWS; this workgroup is column lin mod TX of its team's row
-            int t0;
-            any = span_next(a.sp, 2 * K + 1, v0, v1, 1, TY, t0, ty, z0, zc);
-            tx = lin - (lin / a.team) * a.team;
-        } else {
-            any = span_next(a.sp, 2 * K + 1, v0, v1, TX, TY, tx, ty, z0, zc);
-        }
-        more = v0 < v1;
-        if (!any) continue;
-        k0 = a.z_begin + z0;
-    } else {
-        int chunk;
-        const int c0 = (a.z_end - a.z_begin + a.zc - 1) / a.zc, c1 = (a.z_end2 - a.z_begin2 + a.zc - 1) / a.zc;
-        if (a.slow_c > 0) {
-            // A launch of ONE round with slots to spare: the full rim tiles -- first tile column and first tile row: EDGE
-            // steps on every lane's worth of memory traffic, 8 - 17 % longer than an inner tile's (tools/probes/
-            // lanes3_timeline.hip) -- are cut into one chunk more than the others, so that the launch no longer waits for them.
-            const int nslow = TX + TY - 1, na = nslow * a.slow_c;
-            if (lin < na) {
-                const int j = lin / a.slow_c;
-                chunk = lin - j * a.slow_c;
-                tx = j < TY ? 0 : j - TY + 1;
-                ty = j < TY ? j : 0;
-                k0 = a.z_begin + chunk * a.slow_zc;
-                zc = min(a.slow_zc, a.z_end - k0);
-            } else {
-                const int l2 = lin - na, i = l2 / c0;
-                chunk = l2 - i * c0;
-                ty = 1 + i / (TX - 1);
-                tx = 1 + i - (ty - 1) * (TX - 1);
-                k0 = a.z_begin + chunk * a.zc;
-                zc = min(a.zc, a.z_end - k0);
-            }
-        } else {
-            // (a.deal: the chunks of a launch of several rounds are DEALT to the resident workgroups, chunk j to workgroup
-            // j mod slots, instead of being dispatched one workgroup each as slots fall free.  Every workgroup then runs the
-            // same number of chunks and about the same number of rim chunks.  Dispatched one by one, the 1792 chunks of
-            // box3d1r 768^3 -- seven rounds exactly, rim chunks 259 us, inner ones 225 -- left some CUs with eight chunks and
-            // others with six: the last tenth of the launch ran on 96 of 256 CUs, profiles/r04_lanes3_timeline.txt.)
-            chunk_of(job, c0 + c1, TX, TY, chunk, tx, ty);
-            const int zb = chunk < c0 ? a.z_begin : a.z_begin2, ze = chunk < c0 ? a.z_end : a.z_end2;
-            k0 = zb + (chunk < c0 ? chunk : chunk - c0) * a.zc;
-            zc = min(a.zc, ze - k0);
-            job += (int) gridDim.x;
-        }
-        more = a.deal > 0 && job < a.deal;
-    }
+    if (!cut3_next<rules.decodes>(a.cut, rules.S, (int) gridDim.x, cur, tx, ty, k0, zc, more)) continue;
     // (the segment before is done with the rows in LDS when its slowest wave is)
     if (!first) __builtin_amdgcn_s_barrier();
 #ifdef LORA_L3_STAMP
@@ -474,22 +414,8 @@ template <int TAPSET, int K, int NW>
 hipError_t launch_lanes_t(const Plan &p, const double *in, double *out, int begin, int end, int begin2, int end2, hipStream_t s) {
     constexpr int OH = 4 * NW - 2 * K;
     auto kernel = stencil3d_lanes_kernel<TAPSET, K, NW>;
-    static int per_cu[64] = {0};  // resolved once per device (and with it the kernel itself: lora_plan_create's share)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (per_cu[dev] == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, NW * 64, 0) != hipSuccess || nb < 1) {
-            (void) hipGetLastError();
-            nb = -1;  // no workgroup of this kernel is resident on this device: the plan must not choose it
-        }
-        per_cu[dev] = nb;
-    }
-    if (per_cu[dev] < 0) return hipErrorLaunchOutOfResources;
+    const long slots = resident_slots<stencil3d_lanes_kernel<TAPSET, K, NW>>(NW * 64);
+    if (slots < 0) return hipErrorLaunchOutOfResources;
     if (end <= begin && end2 <= begin2) return hipSuccess;  // prepare_3d_lanes()
     ArgsL3 a{};
     a.in = in;
@@ -500,54 +426,9 @@ hipError_t launch_lanes_t(const Plan &p, const double *in, double *out, int begi
     a.ld = a.n + 8;
     a.plane = (long) (a.m + 4) * (a.n + 8);
     if (a.plane * 8 >= (1L << 31)) return hipErrorInvalidValue;  // 32-bit byte offsets inside a plane
-    a.z_begin = begin;
-    a.z_end = end;
-    a.tiles_x = (a.n + kOutW - 1) / kOutW;
-    a.tiles_y = (a.m + OH - 1) / OH;
-    const long tiles = (long) a.tiles_x * a.tiles_y;
-    // How the launch is cut along z (spans.h): chunks of option fused_z_chunk; else spans (option spans3 = 1, or by itself
-    // where they pay: spans_pay); else equal chunks by the model of rounds of workgroups.
-    const long slots = (long) std::max(per_cu[dev], 1) * cus, depth = end - begin, depth2 = std::max(end2 - begin2, 0);
-    constexpr int S = 2 * K + 1;
-    long nblocks = 0;
-    a.zc = 0;
-    a.z_begin2 = begin2;
-    a.z_end2 = begin2 + (int) depth2;
-    if (p.fused_z_chunk > 0) {
-        a.zc = std::min((long) p.fused_z_chunk, std::max(depth, depth2));
-    } else if (depth2 > 0) {  // two ranges (a slab's end regions): chunks, as many workgroups as two ranges of the longer depth
-        a.zc = chunk_model(2 * tiles, std::max(depth, depth2), S, slots, 8 * K, nullptr);
-    } else {
-        const int zc_model = chunk_model(tiles, depth, S, slots, 8 * K, nullptr);
-        const bool spans = p.spans3 >= 1 || (p.spans3 < 0 && spans_pay(tiles, depth, S, slots, zc_model, 8.0 * (double) a.plane * (double) depth, 300.0e6));
-        if (p.spans3 == 2 && a.tiles_x <= slots) {  // (by option only: measured 4 - 9 % slower than chunks on fp64 grids, spans.h)
-            // TEAM spans: the line runs over tile rows and is cut into one piece per team of tiles_x workgroups, one per
-            // tile of the row -- x-neighbours stay at the same depth (and, dealt out contiguously, in the same XCD's L2)
-            const long nteams = spans_setup(a.sp, 1, a.tiles_y, depth, S, slots / a.tiles_x, 1, 1);
-            a.team = a.tiles_x;
-            nblocks = nteams * a.tiles_x;
-        } else if (spans) {
-            nblocks = spans_setup(a.sp, a.tiles_x, a.tiles_y, depth, S, slots, 10, 9);
-        }
-        if (nblocks == 0) a.zc = zc_model;  // (or a line that does not fit 31 bits of cost units)
-    }
-    if (a.zc > 0) nblocks = tiles * ((depth + a.zc - 1) / a.zc + (depth2 + a.zc - 1) / a.zc);
-    if (a.zc > 0 && depth2 == 0 && p.fused_z_chunk <= 0 && a.tiles_x >= 2 && a.tiles_y >= 2 && !(LORA_L3_ABLATE & 256)) {
-        // one round with slots to spare: one chunk more for the tiles of the first tile column and row (see the kernel)
-        const long c = (depth + a.zc - 1) / a.zc, nslow = a.tiles_x + a.tiles_y - 1;
-        const long slow_zc = (depth + c) / (c + 1);
-        if (nblocks <= slots && nblocks + nslow <= slots && slow_zc >= 2 * K) {
-            a.slow_c = (int) ((depth + slow_zc - 1) / slow_zc);
-            a.slow_zc = (int) slow_zc;
-            nblocks = nslow * a.slow_c + (tiles - nslow) * c;
-        }
-    }
-    if (a.zc > 0 && a.slow_c == 0 && nblocks > slots && !(LORA_L3_ABLATE & 512)) {  // several rounds: deal the chunks out
-        if (nblocks > 0x7fffffffL) return hipErrorInvalidValue;
-        a.deal = (int) nblocks;
-        nblocks = slots;
-    }
-    if (nblocks > 0x7fffffffL) return hipErrorInvalidValue;
+    const long nblocks = cut3_plan(lanes3_rules(K, LORA_L3_ABLATE), (a.n + kOutW - 1) / kOutW, (a.m + OH - 1) / OH, a.plane, begin, end,
+                                   begin2, end2, slots, p.fused_z_chunk, p.spans3, a.cut);
+    if (nblocks < 0) return hipErrorInvalidValue;
 #ifdef LORA_L3_STAMP
     extern long long *g_l3_stamps;
     extern long g_l3_stamp_blocks;

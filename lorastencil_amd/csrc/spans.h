@@ -1,5 +1,6 @@
 // spans.h -- how a launch of the register-resident 3D kernels (kernels_3d_lanes.hip, kernels_3d_bf16_lanes.hip) is cut
-// along z, when it is not cut into equal chunks per tile.
+// along z: the host's choice of a layout (cut3_plan, under each kernel's CutRules) and the decode both kernels -- and the
+// host tests -- run for it (cut3_begin / cut3_next).  Mostly about SPANS, the layout that is not equal chunks per tile:
 //
 // Those kernels run ONE workgroup per CU; a workgroup that starts anywhere along z runs S steps (its pipeline filling)
 // before its first output plane, and a launch takes as long as its busiest CU.  Equal chunks per tile leave CUs idle
@@ -13,8 +14,8 @@
 // neighbouring tiles are no longer at the same depth at the same time, so the rows they share -- and the 128-byte lines
 // their misaligned row pieces straddle -- are fetched from HBM twice.  TEAM spans (the line over tile rows, a piece per
 // team of a row's workgroups) keep the neighbours in x together.  Plan option spans3: -1 by the kernels' rules (spans_pay,
-// teams_pay), 0 chunks, 1 spans, 2 team spans.  Chunked launches have two layouts of their own in kernels_3d_lanes.hip:
-// chunks dealt to resident workgroups when there are more chunks than CUs, and one chunk more for the slow rim tiles when a
+// teams_pay), 0 chunks, 1 spans, 2 team spans.  Chunked launches of the fp64 kernel have two layouts of their own: chunks
+// dealt to resident workgroups when there are more chunks than CUs, and one chunk more for the slow rim tiles when a
 // single round has CUs to spare.
 #pragma once
 
@@ -133,13 +134,167 @@ inline bool teams_pay(int tiles_x, int tiles_y, long depth, int S, long slots, i
     return team_steps < 0.97 * chunk_steps;
 }
 
+// ---- the cut of ONE launch: what the host chooses (cut3_plan) and the kernels decode (cut3_begin / cut3_next) ----
+struct Cut3 {
+    int z_begin, z_end;
+    int z_begin2, z_end2;  // a second range of planes in the same launch (chunks only): the two end regions of a slab
+    int zc;                // > 0: chunks of zc planes; 0: spans
+    int tiles_x, tiles_y;
+    Spans sp;  // zc == 0: spans
+    int team;  // zc == 0: 0 = a span per workgroup over all tiles; TX = a span per TEAM of the TX workgroups of a tile row
+    // team spans: the first / last tile COLUMN (rim tiles: EDGE steps, 5 % longer each) is cut into team_nr pieces (Spans sp2),
+    // the columns between into team_ni (Spans sp); team_nr == team_ni: whole teams in lockstep
+    int team_ni, team_nr;
+    Spans sp2;
+    int deal;  // chunks, more workgroups' worth than slots: the launch is `slots` workgroups and chunk j goes to workgroup j mod slots (0: off)
+    int slow_c, slow_zc;  // chunks, one round with slots to spare: the tiles of the first tile column and row get slow_c chunks of slow_zc planes (0: off)
+};
+
+// The layouts only one of the two kernels has (a kernel compiles the decode of its own alone), and what cut3_plan reports:
+// which layout a launch got (where two apply, the later in this list).
+enum : unsigned {
+    CUT3_SLOW = 1,    // chunks, one more for the slow rim tiles
+    CUT3_DEAL = 2,    // chunks dealt to the resident workgroups
+    CUT3_COLUMN = 4,  // team spans over a tile COLUMN's line, its two rim rows first (else: a tile row's teams top to bottom)
+    CUT3_FINER = 8,   // team spans with the rim columns cut finer and rim rows weighed 19 : 18
+};
+enum { CUT3_KIND_FIXED = 1, CUT3_KIND_MODEL, CUT3_KIND_RANGES2, CUT3_KIND_SLOW, CUT3_KIND_DEALT, CUT3_KIND_SPANS, CUT3_KIND_TEAMS, CUT3_KIND_TEAMS_FINER };
+
+// What differs between the two kernels when a launch is cut.
+struct CutRules {
+    int S;                // steps of a segment beyond its planes
+    int min_chunk;        // chunk_model: no shorter chunks while the depth allows
+    int min_slow;         // CUT3_SLOW: no shorter chunks on the slow rim tiles
+    double cell_bytes, bytes_cap;  // spans_pay: a region's input and what of it the Infinity Cache serves twice
+    bool teams_by_rule;   // team spans where teams_pay says so (else by option spans3 = 2 only)
+    unsigned decodes;     // CUT3_* the kernel compiles a decode for
+    unsigned off;         // CUT3_* a probe build switches off (LORA_L3_ABLATE 256 / 512, LORA_BL_ABLATE 512)
+    constexpr bool plans(unsigned layout) const { return (decodes & ~off & layout) != 0; }
+};
+constexpr CutRules lanes3_rules(int K, int ablate = 0) {  // kernels_3d_lanes.hip (fp64)
+    return {2 * K + 1, 8 * K, 2 * K, 8.0, 300.0e6, false, CUT3_SLOW | CUT3_DEAL, ((ablate & 256) ? CUT3_SLOW : 0u) | ((ablate & 512) ? CUT3_DEAL : 0u)};
+}
+constexpr CutRules bf16_lanes_rules(int K, int ablate = 0) {  // kernels_3d_bf16_lanes.hip
+    return {3 * K - 1, 4 * K, 0, 2.0, 256.0e6, true, CUT3_COLUMN | CUT3_FINER, (ablate & 512) ? CUT3_FINER : 0u};
+}
+
+// Spans over all tiles of c.tiles_x x c.tiles_y; returns the workgroups, 0: the line does not fit (then: chunks)
+inline long cut3_set_spans(Cut3 &c, long depth, int S, long slots) {
+    c.zc = c.team = 0;
+    return spans_setup(c.sp, c.tiles_x, c.tiles_y, depth, S, slots, 10, 9);
+}
+
+// TEAM spans: the line runs over tile rows and is cut into one piece per team of tiles_x workgroups, one per tile of the
+// row -- x-neighbours stay at the same depth (and, dealt out contiguously, in the same XCD's L2).  `layouts` & CUT3_COLUMN:
+// a column's line has its rim rows first; & CUT3_FINER: the rim columns' tiles run EDGE steps, ~5 % longer each (tools/probes/
+// bf16_lanes_timeline.hip: 2.47 against 2.34 us per step; with equal pieces the launch ended with the rim columns' workgroups
+// at 775 us, the others at 734), so the rim columns are cut into more, shorter pieces than the columns between -- 38 and 36 at
+// 768^3, which also uses all 256 CUs instead of 252 -- and within a column between them the first and last tile ROW are rim
+// tiles too: their planes weigh 19 : 18.  The columns between stay in lockstep with one another.  Needs tiles_x <= slots.
+inline long cut3_set_teams(Cut3 &c, long depth, int S, long slots, unsigned layouts) {
+    const bool finer = (layouts & CUT3_FINER) != 0, weigh = finer && c.tiles_x >= 3;
+    long ni, nr, ti, tr;
+    team_pieces(c.tiles_x, slots, finer, &ni, &nr);
+    if (layouts & CUT3_COLUMN) {
+        ti = ni > 0 ? spans_setup_column(c.sp, c.tiles_y, depth, S, ni, weigh ? 19 : 1, weigh ? 18 : 1) : 0;
+        tr = nr > 0 ? spans_setup_column(c.sp2, c.tiles_y, depth, S, nr, 1, 1) : 0;
+    } else {
+        ti = tr = spans_setup(c.sp, 1, c.tiles_y, depth, S, ni, 1, 1);
+    }
+    if (ti <= 0 || tr < ti) return 0;
+    c.zc = 0;
+    c.team = c.tiles_x;
+    c.team_ni = (int) ti;
+    c.team_nr = (int) (c.tiles_x >= 3 ? tr : ti);
+    return c.tiles_x >= 3 ? ti * (c.tiles_x - 2) + 2 * tr : ti * c.tiles_x;
+}
+
+// How a launch over planes [begin, end) (and [begin2, end2)) of tiles_x x tiles_y tiles is cut along z on `slots` resident
+// workgroups: chunks of option fused_z_chunk; else spans or team spans (option spans3 = 1 / 2, or by themselves where they
+// pay: spans_pay, teams_pay); else equal chunks by the model of rounds of workgroups, with the kernel's own tails (slow rim
+// tiles, dealt chunks).  `plane`: cells of a padded plane.  Fills `c`; returns the workgroups to launch, -1: too many.
+inline long cut3_plan(const CutRules &R, int tiles_x, int tiles_y, long plane, int begin, int end, int begin2, int end2, long slots,
+                      int fused_z_chunk, int spans3, Cut3 &c, int *kind = nullptr) {
+    const long tiles = (long) tiles_x * tiles_y, depth = end - begin, depth2 = std::max(end2 - begin2, 0);
+    c = Cut3{};
+    c.z_begin = begin;
+    c.z_end = end;
+    c.z_begin2 = begin2;
+    c.z_end2 = begin2 + (int) depth2;
+    c.tiles_x = tiles_x;
+    c.tiles_y = tiles_y;
+    long nblocks = 0;
+    int k = CUT3_KIND_MODEL;
+    if (fused_z_chunk > 0) {
+        c.zc = (int) std::min((long) fused_z_chunk, std::max(depth, depth2));
+        k = CUT3_KIND_FIXED;
+    } else if (depth2 > 0) {  // two ranges (a slab's end regions): chunks, as many workgroups as two ranges of the longer depth
+        c.zc = chunk_model(2 * tiles, std::max(depth, depth2), R.S, slots, R.min_chunk, nullptr);
+    } else {
+        const int zc_model = chunk_model(tiles, depth, R.S, slots, R.min_chunk, nullptr);
+        const bool spans = spans3 >= 1 || (spans3 < 0 && spans_pay(tiles, depth, R.S, slots, zc_model, R.cell_bytes * (double) plane * (double) depth, R.bytes_cap));
+        // (fp64 by option only: team spans measured 4 - 9 % slower than chunks on fp64 grids, teams_pay)
+        const bool teams = spans3 == 2 || (R.teams_by_rule && spans3 < 0 && !spans && teams_pay(tiles_x, tiles_y, depth, R.S, slots, zc_model));
+        if (teams && tiles_x <= slots) {
+            nblocks = cut3_set_teams(c, depth, R.S, slots, R.decodes & ~R.off);
+            k = c.team_nr != c.team_ni ? CUT3_KIND_TEAMS_FINER : CUT3_KIND_TEAMS;
+        } else if (spans) {
+            nblocks = cut3_set_spans(c, depth, R.S, slots);
+            k = CUT3_KIND_SPANS;
+        }
+        if (nblocks == 0) c.zc = zc_model, k = CUT3_KIND_MODEL;  // (or a line that does not fit 31 bits of cost units)
+    }
+    if (c.zc > 0) nblocks = tiles * ((depth + c.zc - 1) / c.zc + (depth2 + c.zc - 1) / c.zc);
+    if (c.zc > 0 && depth2 > 0) k = CUT3_KIND_RANGES2;
+    if (R.plans(CUT3_SLOW) && c.zc > 0 && depth2 == 0 && fused_z_chunk <= 0 && tiles_x >= 2 && tiles_y >= 2) {
+        // one round with slots to spare: one chunk more for the tiles of the first tile column and row (cut3_next)
+        const long ch = (depth + c.zc - 1) / c.zc, nslow = tiles_x + tiles_y - 1;
+        const long slow_zc = (depth + ch) / (ch + 1);
+        if (nblocks <= slots && nblocks + nslow <= slots && slow_zc >= R.min_slow) {
+            c.slow_c = (int) ((depth + slow_zc - 1) / slow_zc);
+            c.slow_zc = (int) slow_zc;
+            nblocks = nslow * c.slow_c + (tiles - nslow) * ch;
+            k = CUT3_KIND_SLOW;
+        }
+    }
+    if (R.plans(CUT3_DEAL) && c.zc > 0 && c.slow_c == 0 && nblocks > slots) {  // several rounds: deal the chunks out
+        if (nblocks > 0x7fffffffL) return -1;
+        c.deal = (int) nblocks;
+        nblocks = slots;
+        k = CUT3_KIND_DEALT;
+    }
+    if (kind) *kind = k;
+    return nblocks > 0x7fffffffL ? -1 : nblocks;
+}
+
 #ifdef __HIPCC__
+// The workgroups of `Kernel` (launched with `threads` threads) resident at once on the current device, resolved once per
+// device (and with it the kernel itself: lora_plan_create's share); -1: none fits a CU, the plan must not choose it.
+template <auto Kernel>
+long resident_slots(int threads) {
+    static int per_cu[64] = {0};
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+    }
+    if (per_cu[dev] == 0) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, threads, 0) != hipSuccess || nb < 1) {
+            (void) hipGetLastError();
+            nb = -1;
+        }
+        per_cu[dev] = nb;
+    }
+    return per_cu[dev] < 0 ? -1 : (long) per_cu[dev] * cus;
+}
 #define LORA_SPANS_FN __host__ __device__ __forceinline__
 #else
 #define LORA_SPANS_FN inline
 #endif
 // (the decode below is what the kernels run; it is plain integer arithmetic and also compiles for the host, where
-// lora_debug_span_cover replays it for the tests)
+// lora_debug_span_cover and lora_debug_cut_cover walk every workgroup of a launch with it for the tests)
 // tile t of the rim-first order -> (tx, ty): the TX x TY tiles' rim (first and last row, then first and last column), then
 // the inner tiles row by row
 LORA_SPANS_FN void rim_first_tile(int t, int TX, int TY, int &tx, int &ty) {
@@ -208,5 +363,128 @@ LORA_SPANS_FN bool span_next(const Spans &sp, int S, unsigned &v0, unsigned v1, 
     v0 = e;
     zc = z1 - z0;
     return zc > 0;
+}
+
+// A workgroup's walk over its SEGMENTS (a tile and planes [k0, k0 + zc) of it), whatever the layout of the cut: spans -- the
+// workgroup owns a range of the line of all (tile, plane) pairs and runs one segment per tile the range touches; chunks -- one
+// segment, chunk `lin / tiles` of its tile, the tiles on the rim of the grid first (they run the slower EDGE steps
+// throughout, and with the long workgroups dispatched first the short ones even out the end of the launch), or several when
+// the chunks are dealt.  DEC: the CUT3_* layouts compiled in (CutRules::decodes); all of it is uniform scalar work.
+struct Cut3Cursor {
+    unsigned v0, v1;  // spans: what is left of the workgroup's range
+    int job;          // chunks: the workgroup's (next) chunk
+    int col;          // team spans: the workgroup's tile column
+    const Spans *line;  // ... and its column's line: c.sp2 for a rim column with pieces of its own, else c.sp
+};
+
+LORA_SPANS_FN int cut3_min(int a, int b) { return a < b ? a : b; }
+
+template <unsigned DEC>
+LORA_SPANS_FN void cut3_begin(const Cut3 &c, int lin, Cut3Cursor &s) {
+    s.v0 = s.v1 = 0;
+    s.job = lin;
+    s.col = 0;
+    // (The range is taken from c.sp / c.sp2 by name and the line chosen in a statement of its own on purpose: with the range
+    // taken through s.line the four-application bf16 kernel, which has no register to spare, spills 8 bytes per lane.)
+    if (c.zc == 0 && c.team) {
+        // workgroups 0 .. TX team_ni - 1: piece lin / TX of column lin mod TX (x-neighbours side by side: one L2); the rest:
+        // the extra pieces of the two rim columns
+        int j;
+        if (!(DEC & CUT3_FINER) || lin < c.team * c.team_ni) {
+            j = lin / c.team;
+            s.col = lin - j * c.team;
+        } else {
+            const int r = lin - c.team * c.team_ni;
+            j = c.team_ni + (r >> 1);
+            s.col = (r & 1) ? c.team - 1 : 0;
+        }
+        if ((DEC & CUT3_FINER) && c.team_nr != c.team_ni && (s.col == 0 || s.col == c.team - 1))
+            span_range(c.sp2, j, s.v0, s.v1);
+        else
+            span_range(c.sp, j, s.v0, s.v1);
+    } else if (c.zc == 0) {
+        span_range(c.sp, lin, s.v0, s.v1);
+    }
+    s.line = ((DEC & CUT3_FINER) && c.team && c.team_nr != c.team_ni && (s.col == 0 || s.col == c.team - 1)) ? &c.sp2 : &c.sp;
+}
+
+// The next segment of workgroup `lin` of `nwg`; `more`: call again.  false: this piece of a span holds no plane.
+template <unsigned DEC>
+LORA_SPANS_FN bool cut3_next(const Cut3 &c, int S, int nwg, Cut3Cursor &s, int &tx, int &ty, int &k0, int &zc, bool &more) {
+    const int TX = c.tiles_x, TY = c.tiles_y;
+    if (c.zc == 0) {
+        int z0;
+        bool any;
+        if (c.team) {  // the line runs over tile ROWS; this workgroup is column s.col of its team's row
+            int t0;
+            any = span_next((DEC & CUT3_FINER) ? *s.line : c.sp, S, s.v0, s.v1, 1, TY, t0, ty, z0, zc);
+            if (DEC & CUT3_COLUMN) ty = column_line_row(ty, TY);
+            tx = s.col;
+        } else {
+            any = span_next(c.sp, S, s.v0, s.v1, TX, TY, tx, ty, z0, zc);
+        }
+        more = s.v0 < s.v1;
+        k0 = c.z_begin + z0;
+        return any;
+    }
+    int chunk;
+    const int c0 = (c.z_end - c.z_begin + c.zc - 1) / c.zc, c1 = (c.z_end2 - c.z_begin2 + c.zc - 1) / c.zc;
+    if ((DEC & CUT3_SLOW) && c.slow_c > 0) {
+        // A launch of ONE round with slots to spare: the full rim tiles -- first tile column and first tile row: EDGE
+        // steps on every lane's worth of memory traffic, 8 - 17 % longer than an inner tile's (tools/probes/
+        // lanes3_timeline.hip) -- are cut into one chunk more than the others, so that the launch no longer waits for them.
+        const int lin = s.job, nslow = TX + TY - 1, na = nslow * c.slow_c;
+        if (lin < na) {
+            const int j = lin / c.slow_c;
+            chunk = lin - j * c.slow_c;
+            tx = j < TY ? 0 : j - TY + 1;
+            ty = j < TY ? j : 0;
+            k0 = c.z_begin + chunk * c.slow_zc;
+            zc = cut3_min(c.slow_zc, c.z_end - k0);
+        } else {
+            const int l2 = lin - na, i = l2 / c0;
+            chunk = l2 - i * c0;
+            ty = 1 + i / (TX - 1);
+            tx = 1 + i - (ty - 1) * (TX - 1);
+            k0 = c.z_begin + chunk * c.zc;
+            zc = cut3_min(c.zc, c.z_end - k0);
+        }
+    } else {
+        // (c.deal: the chunks of a launch of several rounds are DEALT to the resident workgroups, chunk j to workgroup
+        // j mod slots, instead of being dispatched one workgroup each as slots fall free.  Every workgroup then runs the
+        // same number of chunks and about the same number of rim chunks.  Dispatched one by one, the 1792 chunks of
+        // box3d1r 768^3 -- seven rounds exactly, rim chunks 259 us, inner ones 225 -- left some CUs with eight chunks and
+        // others with six: the last tenth of the launch ran on 96 of 256 CUs, profiles/r04_lanes3_timeline.txt.)
+        chunk_of(s.job, c0 + c1, TX, TY, chunk, tx, ty);
+        const int zb = chunk < c0 ? c.z_begin : c.z_begin2, ze = chunk < c0 ? c.z_end : c.z_end2;
+        k0 = zb + (chunk < c0 ? chunk : chunk - c0) * c.zc;
+        zc = cut3_min(c.zc, ze - k0);
+        if (DEC & CUT3_DEAL) s.job += nwg;
+    }
+    more = (DEC & CUT3_DEAL) && c.deal > 0 && s.job < c.deal;
+    return true;
+}
+
+// Host, for the tests (lora_debug_span_cover, lora_debug_cut_cover): every workgroup of a launch of `wgs` cut as `c` walked
+// with the cursor above; cover[(ty * tiles_x + tx) * h + z] += 1 per segment that sweeps plane z of h of the tile, *max_steps =
+// the busiest workgroup's steps (S per segment + its planes).  false: a segment outside the tiles or the planes.
+template <unsigned DEC>
+inline bool cut3_walk(const Cut3 &c, int S, long wgs, int h, int *cover, int *max_steps) {
+    int busiest = 0;
+    for (long lin = 0; lin < wgs; ++lin) {
+        Cut3Cursor cur;
+        cut3_begin<DEC>(c, (int) lin, cur);
+        int steps = 0;
+        for (bool more = true; more;) {
+            int tx, ty, k0, zc;
+            if (!cut3_next<DEC>(c, S, (int) wgs, cur, tx, ty, k0, zc, more)) continue;
+            if (tx < 0 || tx >= c.tiles_x || ty < 0 || ty >= c.tiles_y || k0 < 0 || k0 + zc > h) return false;
+            for (int z = k0; z < k0 + zc; ++z) cover[((long) ty * c.tiles_x + tx) * h + z] += 1;
+            steps += S + zc;
+        }
+        busiest = std::max(busiest, steps);
+    }
+    if (max_steps) *max_steps = busiest;
+    return true;
 }
 }  // namespace lora

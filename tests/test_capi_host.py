@@ -357,3 +357,82 @@ def test_spans_cover_every_tile_plane_exactly_once(L, team):
         lines = ty if team else tx * ty
         even = lines * (depth + S) / groups
         assert busiest.value <= 1.25 * even + 2 * S + 2, (tx, ty, depth, S, slots, team, busiest.value, even)
+
+
+# (tiles_x, tiles_y), h, (begin, end, begin2, end2), slots, fused_z_chunk, spans3, layout under the fp64 / the bf16 kernel's rules
+CUT_CASES = [
+    ((1, 9), 300, (0, 300, 0, 0), 256, 0, 0, "model", "model"),         # model chunks (one tile column: no slow rim tiles)
+    ((7, 14), 768, (0, 768, 0, 0), 256, 0, 0, "dealt", "model"),         # 98 tiles x 5 chunks on 256 slots
+    ((7, 14), 768, (0, 768, 0, 0), 512, 0, 0, "slow", "model"),          # one round, slots to spare
+    ((2, 3), 40, (0, 40, 0, 0), 256, 3, -1, "fixed", "fixed"),           # fixed chunks, the last one short
+    ((2, 3), 40, (0, 40, 0, 0), 256, 100, -1, "fixed", "fixed"),         # ... longer than the region
+    ((5, 6), 45, (0, 7, 20, 45), 256, 0, -1, "ranges2", "ranges2"),      # two ranges
+    ((5, 6), 45, (20, 45, 0, 7), 256, 0, -1, "ranges2", "ranges2"),      # ... the upper one first
+    ((5, 6), 45, (7, 7, 20, 45), 256, 0, -1, "ranges2", "ranges2"),      # ... the first one empty
+    ((5, 6), 45, (0, 7, 20, 45), 256, 3, -1, "dealt", "ranges2"),        # ... in fixed chunks: 360
+    ((7, 14), 800, (0, 300, 400, 800), 64, 0, 0, "dealt", "ranges2"),    # ... over several rounds
+    ((3, 5), 30, (0, 30, 0, 0), 256, 0, 0, "slow", "model"),             # slow rim tiles
+    ((3, 5), 50, (10, 40, 0, 0), 256, 0, 0, "slow", "model"),            # ... of a region inside the grid
+    ((5, 22), 64, (0, 64, 0, 0), 256, 0, 0, "slow", "model"),
+    ((3, 5), 96, (0, 96, 0, 0), 256, 3, -1, "dealt", "fixed"),           # 480 chunks dealt to 256 workgroups
+    ((7, 14), 100, (0, 100, 0, 0), 256, 3, -1, "dealt", "fixed"),
+    ((5, 22), 64, (0, 64, 0, 0), 256, 0, 1, "spans", "spans"),           # spans by option
+    ((3, 5), 100, (10, 90, 0, 0), 256, 0, -1, "spans", "spans"),         # ... by rule (spans_pay), inside the grid
+    ((40, 1), 33, (0, 33, 0, 0), 256, 0, -1, "spans", "spans"),
+    ((5, 22), 64, (0, 64, 0, 0), 256, 0, 2, "teams", "teams_finer"),     # team spans by option
+    ((2, 9), 64, (0, 64, 0, 0), 256, 0, 2, "teams", "teams"),            # ... two columns: none between the rims
+    ((7, 14), 768, (0, 768, 0, 0), 256, 0, 2, "teams", "teams_finer"),
+    ((7, 14), 768, (0, 768, 0, 0), 256, 0, -1, "dealt", "teams_finer"),  # bf16 by rule (teams_pay): 36 and 38 pieces
+    ((40, 1), 33, (0, 33, 0, 0), 64, 0, 2, "teams", "teams_finer"),
+    ((1, 1), 1, (0, 1, 0, 0), 256, 0, -1, "model", "model"),             # degenerate grids
+    ((1, 1), 1, (0, 1, 0, 0), 256, 0, 1, "spans", "spans"),
+    ((1, 1), 1, (0, 1, 0, 0), 256, 0, 2, "teams", "teams"),
+    ((2, 2), 5, (0, 5, 0, 0), 256, 0, 0, "model", "model"),
+    ((2, 2), 5, (0, 5, 0, 0), 256, 0, 1, "spans", "spans"),
+    ((2, 2), 5, (0, 5, 0, 0), 256, 0, 2, "teams", "teams"),
+    ((40, 1), 33, (0, 33, 0, 0), 256, 0, 0, "model", "model"),
+    ((3, 5), 100, (0, 100, 0, 0), 7, 0, 0, "dealt", "model"),            # seven slots
+    ((3, 5), 100, (0, 100, 0, 0), 7, 9, 0, "dealt", "fixed"),
+    ((3, 5), 100, (0, 10, 60, 100), 7, 0, 0, "dealt", "ranges2"),
+    ((3, 5), 100, (0, 100, 0, 0), 7, 0, 1, "spans", "spans"),
+    ((3, 5), 100, (0, 100, 0, 0), 7, 0, 2, "teams", "teams"),
+    ((40, 1), 33, (0, 33, 0, 0), 7, 0, 2, "spans", "spans"),             # more tile columns than slots: no teams
+]
+CUT_KINDS = {"fixed": 1, "model": 2, "ranges2": 3, "slow": 4, "dealt": 5, "spans": 6, "teams": 7, "teams_finer": 8}  # enum lora_cut_kind
+
+
+@pytest.mark.parametrize("K", [2, 4])
+@pytest.mark.parametrize("kernel", [0, 1])
+def test_every_cut_of_a_launch_covers_its_planes_exactly_once(L, kernel, K):
+    """csrc/spans.h: the cut a launch of the fp64 (kernel 0) / bf16 (1) register-resident 3D kernel gets is chosen by the
+    launchers' own planner (cut3_plan under the kernel's rules) and every workgroup is walked with the cursor the kernels
+    compile (lora_debug_cut_cover), for EVERY layout: every plane of a range is swept once per tile, no other plane at all,
+    no segment lies outside the grid, span and dealt launches fit the resident slots (dealt ones fill them), and each case
+    lands in the layout it is here for -- so each layout of each kernel is reached."""
+    import ctypes
+
+    from lorastencil_amd import _lib
+
+    lib = _lib.lib()
+    reached = set()
+    for (tx, ty), h, (b, e, b2, e2), slots, fzc, spans3, kind_f64, kind_bf16 in CUT_CASES:
+        case = (kernel, K, tx, ty, h, b, e, b2, e2, slots, fzc, spans3)
+        cover = (ctypes.c_int * (tx * ty * h))()
+        wgs, busiest, kind = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = lib.lora_debug_cut_cover(*case, cover, ctypes.byref(wgs), ctypes.byref(busiest), ctypes.byref(kind))
+        assert rc == 0, case
+        expect = np.zeros(h, dtype=np.int32)
+        expect[b:e] += 1
+        expect[b2:max(e2, b2)] += 1
+        counts = np.frombuffer(cover, dtype=np.int32).reshape(tx * ty, h)
+        assert np.array_equal(counts, np.broadcast_to(expect, counts.shape)), case
+        want = kind_bf16 if kernel else kind_f64
+        assert kind.value == CUT_KINDS[want], (case, kind.value, want)
+        reached.add(want)
+        assert wgs.value >= 1 and busiest.value >= 1
+        if want in ("spans", "teams", "teams_finer", "dealt"):
+            assert wgs.value <= slots, (case, wgs.value)
+        if want == "dealt":
+            assert wgs.value == slots, (case, wgs.value)
+    layouts = {"fixed", "model", "ranges2", "spans", "teams"} | ({"teams_finer"} if kernel else {"slow", "dealt"})
+    assert reached == layouts, (kernel, K, reached)

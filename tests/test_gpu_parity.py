@@ -544,6 +544,38 @@ def test_3d_register_resident_kernel_equals_step_by_step(L, O, shape, dims):
                 assert rel_err(got, exp) < 1e-13, f"{shape} {dims} t={t} {cut}"
 
 
+@pytest.mark.parametrize("shape", ["star3d1r", "box3d1r"])
+def test_3d_register_resident_kernel_dealt_chunks_equal_step_by_step(L, O, shape):
+    """kernels_3d_lanes.hip, chunks DEALT to the resident workgroups (spans.h): 96 x 100 x 260 in chunks of three planes is
+    15 tiles x 32 chunks = 480 chunks, more than a device has slots, so a workgroup runs chunk after chunk through the
+    same LDS.  The launchers' own planner, asked on the host with the device's CU count for slots, must report that
+    layout for the four-application launch; the whole padded buffer equals the oracle."""
+    import ctypes
+
+    import torch
+
+    from lorastencil_amd import _lib
+
+    dims = (96, 100, 260)
+    slots = torch.cuda.get_device_properties(0).multi_processor_count  # (one workgroup of this kernel per CU)
+    tx, ty = -(-dims[2] // 120), -(-dims[1] // 24)  # output columns / rows of a tile at K = 4
+    cover = (ctypes.c_int * (tx * ty * dims[0]))()
+    wgs, busiest, kind = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().lora_debug_cut_cover(0, 4, tx, ty, dims[0], 0, dims[0], 0, 0, slots, 3, -1, cover, ctypes.byref(wgs),
+                                          ctypes.byref(busiest), ctypes.byref(kind))
+    assert rc == 0 and kind.value == 5 and wgs.value == slots, (rc, kind.value, wgs.value, slots)  # LORA_CUT_DEALT
+    a = O.reference_input(shape, dims)
+    plan = L.Plan(shape, dims).set_option("steps_per_launch", 4)
+    assert plan.get_option("steps_per_launch") == 4 and plan.kernel_name == "stencil3d_lanes_kernel"
+    for t in (4, 6):
+        exp = O.run(shape, a, t)
+        got = plan_run(L, shape, a, t, options={"steps_per_launch": 4, "fused_z_chunk": 3})
+        if np.abs(exp).max() < 2.0 ** 50:
+            assert np.array_equal(got, exp), f"{shape} {dims} t={t}"
+        else:
+            assert rel_err(got, exp) < 1e-13, f"{shape} {dims} t={t}"
+
+
 @pytest.mark.parametrize("shape,dims", [("star3d1r", (200, 600, 760)), ("box3d1r", (200, 600, 760)), ("star3d1r", (512, 512, 512)),
                                         ("box3d1r", (96, 250, 1000))])
 def test_3d_register_resident_kernel_launch_shapes_at_size(L, O, shape, dims):
