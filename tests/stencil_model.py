@@ -1,5 +1,6 @@
-"""An exact integer model of the stencil and of the single-launch entries built on it -- the yardstick of
-tests/test_gpu_tap_orientation.py, checked on the CPU by tests/test_stencil_model_host.py.
+"""An exact integer model of the stencil, of the single-launch entries built on it and of the launches of K applications -- the
+yardstick of tests/test_gpu_tap_orientation.py and tests/test_gpu_multisweep_taps.py, checked on the CPU by
+tests/test_stencil_model_host.py.
 
 Why it exists.  The solver-side kernels are tested by a chain: kernel == ``plan.step_region`` plus one numpy operation, bit for
 bit.  The chain's tap tables (``1 + arange % 3`` and ``1 + min(t, n - 1 - t) % 3`` on the shape's support) are invariant under
@@ -11,7 +12,7 @@ to itself (``fingerprint_taps`` asserts both), the data are small integers, and 
 The model shares no code with the engine and none with oracle/: ``apply`` is a sum of shifted slices of the whole padded array
 in int64.  tests/test_stencil_model_host.py anchors its orientation -- which neighbour ``w[t]`` multiplies -- to the CPU oracle.
 
-Not a conftest.py and no fixtures: a plain module the two test files import.
+Not a conftest.py and no fixtures: a plain module the test files import.
 """
 import itertools
 import zlib
@@ -88,6 +89,46 @@ def fingerprint_taps(support, form="direct"):
         raise ValueError(form)
     assert (w[support] > 0).all() and not w[~support].any()
     assert equal_pairs(w, support) == 0, "two taps of the support are equal"
+    assert invariant_symmetries(w) == [], "a signed axis permutation maps the table to itself"
+    return w
+
+
+# ---- tables that stay exact at depth K (tests/test_gpu_multisweep_taps.py) -------------------------------------------------------
+# A launch of K applications grows the data by (tap sum)**K, and `1 + t` on the 49-tap box (sum 1225) passes 2**53 beyond K = 4.
+SEP_K = ((1, 2, 3), (5, 4, 7), (11, 8, 13))  # a (z), b (y), c (x): the centre entries are powers of two
+
+
+def ranked_taps(support):
+    """the values 1 .. n on the n cells of `support` (a boolean table, flat) in row-major order: pairwise distinct (0 equal
+    pairs), no symmetry of the table left.  Tap sums: 1d1r 6, 1d2r 15, diamond (star2d1r) 325, star2d3r 91, the 3D star 28,
+    the 27-tap box 378, the 49-tap box 1225 (there it is `1 + t`)."""
+    support = np.asarray(support, dtype=bool).ravel()
+    w = np.zeros(support.size, dtype=np.int64)
+    w[support] = 1 + np.arange(int(support.sum()))
+    assert equal_pairs(w, support) == 0, "two taps of the support are equal"
+    assert invariant_symmetries(w) == [], "a signed axis permutation maps the table to itself"
+    return w
+
+
+def mod7_taps():
+    """the 49-tap box at K = 6: 1 + (i + 3 j) % 7, i the row and j the column of the table.  Every row and every column holds
+    1 .. 7 once: sum 196 (196**6 * 9 < 2**53), no symmetry of the table left, but 147 equal pairs of the 1176 -- a swap of
+    two equal taps is invisible here and shows at K = 4 and 2, where the same kernel runs `1 + t`."""
+    i, j = np.divmod(np.arange(49), 7)
+    w = (1 + (i + 3 * j) % 7).astype(np.int64)
+    assert w.sum() == 196 and equal_pairs(w, np.ones(49, bool)) == 147
+    assert invariant_symmetries(w) == [], "a signed axis permutation maps the table to itself"
+    return w
+
+
+def sep_k_taps():
+    """the 27-tap box as a (x) b (x) c = (1, 2, 3) (x) (5, 4, 7) (x) (11, 8, 13) over z, y, x.  The engine's exact rank-1 test
+    reads the factors back through the centre tap, 2 * 4 * 8 = 64: divisions by a power of two, so it accepts this table
+    (c = (88, 64, 104), b = (1.25, 1, 1.75), a = (0.5, 1, 1.5)) where it refuses SEP_FACTORS.  27 distinct entries (0 equal
+    pairs), sum 6 * 16 * 32 = 3072, no symmetry left; 3072**4 * 9 < 2**53."""
+    a, b, c = (np.array(v, dtype=np.int64) for v in SEP_K)
+    w = np.einsum("i,j,k->ijk", a, b, c).ravel()
+    assert w.sum() == 3072 and equal_pairs(w, np.ones(27, bool)) == 0
     assert invariant_symmetries(w) == [], "a signed axis permutation maps the table to itself"
     return w
 
@@ -178,6 +219,65 @@ def source2(shape, u, w, f, begin, end):
     return source(shape, level1, w, f, begin, end)
 
 
+def levels(shape, u, w, K, dirichlet=False):
+    """The contract of lora_plan_stepk / lora_plan_stepn_region (include/lorastencil.h), which generalises source2 without a
+    source: level 0 is the source buffer; level k = S(level k - 1) on the WHOLE interior; the halo cells of level k are 0 at
+    odd k and the source buffer's at even k (the state the step-by-step driver leaves), under the Dirichlet option the source
+    buffer's at every level.  Returns level K as a padded int64 array."""
+    src = ints(u)
+    level = src
+    for k in range(1, K + 1):
+        level = with_halo(shape, apply(shape, level, w), src if dirichlet or k % 2 == 0 else 0)
+    return level
+
+
+def stepn(shape, u, w, K, begin, end, dirichlet=False):
+    """K applications in one launch: the interior of level K on the outermost range [begin, end)"""
+    return interior(shape, levels(shape, u, w, K, dirichlet))[begin:end]
+
+
+def levels_real(shape, u, w, K, dirichlet=False):
+    """`levels` for real data and taps, evaluated in np.longdouble (the depths no integer table keeps exact): the same shifted
+    slices, the same halo rule.  Returns the interior of level K."""
+    nd = ndim_of(shape)
+    LD = np.longdouble
+    src, w = np.asarray(u).astype(LD), np.asarray(w).astype(LD).ravel()
+    h, offs = HALO[nd], tap_offsets(nd)
+    dims = tuple(n - 2 * k for n, k in zip(src.shape, h))
+    level = src
+    for k in range(1, K + 1):
+        out = np.zeros(dims, dtype=LD)
+        for t, d in enumerate(offs):
+            if w[t]:
+                out += w[t] * level[tuple(slice(q + x, q + x + n) for q, x, n in zip(h, d, dims))]
+        level = src.copy() if dirichlet or k % 2 == 0 else np.zeros_like(src)
+        interior(shape, level)[...] = out
+    return interior(shape, level)
+
+
+def apply_periodic(shape, inner, w):
+    """S on a torus: out[i] = sum_t w[t] inner[(i + offset(t)) mod dims], by np.roll of the interior array (no halo takes
+    part; shares nothing with `apply`).  Keeps the dtype of `inner` unless it is an integer array (then int64)."""
+    nd = ndim_of(shape)
+    inner = np.asarray(inner)
+    if inner.dtype.kind in "iu":
+        inner = inner.astype(np.int64)
+    w = np.asarray(w).ravel()
+    out = np.zeros_like(inner)
+    for t, d in enumerate(tap_offsets(nd)):
+        if w[t]:
+            out = out + w[t] * np.roll(inner, tuple(-x for x in d), axis=tuple(range(nd)))
+    return out
+
+
+def periodic(shape, u, w, times):
+    """`times` sweeps under the periodic boundary: the interior after them (the halo of u is never used)"""
+    level = interior(shape, ints(u))
+    for _ in range(times):
+        level = apply_periodic(shape, level, ints(w))
+    return level
+
+
 def leapfrog2(shape, prev, cur, w, f, a1, c1, a2, c2, begin, end):
     """lora_plan_step2_leapfrog[_src]: out1 = a1 (S(cur) + f) + c1 prev; level 1 is out1 on the WHOLE interior with the values
     `prev` holds outside the interior; out2 = a2 (S(level 1) + f) + c2 cur.  Returns (out1, out2) on [begin, end)."""
@@ -246,6 +346,35 @@ def source2_magnitude(shape, u, w, f):
     """the bound of `magnitude` for the second level of source2"""
     level1 = with_halo(shape, magnitude(shape, u, w, f), 0)
     return magnitude(shape, level1, w, f)
+
+
+def levels_magnitude(shape, u, w, K, dirichlet=False):
+    """the bound of `magnitude` for every level of `levels`, which generalises source2_magnitude: the K-level model on |w| and
+    |u|.  One array per level, 1 .. K: no partial sum of that level's accumulation, in any order, exceeds it."""
+    src = np.abs(ints(u))
+    level, out = src, []
+    for k in range(1, K + 1):
+        mag = magnitude(shape, level, w)
+        out.append(mag)
+        level = with_halo(shape, mag, src if dirichlet or k % 2 == 0 else 0)
+    return out
+
+
+def periodic_magnitude(shape, u, w, times):
+    """the same for `periodic`: one array per sweep"""
+    level, out = np.abs(interior(shape, ints(u))), []
+    for _ in range(times):
+        level = apply_periodic(shape, level, np.abs(ints(w)))
+        out.append(level)
+    return out
+
+
+def data_small(shape, dims, seed, top):
+    """u as a float64 padded array of integers 0 .. top over the WHOLE padded array (non-zero halos: the halo rule of every
+    level is exercised); read-only"""
+    u = np.random.default_rng(seed).integers(0, top + 1, padded_shape(shape, dims)).astype(np.float64)
+    u.setflags(write=False)
+    return u
 
 
 def leapfrog2_magnitude(shape, prev, cur, w, f, a1, c1, a2, c2):

@@ -1110,14 +1110,16 @@ def test_bf16_register_resident_kernel_equals_step_by_step(L, O, dims):
                      {"steps_per_launch": 4, "spans3": 1}, {"steps_per_launch": 4, "spans3": 0},
                      {"steps_per_launch": 4, "spans3": 2}):  # (spans.h: spans, chunks, team spans)
             assert np.array_equal(plan_run_bf16(L, shape, bits, t, weights=w, options=opts), exp), (dims, t, opts)
-    # any exactly separable taps: a (x) b (x) c of random factors
+    # any exactly separable taps: a (x) b (x) c of random factors whose centre entries are powers of two -- the exact rank-1
+    # test reads the factors back through the centre tap, and dividing by a power of two commutes with the products' roundings
     a, b, c = (rng.standard_normal(3).astype(np.float32) for _ in range(3))
+    a[1], b[1], c[1] = 0.5, 2.0, 1.0
     ws = (a[:, None, None] * b[None, :, None]).astype(np.float32)[..., None] * c[None, None, None, :]
     ws = np.asarray(ws, dtype=np.float32).reshape(27).astype(np.float64) / 8.0
     sp = L.Plan(shape, dims, dtype="bf16").set_weights(ws).set_option("steps_per_launch", 4)
-    if sp.kernel_name == "stencil3d_bf16_lanes_kernel":  # (the exact rank-1 test may refuse products that rounded)
-        assert np.array_equal(plan_run_bf16(L, shape, bits, 9, weights=ws, options={"steps_per_launch": 4}),
-                              O.run_bf16(shape, bits, 9, weights=ws))
+    assert sp.kernel_name == "stencil3d_bf16_lanes_kernel"
+    assert np.array_equal(plan_run_bf16(L, shape, bits, 9, weights=ws, options={"steps_per_launch": 4}),
+                          O.run_bf16(shape, bits, 9, weights=ws))
     wr = rng.standard_normal(27)
     wr /= np.abs(wr).sum()
     general = L.Plan(shape, dims, dtype="bf16").set_weights(wr).set_option("steps_per_launch", 4)

@@ -30,7 +30,7 @@ Tap sets: 2D diamond / star / box through star2d1r / star2d3r / box2d3r; 3D star
 "direct" (1 + t), "sep" (the outer product (1, 2, 3) x (1, 5, 7) x (1, 11, 13)) and "sep0" ("direct" with option separable = 0).
 The fp64 single-launch entries have no separable evaluation (plan.cpp keeps the factors for the plane-streaming and
 register-resident multi-sweep kernels only), so all three run the 27-tap order; test_cases_reach_every_tap_set says what the
-plans resolve.
+plans resolve.  Those multi-sweep kernels are pinned the same way by tests/test_gpu_multisweep_taps.py.
 
 MEASURED on the MI355X: every entry agrees with the model as it is (no kernel changed); cg_small's one iteration gives numpy's
 bits (0 of the 2 units allowed); the file takes about 3 s.  With the two inner offsets of kernels_cg_small.hip's host-built table

@@ -5,6 +5,10 @@
 2. The fingerprint tables have teeth: on the GPU tests' own data, every signed axis permutation of a table and every
    transposition of two taps of its support changes the model's output, on the whole grid and on a region of two, and the GPU
    tests' comparison rejects the changed output.
+   2b. The same for tests/test_gpu_multisweep_taps.py: its K-application model (``levels``: the contract of lora_plan_stepk) and its
+   periodic model are the oracle's drivers bit for bit, whole padded buffer; its tables (ranked, mod-7, separable) are asymmetric,
+   hold the equal pairs their docstrings state, stay exact at the depth they run at, and every mirrored, transposed or swapped
+   table changes level K; the bf16 oracle has the model's orientation on the separable table.
 3. Negative control, and the record of why these files exist: the tap tables of the existing chain tests are blind to the
    symmetries and hold the equal pairs pinned below.
 """
@@ -15,6 +19,7 @@ import pytest
 
 import stencil_model as SM
 import test_gpu_cg
+import test_gpu_multisweep_taps as MS
 import test_gpu_pcg
 import test_gpu_residual
 import test_gpu_tap_orientation as T
@@ -145,6 +150,121 @@ def test_fingerprint_taps_refuse_blind_tables():
     with pytest.raises(AssertionError):
         SM.assert_exact("too big", [2 ** 53])
     assert SM.assert_exact("fits", [np.array([-5, 3]), 2 ** 53 - 1]) == 2 ** 53 - 1
+
+
+# ---- 2b. the K-application contract and the tables that stay exact at depth (tests/test_gpu_multisweep_taps.py) -----------------------
+# (shape, table, the deepest launch the GPU tests run it at, equal pairs, tap sum)
+DEEP = [("1d1r", "ranked", 8, 0, 28), ("1d2r", "ranked", 8, 0, 45), ("star2d1r", "ranked", 6, 0, 325), ("star2d3r", "ranked", 6, 0, 91),
+        ("box2d3r", "ranked", 4, 0, 1225), ("box2d3r", "mod7", 6, 147, 196), ("star3d1r", "ranked", 4, 0, 28),
+        ("box3d1r", "ranked", 3, 0, 378), ("box3d1r", "sepk", 4, 0, 3072)]
+DEEP_IDS = [f"{s}-{t}" for s, t, _, _, _ in DEEP]
+SMALL = {1: (2051,), 2: (7, 13), 3: (3, 5, 7)}  # grids of the GPU tests' own cases
+
+
+def deep_table(L, shape, tname):
+    w = MS.table(L, shape, tname)
+    return w, L.effective_weights(shape)[:L.ops.ntaps(shape)] != 0 if tname == "ranked" else np.ones(w.size, bool)
+
+
+@pytest.mark.parametrize("shape,tname,depth,pairs,total", DEEP, ids=DEEP_IDS)
+def test_the_deep_tables_are_asymmetric_and_exact(L, shape, tname, depth, pairs, total):
+    w, support = deep_table(L, shape, tname)
+    assert SM.invariant_symmetries(w) == [] and SM.equal_pairs(w, support) == pairs and int(w.sum()) == total
+    assert not w[~support].any() and (w[support] > 0).all()
+    top = MS.top_of(w, depth)
+    assert top * total ** depth < SM.EXACT and (top == 9 or (top + 1) * total ** depth >= SM.EXACT)
+    if tname == "sepk":
+        c, b, a = L.separable_3x3x3(w.astype(np.float64))  # the engine's exact rank-1 test takes the table and reads these factors
+        assert (c.tolist(), b.tolist(), a.tolist()) == ([88.0, 64.0, 104.0], [1.25, 1.0, 1.75], [0.5, 1.0, 1.5])
+        assert L.separable_3x3x3(SM.fingerprint_taps(np.ones(27, bool), "sep").astype(np.float64)) is None  # (it refuses SEP_FACTORS)
+    with pytest.raises(AssertionError):
+        MS.top_of(w, 40)
+
+
+@pytest.mark.parametrize("shape,tname,depth,pairs,total", DEEP, ids=DEEP_IDS)
+def test_the_k_level_model_is_the_oracle_bit_for_bit(O, L, shape, tname, depth, pairs, total):
+    """lora_plan_stepk's contract is "the state the step-by-step driver would leave": the oracle's driver, K sweeps from an even
+    level, WHOLE padded buffer (level K with the halo the contract gives it), under the reference and the Dirichlet rule; and
+    the rolled periodic model against the oracle's periodic driver."""
+    nd = SM.ndim_of(shape)
+    dims = ANCHOR_DIMS[nd]
+    w, _ = deep_table(L, shape, tname)
+    top = MS.top_of(w, depth)
+    u = SM.data_small(shape, dims, SM.seed_of("anchor K", shape, tname), top)
+    wf = w.astype(np.float64)
+    for K in range(1, depth + 1):
+        for dirichlet in (False, True):
+            SM.assert_exact(f"{shape} {tname} K = {K}", SM.levels_magnitude(shape, u, w, K, dirichlet))
+            want = SM.levels(shape, u, w, K, dirichlet)
+            assert np.array_equal(SM.interior(shape, want)[1:3], SM.stepn(shape, u, w, K, 1, 3, dirichlet))
+            got = O.run_bc(shape, np.array(u), K, "dirichlet", weights=wf) if dirichlet else O.run(shape, np.array(u), K, weights=wf)
+            if nd == 1:  # the 1D driver copies back all but the last element of the padded array (oracle/lorastencil_oracle.h): a halo cell
+                got, want = got[:-1], want[:-1]
+            assert SM.exactly(got, want), f"{shape} {tname} K = {K} dirichlet = {dirichlet}: the model and the oracle disagree"
+        SM.assert_exact(f"{shape} {tname} periodic {K}", SM.periodic_magnitude(shape, u, w, K))
+        got = O.interior(shape, O.run_bc(shape, np.array(u), K, "periodic", weights=wf)).copy()
+        assert SM.exactly(got, SM.periodic(shape, u, w, K)), f"{shape} {tname} K = {K}: the periodic model and the oracle disagree"
+    # the long-double model of the depths without an exact table is the same model: equal to the integers where those are exact
+    assert np.array_equal(SM.levels_real(shape, u, wf, depth).astype(np.float64), SM.stepn(shape, u, w, depth, 0, None).astype(np.float64))
+    assert np.array_equal(SM.levels_real(shape, u, wf, depth, True).astype(np.float64), SM.stepn(shape, u, w, depth, 0, None, True).astype(np.float64))
+
+
+@pytest.mark.parametrize("shape,tname,depth,pairs,total", DEEP, ids=DEEP_IDS)
+def test_every_mirrored_transposed_or_swapped_table_changes_the_k_level_output(L, shape, tname, depth, pairs, total):
+    """On the GPU tests' own data (their smallest grid with every extent above one), at the deepest launch the table runs at:
+    every signed axis permutation (under both halo rules) and every transposition of two UNEQUAL taps (under the reference
+    rule) changes level K, on the whole grid and on a region of two -- and the GPU tests' comparison rejects the changed output."""
+    nd = SM.ndim_of(shape)
+    dims = SMALL[nd]
+    assert any(c[1] == shape and c[3] == dims for c in MS.CASES)
+    w, support = deep_table(L, shape, tname)
+    top = MS.top_of(w, depth)
+    u = MS.data(shape, dims, top)
+    lo, hi = (510, 512) if nd == 1 else (1, 3)
+    count = 0
+    for dirichlet in (False, True):
+        base = SM.stepn(shape, u, w, depth, 0, None, dirichlet)
+        for name, tw in mutations(w, support):
+            if np.array_equal(tw, w):  # a swap of two equal taps (the mod-7 table has 147): not a mutation
+                continue
+            if dirichlet and name.startswith("taps"):  # (the transpositions under the reference rule only: time)
+                continue
+            wrong = SM.stepn(shape, u, tw, depth, 0, None, dirichlet)
+            assert (wrong != base).any(), f"{shape} {tname} {dims}: {name} leaves level {depth} unchanged"
+            assert (wrong[lo:hi] != base[lo:hi]).any(), f"{shape} {tname} {dims}: {name} leaves [{lo}, {hi}) of level {depth} unchanged"
+            assert not SM.exactly(wrong.astype(np.float64), base) and not SM.exactly(wrong[lo:hi].astype(np.float64), base[lo:hi]), name
+            count += 1
+    n = int(support.sum())
+    assert count >= n * (n - 1) // 2 - pairs + 2
+
+
+def bf16_nearest_even(x):
+    """float64 values -> bf16 bit patterns, round to nearest even, in numpy (finite values that fp32 holds exactly)"""
+    f = np.asarray(x, dtype=np.float64).astype(np.float32)
+    assert np.array_equal(f.astype(np.float64), x)
+    bits = f.view(np.uint32).astype(np.uint64)
+    return ((bits + 0x7FFF + ((bits >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def test_the_bf16_oracle_has_the_models_orientation_on_the_separable_table(O):
+    """One sweep of sep_k_taps / 4096 on data 0 .. 3: every product and partial sum is an integer below 2**24 over 4096 --
+    exact in fp32 in any order -- so the oracle's bf16 sweep, in both of its summation orders, must be the model's integers over
+    4096 rounded once to the nearest even bf16."""
+    shape = "box3d1r"
+    wi = SM.sep_k_taps()
+    w = MS.bf16_taps()
+    assert np.array_equal(w * 4096.0, wi.astype(np.float64))
+    for dims, _ in MS.GRIDS_BF16:
+        u = MS.data(shape, dims, 3)
+        assert SM.assert_exact("bf16 anchor", [SM.magnitude(shape, u, wi)]) < 2 ** 24
+        bits = O.to_bf16(u)
+        assert np.array_equal(O.from_bf16(bits), u)
+        want = bf16_nearest_even(SM.apply(shape, u, wi).astype(np.float64) / 4096.0)
+        mirrored = bf16_nearest_even(SM.apply(shape, u, SM.transform(wi, (0, 1, 2), (0, 0, 1))).astype(np.float64) / 4096.0)
+        assert not np.array_equal(mirrored, want)
+        for separable in (True, False):
+            got = O.interior(shape, O.run_bf16(shape, bits, 1, weights=w, separable=separable))
+            assert np.array_equal(got, want), f"{dims} separable = {separable}: the bf16 oracle and the model disagree"
 
 
 # ---- 3. negative control: what the existing tables cannot see ---------------------------------------------------------------------
