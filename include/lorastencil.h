@@ -154,6 +154,17 @@ int lora_run_host_until(int shape, int dtype, const void *in, void *out, const d
  * leapfrog depth.  LORA_EUNSUPPORTED while the thread has a default source (lora_set_default_source). */
 int lora_run_host_leapfrog(int shape, const double *in_cur, const double *in_prev, double *out, const double *params, double c,
                            int times, const int *dims, int quiet, lora_run_info *info);
+/* Variable-coefficient wave steps u(t+1) = kappa(x) S(u(t)) + b u(t) + c u(t-1) on host arrays (fp64; see lora_plan_run_wave in
+ * group B): uploads the padded host arrays `in_cur` (level 0), `in_prev` (level -1) and `kappa` (the coefficient grid, laid out
+ * like them; its halo is never read) outside the timed region, runs `times` steps with lora_plan_run_wave and copies level
+ * `times` (the whole padded array) to `out`.  With laplacian != 0 the operator runs on the zero-sum form of its taps: after the
+ * plan is opened its centre tap (index 4 / 24 / 13 in 1D / 2D / 3D) is replaced by centre - s, s the sum of all taps accumulated
+ * sequentially in table order in fp64 (lora_plan_get_weights / lora_plan_set_weights), so b = 2, c = -1 is
+ * 2 u - u- + kappa L u.  Prints the operator's three lines unless `quiet`; fills lora_run_info with hbm_gbs counting 4 x 8 bytes
+ * per point and step and steps_per_launch = the plan's wave depth.  LORA_EINVAL for a null array, times < 0, a non-finite b or c;
+ * LORA_EUNSUPPORTED while the thread has a default source (lora_set_default_source). */
+int lora_run_host_wave(int shape, const double *in_cur, const double *in_prev, const double *kappa, double *out, const double *params,
+                       double b, double c, int laplacian, int times, const int *dims, int quiet, lora_run_info *info);
 /* The Chebyshev semi-iteration for u = S(u) + f on host arrays (fp64; see lora_plan_run_chebyshev_until in group B): uploads
  * the padded host array `in` as BOTH levels and `source` (a padded host array of f, or NULL: none) beside it, runs `times` steps
  * of lora_plan_run_leapfrog_src with lora_chebyshev_coeffs(rho, 1, times) -- or, with `u` not NULL, lora_plan_run_chebyshev_until
@@ -568,6 +579,55 @@ int lora_plan_run_leapfrog_src(lora_plan *plan, void *d_prev, void *d_cur, const
  * while rho < 1.  LORA_EINVAL unless 0 <= rho < 1 (NaN included), first_step >= 1, count >= 0. */
 int lora_chebyshev_coeffs(double rho, int first_step, int count, double *a, double *c);
 /* The group-A form is lora_run_host_chebyshev (section A); lora_plan_run_chebyshev_until follows lora_plan_run_until below. */
+
+/* ---- variable-coefficient wave steps (NEW): u+ = k(x) S(u) + b u + c u-.  k (d_k: a padded device grid of the
+ * plan, laid out like d_cur) is a per-cell coefficient, b and c are scalars.  With S the zero-sum form L of the taps, b = 2,
+ * c = -1 is the wave equation in a heterogeneous medium, u(t+1) = 2 u(t) - u(t-1) + kappa(x) L u(t); b = 1, c = 0 is the explicit
+ * heterogeneous diffusion step u + kappa(x) L u.  d_k, b, c and the buffers are call arguments, not plan state: no option,
+ * kernel name, signature or leapfrog depth of the plan changes, no cached graph is touched.  The plans are those of
+ * lora_plan_wave_depth; a plan on which lora_plan_set_source was called is refused, as the leapfrog entries refuse it.
+ *   Status codes, in this order, before anything is dereferenced or launched: LORA_EINVAL for a null plan or pointer (d_k is
+ * mandatory), a non-finite b or c, a bad range (begin obeys lora_plan_region_granularity), times < 0, and any two of a call's
+ * buffers being equal (d_k included); LORA_EUNSUPPORTED for a buffer that is not 16-byte aligned, for a refused plan and for a
+ * two-step entry on a plan of wave depth below 2; LORA_ENODEVICE when the launch fails for want of a device.  All entries are
+ * asynchronous on `stream`. */
+/* 0: the plan has no wave kernel (LORA_BF16 plans, 2D plans of LORA_VARIANT_MFMA, plans that currently carry a source);
+ * 2: also the two-step launch (2D plans of the direct variant with an even innermost extent); 1: single steps (every other
+ * plan; a 3D plan reads 1 with or without option "leap3": there is no two-step wave launch in 3D).  A function of the plan
+ * alone; needs no device. */
+int lora_plan_wave_depth(const lora_plan *plan);
+/* One step, in place: on every interior cell of the swept range
+ *     d_prev = fl( fl( fl(k * acc) + fl(b * u) ) + fl(c * d_prev) )
+ * where acc has exactly the bits the plan's plain single sweep of d_cur stores, u is the cell of d_cur and k the cell of d_k at
+ * the store's address, and the five operations are separate fp64 roundings, never a fused multiply-add.  A step equals
+ * "lora_plan_step_region into a spare grid, then the five operations one at a time on the interior of the region" bit for bit,
+ * non-finite values included.  k is read with the store's own addressing and predicate: its halo cells are never used, it is
+ * never written; d_cur is never written; of d_prev only the cells stored are read, each by the lane that stores it; nothing
+ * outside the padded arrays is touched. */
+int lora_plan_step_wave(lora_plan *plan, const void *d_cur, void *d_prev, const void *d_k, double b, double c, void *stream);
+int lora_plan_step_wave_region(lora_plan *plan, const void *d_cur, void *d_prev, const void *d_k, double b, double c, int begin, int end,
+                               void *stream);
+/* Two steps in one launch (plans of wave depth 2; LORA_EUNSUPPORTED otherwise): d_out1 = k S(d_cur) + b d_cur + c d_prev and
+ * d_out2 = k S(d_out1) + b d_out1 + c d_cur on the interior cells of rows [begin, end), with the rounding rule above at both
+ * levels; the five buffers are pairwise distinct.  Level-1 cells outside the interior take the value d_prev holds there; direct
+ * taps in row-major order at both levels whatever option "lowrank_valu" says: a launch equals two single steps bit for bit on
+ * any data.  Halo cells of d_out1 / d_out2 are never written, d_prev, d_cur and d_k never at all; d_k is read on interior
+ * cells alone, at both levels. */
+int lora_plan_step2_wave(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_k, void *d_out1, void *d_out2, double b,
+                         double c, void *stream);
+int lora_plan_step2_wave_region(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_k, void *d_out1, void *d_out2,
+                                double b, double c, int begin, int end, void *stream);
+/* `times` steps from d_prev = level -1 and d_cur = level 0.  Buffer placement, the three boundary modes and the schedule are
+ * lora_plan_run_leapfrog's with the wave depth in place of the leapfrog depth: on plans of wave depth 2, times / 4 pairs of
+ * two-step launches through the plan's two scratch grids (the same two; lora_plan_prepare_wave allocates them; d_k must differ
+ * from them as from d_prev and d_cur, else the run takes single steps), times % 4 single steps at the end; single steps only
+ * under LORA_BC_PERIODIC (d_k is never wrapped: its halo is never read), with option "scratch" = 0, and on every 3D plan
+ * whatever option "leap3" says.  Direct launches.  Whatever the schedule, the result is bit for bit that of `times` single
+ * steps. */
+int lora_plan_run_wave(lora_plan *plan, void *d_prev, void *d_cur, const void *d_k, double b, double c, int times, void *stream);
+/* Allocates now what lora_plan_run_wave(plan, ..., times, ...) would allocate on first need.  Optional and idempotent. */
+int lora_plan_prepare_wave(lora_plan *plan, int times);
+/* The group-A form is lora_run_host_wave (section A). */
 
 /* ---- reductions over grids on the device (NEW: the reference prints its "Result range" from a host loop over the copied-back
  * array).  Both read the interior cells of the outermost range [begin, end) as lora_plan_step_region counts it (begin == end

@@ -46,6 +46,7 @@ from .ops import (  # noqa: F401
     run_host_cg,
     run_host_chebyshev,
     run_host_leapfrog,
+    run_host_wave,
     run_host_mg,
     run_host_pcg,
     run_host_theta_mg,

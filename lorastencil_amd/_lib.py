@@ -280,6 +280,14 @@ SIGNATURES = {
                                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp]),
     "lora_plan_run_leapfrog_src": (ctypes.c_int, [_vp, _vp, _vp, _vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _vp]),
     "lora_chebyshev_coeffs": (ctypes.c_int, [ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    "lora_plan_wave_depth": (ctypes.c_int, [_vp]),
+    "lora_plan_step_wave": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "lora_plan_step_wave_region": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp]),
+    "lora_plan_step2_wave": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "lora_plan_step2_wave_region": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                   _vp]),
+    "lora_plan_run_wave": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp]),
+    "lora_plan_prepare_wave": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lora_plan_run_chebyshev_until": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, ctypes.POINTER(Until), ctypes.POINTER(UntilResult),
                                                      _vp]),
     "lora_run_host_chebyshev": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.POINTER(Until),
@@ -325,6 +333,8 @@ SIGNATURES = {
                                               ctypes.POINTER(ThetaResult)]),
     "lora_run_host_leapfrog": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int,
                                               ctypes.POINTER(RunInfo)]),
+    "lora_run_host_wave": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                          _ip, ctypes.c_int, ctypes.POINTER(RunInfo)]),
     "lora_plan_destroy": (None, [_vp]),
     "lora_default_params": (ctypes.c_int, [ctypes.c_int, _dp]),
     "lora_effective_weights": (ctypes.c_int, [ctypes.c_int, _dp, _dp]),

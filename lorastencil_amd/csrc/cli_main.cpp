@@ -23,6 +23,9 @@
 //                      (lora_run_host_leapfrog; default C = -1, the wave equation); one GPU, fp64
 //   --leap3            (lorastencil_3d only, with --leapfrog or --chebyshev) the run takes two leapfrog steps per launch
 //                      (lora_set_default_leap3; plan option leap3); same results, same output
+//   --wave=K0[,K1]     time_size steps of the wave equation in a heterogeneous medium, u(t+1) = 2 u(t) - u(t-1) + kappa(x) L u(t)
+//                      from u(-1) = u(0), L the zero-sum form of the taps (lora_run_host_wave with b = 2, c = -1, laplacian = 1);
+//                      kappa = K0 on the first half of the outermost dimension and K1 (default K0) on the rest; one GPU, fp64
 //   --chebyshev=RHO    solve u = S(u) + f by the Chebyshev semi-iteration for a spectrum of S inside [-RHO, RHO], 0 <= RHO < 1
 //                      (lora_run_host_chebyshev): time_size steps, or with --until=TOL until the true residual
 //                      max |S(u) + f - u| <= TOL (time_size is the cap); f from --source= when given; one GPU, fp64
@@ -168,6 +171,8 @@ int main(int argc, char *argv[]) {
     double source_value = 0.0;
     bool leapfrog = false;
     double leapfrog_c = -1.0;
+    bool wave = false;
+    double wave_k[2] = {0.0, 0.0};
     bool chebyshev = false;
     double chebyshev_rho = 0.0;
     bool leap3 = false, coarse1 = false, mgfuse = false;
@@ -234,6 +239,20 @@ int main(int argc, char *argv[]) {
                 return 1;
             }
             leapfrog = true;
+        }
+        else if (a.rfind("--wave=", 0) == 0) {
+            const std::string v = a.substr(7);
+            const size_t comma = v.find(',');
+            const std::string part[2] = {v.substr(0, comma), comma == std::string::npos ? v.substr(0, comma) : v.substr(comma + 1)};
+            for (int q = 0; q < 2; ++q) {
+                char *rest = nullptr;
+                wave_k[q] = std::strtod(part[q].c_str(), &rest);
+                if (part[q].empty() || *rest != '\0' || !std::isfinite(wave_k[q])) {
+                    std::cerr << "Invalid argument: --wave=K0[,K1] needs one or two finite numbers.\n";
+                    return 1;
+                }
+            }
+            wave = true;
         }
         else if (a == "--leap3" && kDim == 3)
             leap3 = true;
@@ -375,6 +394,11 @@ int main(int argc, char *argv[]) {
             std::cerr << "Unknown option: " << a << "\n";
             return 1;
         }
+    }
+
+    if (wave && (gpus_given || grid[0] > 0 || check || until || source_kind || leapfrog || chebyshev || cg || mg || pcg || implicit || bf16)) {
+        std::cerr << "--wave runs on one GPU in fp64 for a fixed number of steps without a source: not with --gpus, --grid, --check, --until, --source, --leapfrog, --chebyshev, --cg, --mg, --pcg, --implicit or --dtype=bf16\n";
+        return 1;
     }
 
     if (precond && !implicit) {
@@ -575,6 +599,16 @@ int main(int argc, char *argv[]) {
             std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
             return 1;
         }
+    } else if (wave) {
+        // prev = cur: zero initial velocity; kappa in two halves of the outermost dimension (its halo cells are never read)
+        std::vector<double> kappa(count, wave_k[0]);
+        const size_t outer = (size_t) dims[0] + (kDim == 3 ? 2 : 8), slice = count / outer, half = (kDim == 3 ? 1 : 4) + (size_t) dims[0] / 2;
+        std::fill(kappa.begin() + half * slice, kappa.end(), wave_k[1]);
+        const int rc = lora_run_host_wave(shape, matrix.data(), matrix.data(), kappa.data(), output.data(), params, 2.0, -1.0, 1, times, dims, 0, nullptr);
+        if (rc != LORA_OK) {
+            std::printf("LoRAStencil HIP Error: %s %s\n", lora_strerror(rc), lora_last_error());
+            return 1;
+        }
     } else if (chebyshev) {
         // both starting levels are the input; with --until time_size is the cap; the operator prints the reference's three lines
         how.max_times = times;
@@ -683,6 +717,7 @@ int main(int argc, char *argv[]) {
                     how.check_every);
     if (extra && normalize) std::printf("Taps normalised (weights / sum of weights)\n");
     if (extra && leapfrog) std::printf("Leapfrog: u(t+1) = S(u(t)) + %g u(t-1), u(-1) = u(0)\n", leapfrog_c);
+    if (extra && wave) std::printf("Wave: u(t+1) = 2 u(t) - u(t-1) + kappa L u(t), u(-1) = u(0), kappa = %g | %g (halves of the outermost dimension)\n", wave_k[0], wave_k[1]);
     if (extra && source_kind)
         std::printf(implicit ? "Source: f = %g %s (du/dt = S(u) + f - u)\n" : chebyshev || cg || mg || pcg ? "Source: f = %g %s (u = S(u) + f)\n" : "Source: f = %g %s (u <- S(u) + f)\n", source_value, source_kind == 1 ? "on every interior cell" : "on the interior centre cell");
     if (extra) {

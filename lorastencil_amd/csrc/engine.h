@@ -423,6 +423,20 @@ inline hipError_t launch_leapfrog2_src(const Plan &p, const double *prev, const 
                        : launch_leapfrog2_src_2d(p, prev, cur, f, out1, out2, a1, c1, a2, c2, begin, end, s);
 }
 
+// ---- variable-coefficient wave steps, prev <- k S(cur) + b cur + c prev with k a padded grid (kernels_step.hip: one step;
+// kernels_2d_wave2.hip: two per launch in 2D; 3D has single steps only, whatever option leap3 says).  k is a call argument.
+// Picked by the *_wave entries of leapfrog.cpp and by nothing else.
+hipError_t launch_wave(const Plan &p, const double *cur, double *prev, const double *k, double b, double c, int begin, int end,
+                       hipStream_t s);
+hipError_t launch_wave2_2d(const Plan &p, const double *prev, const double *cur, const double *k, double *out1, double *out2, double b,
+                           double c, int begin, int end, hipStream_t s);
+// 0: no wave kernel (the plans of leapfrog depth 0); 2: also the two-step launch (2D: direct variant, even innermost extent);
+// 1: single steps (every other plan, every 3D plan among them).
+inline int wave_depth(const Plan &p) {
+    if (leapfrog_depth(p) == 0) return 0;
+    return p.ndim == 2 && !p.generic ? 2 : 1;
+}
+
 // ---- the launch dispatcher (capi.cpp): the one place that picks a launch's kernel ----------------------------
 // One launch of `napps` applications over the outermost interior range [begin, end) and, in the same launch,
 // [begin2, end2) (register-resident 3D kernels only; empty = none).

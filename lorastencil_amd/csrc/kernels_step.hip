@@ -5,6 +5,8 @@
 //     EPI_LEAP          prev = fl(acc + fl(c prev))                      lora_plan_step_leapfrog      (launch_leapfrog)
 //     EPI_LEAP_SCALED   prev = fl(fl(a acc) + fl(c prev))                lora_plan_step_leapfrog_src  (launch_leapfrog_src, f == nullptr)
 //     EPI_LEAP_SRC      prev = fl(fl(a fl(acc + f)) + fl(c prev))        lora_plan_step_leapfrog_src  (launch_leapfrog_src)
+//     EPI_WAVE          prev = fl(fl(fl(k acc) + fl(b u)) + fl(c prev))  lora_plan_step_wave          (launch_wave; k: a grid
+//                       in f's place, read as f is; u: the cell of `in` at the store's address, on chip in every family)
 // Every operation after `acc` is one separate fp64 rounding, never a fused multiply-add.  Each rule is its own instantiation of
 // one kernel body per family; an operand the rule does not read produces no load.
 //
@@ -71,15 +73,16 @@ __global__ __launch_bounds__(256) void stencil1d_step_kernel(const double *__res
             a1 = fma(W.w[t], win[t + 1], a1);
         }
         d2 r;
-        r.x = step_epilogue<EPI>(a0, sv.x, sa, c, pv.x);
-        r.y = step_epilogue<EPI>(a1, sv.y, sa, c, pv.y);
+        r.x = step_epilogue<EPI>(a0, sv.x, sa, c, pv.x, win[4]);
+        r.y = step_epilogue<EPI>(a1, sv.y, sa, c, pv.y, win[5]);
         *reinterpret_cast<d2 *>(out + i + 4) = r;
     } else {
         // odd tail: one point, scalar loads stay inside the padded arrays
         double a0 = 0.0;
 #pragma unroll
         for (int t = 0; t < 9; ++t) a0 = fma(W.w[t], in[i + t], a0);
-        out[i + 4] = step_epilogue<EPI>(a0, cell_at<epi_reads_f(EPI)>(f, i + 4), sa, c, cell_at<epi_reads_prev(EPI)>(out, i + 4));
+        out[i + 4] = step_epilogue<EPI>(a0, cell_at<epi_reads_f(EPI)>(f, i + 4), sa, c, cell_at<epi_reads_prev(EPI)>(out, i + 4),
+                                        cell_at<epi_reads_u(EPI)>(in, i + 4));
     }
 }
 
@@ -206,9 +209,14 @@ __global__ __launch_bounds__(256, 3) void stencil2d_step_kernel(const ArgsStep2D
             const int r = j - 6;
             const int row = i0 + wv * RPT + r;
             if (col < a.n && row < a.row_end) {
+                // EPI_WAVE: the centre cells of the row, re-read from the tile (it is never overwritten)
+                d2 u;
+                u.x = 0.0;
+                u.y = 0.0;
+                if constexpr (epi_reads_u(EPI)) u = *reinterpret_cast<const d2 *>(tile + (wv * RPT + r + 3) * kLdsW + 2 * lane + 4);
                 d2 v;
-                v.x = step_epilogue<EPI>(acc0[r], sv[r].x, a.sa, a.c, pv[r].x);
-                v.y = step_epilogue<EPI>(acc1[r], sv[r].y, a.sa, a.c, pv[r].y);
+                v.x = step_epilogue<EPI>(acc0[r], sv[r].x, a.sa, a.c, pv[r].x, u.x);
+                v.y = step_epilogue<EPI>(acc1[r], sv[r].y, a.sa, a.c, pv[r].y, u.y);
                 *reinterpret_cast<d2 *>(a.out + (size_t) (row + 4) * a.ld + (col + 4)) = v;
             }
         }
@@ -265,7 +273,7 @@ struct ArgsStep3D {
 // (the four pieces of f per plane do not fit the 128 registers of four workgroups per CU beside the prev pieces: three for the
 // rule that reads both, as the 2D kernel has)
 template <int TAPSET, int EPI>
-__global__ __launch_bounds__(256, EPI == EPI_LEAP_SRC ? 3 : 4) void stencil3d_step_kernel(const ArgsStep3D a, const Taps27 W) {
+__global__ __launch_bounds__(256, (EPI == EPI_LEAP_SRC || EPI == EPI_WAVE) ? 3 : 4) void stencil3d_step_kernel(const ArgsStep3D a, const Taps27 W) {
     constexpr int RY = kRY;
     constexpr int TY = 4 * RY;
     constexpr int LH = TY + 2;
@@ -334,6 +342,13 @@ __global__ __launch_bounds__(256, EPI == EPI_LEAP_SRC ? 3 : 4) void stencil3d_st
     write_plane(0);
     __syncthreads();
 
+    d2 uc[RY];  // EPI_WAVE: the centre cells of the plane consumed last (unread, and gone, in every other rule)
+#pragma unroll
+    for (int r = 0; r < RY; ++r) {
+        uc[r].x = 0.0;
+        uc[r].y = 0.0;
+    }
+
     auto consume = [&](int p, auto phase_tag) {
         constexpr int PHASE = decltype(phase_tag)::value;
         const bool more = p + 1 < nplanes;
@@ -397,8 +412,8 @@ __global__ __launch_bounds__(256, EPI == EPI_LEAP_SRC ? 3 : 4) void stencil3d_st
                 for (int r = 0; r < RY; ++r) {
                     if (i0 + wv * RY + r < a.m) {
                         d2 v;
-                        v.x = step_epilogue<EPI>(acc0[s][r], sv[r].x, a.sa, a.c, pv[r].x);
-                        v.y = step_epilogue<EPI>(acc1[s][r], sv[r].y, a.sa, a.c, pv[r].y);
+                        v.x = step_epilogue<EPI>(acc0[s][r], sv[r].x, a.sa, a.c, pv[r].x, uc[r].x);
+                        v.y = step_epilogue<EPI>(acc1[s][r], sv[r].y, a.sa, a.c, pv[r].y, uc[r].y);
                         *reinterpret_cast<d2 *>(dst + (long) r * a.ld) = v;
                     }
                 }
@@ -408,6 +423,13 @@ __global__ __launch_bounds__(256, EPI == EPI_LEAP_SRC ? 3 : 4) void stencil3d_st
                 acc0[s][r] = 0.0;
                 acc1[s][r] = 0.0;
             }
+        }
+        // EPI_WAVE: plane p is the centre plane of the output plane the NEXT step completes.  That step's write_plane refills
+        // this tile before its barrier -- a faster wave may already be overwriting it at the store -- so the lane's centre
+        // pieces (strip row r + 1, window columns 2, 3) are carried in registers from here, in front of this step's barrier
+        if constexpr (epi_reads_u(EPI)) {
+#pragma unroll
+            for (int r = 0; r < RY; ++r) uc[r] = *reinterpret_cast<const d2 *>(strip + (r + 1) * kLdsW + 2);
         }
         if (more) write_plane((p + 1) & 1);
         __syncthreads();
@@ -477,7 +499,7 @@ __global__ __launch_bounds__(256) void stencil2d_generic_step_kernel(const doubl
             const double w = W.w[dy * 7 + dx];
             if (w != 0.0) s = fma(w, c[(dy - 3) * ld + (dx - 3)], s);
         }
-    out[cell] = step_epilogue<EPI>(s, sv, sa, cf, pv);
+    out[cell] = step_epilogue<EPI>(s, sv, sa, cf, pv, cell_at<epi_reads_u(EPI)>(in, cell));
 }
 
 template <int EPI>
@@ -503,7 +525,7 @@ __global__ __launch_bounds__(256) void stencil3d_generic_step_kernel(const doubl
                 const double w = W.w[dz * 9 + dy * 3 + dx];
                 if (w != 0.0) s = fma(w, c[(dz - 1) * plane + (dy - 1) * ld + (dx - 1)], s);
             }
-    out[cell] = step_epilogue<EPI>(s, sv, sa, cf, pv);
+    out[cell] = step_epilogue<EPI>(s, sv, sa, cf, pv, cell_at<epi_reads_u(EPI)>(in, cell));
 }
 
 template <int EPI>
@@ -577,6 +599,8 @@ hipError_t launch_step(int epi, const Plan &p, const double *in, double *out, co
             return launch_step_t<EPI_LEAP>(p, in, out, f, sa, c, begin, end, s);
         case EPI_LEAP_SCALED:
             return launch_step_t<EPI_LEAP_SCALED>(p, in, out, f, sa, c, begin, end, s);
+        case EPI_WAVE:
+            return launch_step_t<EPI_WAVE>(p, in, out, f, sa, c, begin, end, s);
         default:
             return launch_step_t<EPI_LEAP_SRC>(p, in, out, f, sa, c, begin, end, s);
     }
@@ -601,6 +625,13 @@ hipError_t launch_leapfrog(const Plan &p, const double *in, double *prev, double
 hipError_t launch_leapfrog_src(const Plan &p, const double *in, double *prev, const double *f, double sa, double c, int begin, int end,
                                hipStream_t s) {
     return launch_step(f ? EPI_LEAP_SRC : EPI_LEAP_SCALED, p, in, prev, f, sa, c, begin, end, s);
+}
+
+// One step prev <- k S(in) + b in + c prev in place over `prev`, k a padded grid read like the f above (the same plans: the
+// entries of leapfrog.cpp refuse the others).
+hipError_t launch_wave(const Plan &p, const double *in, double *prev, const double *k, double b, double c, int begin, int end,
+                       hipStream_t s) {
+    return launch_step(EPI_WAVE, p, in, prev, k, b, c, begin, end, s);
 }
 
 // The kernel lora_plan_kernel_name reports for a single source sweep of this plan: the EPI_SOURCE instantiation of

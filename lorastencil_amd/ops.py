@@ -465,6 +465,28 @@ def run_host_leapfrog(shape, cur: np.ndarray, prev: np.ndarray, c: float = -1.0,
     return out, info
 
 
+def run_host_wave(shape, cur: np.ndarray, prev: np.ndarray, kappa: np.ndarray, b: float = 2.0, c: float = -1.0, laplacian: bool = True,
+                  times: int = 1, params=None, quiet: bool = True):
+    """``times`` variable-coefficient wave steps u(t+1) = kappa S(u(t)) + b u(t) + c u(t-1) from the padded float64 host arrays ``cur``
+    (level 0), ``prev`` (level -1) and ``kappa`` (the per-cell coefficient; its halo is never read) (lora_run_host_wave).  With
+    ``laplacian`` S is the zero-sum form of the taps, so b = 2, c = -1 is 2 u - u- + kappa L u.  Returns (level ``times`` as a padded
+    array, RunInfo)."""
+    sid = shape_id(shape)
+    cur = np.ascontiguousarray(cur, dtype=np.float64)
+    prev = np.ascontiguousarray(prev, dtype=np.float64)
+    kappa = np.ascontiguousarray(kappa, dtype=np.float64)
+    h = halo(sid)
+    if cur.ndim != len(h) or prev.shape != cur.shape or kappa.shape != cur.shape:
+        raise ValueError("cur, prev and kappa must be padded arrays of the shape's rank and of one size")
+    dims = [cur.shape[i] - 2 * h[i] for i in range(cur.ndim)]
+    out = np.zeros_like(cur)
+    pp = None if params is None else _p(np.ascontiguousarray(params, dtype=np.float64))
+    info = RunInfo()
+    check(_lib.lib().lora_run_host_wave(sid, _p(cur), _p(prev), _p(kappa), _p(out), pp, float(b), float(c), int(bool(laplacian)), int(times),
+                                        _dims_arg(dims), int(quiet), ctypes.byref(info)), f"lora_run_host_wave({SHAPE_NAMES.get(sid, sid)})")
+    return out, info
+
+
 def chebyshev_coeffs(rho: float, first_step: int = 1, count: int = 1):
     """The Chebyshev schedule for a spectrum inside [-rho, rho] (lora_chebyshev_coeffs; host only): (a, c) as float64 arrays with
     a[i] = w(first_step + i), c[i] = 1 - a[i]; w(1) = 1, w(2) = 1 / (1 - rho^2 / 2), w(k+1) = 1 / (1 - rho^2 w(k) / 4).  For the
@@ -891,6 +913,41 @@ class Plan:
         """Allocate now what ``run_leapfrog(..., times)`` would allocate on first need (its two scratch grids)."""
         check(_lib.lib().lora_plan_prepare_leapfrog(self._h, int(times)), "lora_plan_prepare_leapfrog")
         return self
+
+    # -- variable-coefficient wave steps: u+ = k S(u) + b u + c u-; d_k is a padded device grid, read on interior cells alone
+    @property
+    def wave_depth(self) -> int:
+        """0: no wave kernel; 1: single steps; 2: also the two-step launch, 2D only (lora_plan_wave_depth)."""
+        return _lib.lib().lora_plan_wave_depth(self._h)
+
+    def step_wave(self, d_cur, d_prev, d_k, b: float = 2.0, c: float = -1.0, stream=None):
+        """One step in place: d_prev <- d_k * S(d_cur) + b * d_cur + c * d_prev on the interior (lora_plan_step_wave)."""
+        check(_lib.lib().lora_plan_step_wave(self._h, _ptr(d_cur), _ptr(d_prev), _ptr(d_k), float(b), float(c), _stream(stream)),
+              "lora_plan_step_wave")
+
+    def step_wave_region(self, d_cur, d_prev, d_k, b: float, c: float, begin: int, end: int, stream=None):
+        check(_lib.lib().lora_plan_step_wave_region(self._h, _ptr(d_cur), _ptr(d_prev), _ptr(d_k), float(b), float(c), int(begin), int(end),
+                                                    _stream(stream)), "lora_plan_step_wave_region")
+
+    def step2_wave(self, d_prev, d_cur, d_k, d_out1, d_out2, b: float = 2.0, c: float = -1.0, stream=None):
+        """Two steps in one launch: d_out1 = k S(d_cur) + b d_cur + c d_prev, d_out2 = k S(d_out1) + b d_out1 + c d_cur
+        (lora_plan_step2_wave; plans of wave depth 2)."""
+        check(_lib.lib().lora_plan_step2_wave(self._h, _ptr(d_prev), _ptr(d_cur), _ptr(d_k), _ptr(d_out1), _ptr(d_out2), float(b), float(c),
+                                              _stream(stream)), "lora_plan_step2_wave")
+
+    def step2_wave_region(self, d_prev, d_cur, d_k, d_out1, d_out2, b: float, c: float, begin: int, end: int, stream=None):
+        check(_lib.lib().lora_plan_step2_wave_region(self._h, _ptr(d_prev), _ptr(d_cur), _ptr(d_k), _ptr(d_out1), _ptr(d_out2), float(b),
+                                                     float(c), int(begin), int(end), _stream(stream)), "lora_plan_step2_wave_region")
+
+    def run_wave(self, d_prev, d_cur, d_k, b: float = 2.0, c: float = -1.0, times: int = 1, stream=None):
+        """``times`` steps from d_prev = level -1, d_cur = level 0; level ``times`` ends in ``d_cur`` if ``times`` is even, in
+        ``d_prev`` if odd (lora_plan_run_wave)."""
+        check(_lib.lib().lora_plan_run_wave(self._h, _ptr(d_prev), _ptr(d_cur), _ptr(d_k), float(b), float(c), int(times), _stream(stream)),
+              "lora_plan_run_wave")
+
+    def prepare_wave(self, times: int):
+        """Allocate now what ``run_wave(..., times)`` would allocate on first need (the two scratch grids)."""
+        check(_lib.lib().lora_plan_prepare_wave(self._h, int(times)), "lora_plan_prepare_wave")
 
     # -- leapfrog steps with a source and a scale: u+ = a (S(u) + f) + c u-; d_f is a padded device grid or None
     def step_leapfrog_src(self, d_cur, d_prev, d_f, a: float = 1.0, c: float = -1.0, stream=None):
