@@ -356,7 +356,7 @@ int lora_set_default_mgfuse(int on);
  *                     workgroup, the time levels pipelined over two groups of waves): -1 (default) = in plans that fuse six
  *                     applications per launch, where it also runs the four- / two-application tails; 0 never; 1 at every
  *                     depth (6 / 4 / 2).  wg_rows (output rows per chunk; 0 = one round of resident workgroups),
- *                     wg_edge_pct (how much shorter the chunks of the first / last column strip are, per cent; -1 = 60),
+ *                     wg_edge_pct (how much shorter the chunks of the first / last column strip are, per cent; -1 = 12 at six applications, 60 below),
  *                     wg_prio (log2 of the time slice, in 10 ns ticks, of the alternating wave priorities that share a
  *                     CU evenly between its two workgroups; 0 = off)
  *   lanes3            3D fused launches through the register-resident kernels (kernels_3d_lanes.hip, kernels_3d_bf16_lanes.hip:
@@ -423,6 +423,12 @@ int lora_plan_stepn_region2(lora_plan *plan, int napps, const void *d_in, void *
  * resident workgroups with S steps of start per segment.  cover[(ty * tiles_x + tx) * depth + z] is incremented once per
  * segment that sweeps the pair (the caller zeroes it): every entry must come out 1. */
 int lora_debug_span_cover(int tiles_x, int tiles_y, int depth, int S, int slots, int team, int *cover, int *workgroups, int *max_steps);
+/* Test support, no device needed: the layout the workgroup-row 2D kernel's launcher chooses for one launch of K = 6, 4 or 2
+ * applications over `rows` rows of a 2D plan's grid on cus x per_cu resident workgroups, under the plan's wg_rows and
+ * wg_edge_pct options.  out[0..7] = column strips, output columns per strip, rows per chunk and chunks per strip of the
+ * strips between the rim strips (chunks 0 where there are none), the same two of the rim strips, workgroups of the launch,
+ * rim strips (the first and the last strip; every strip where there are fewer than three). */
+int lora_debug_wg_layout(lora_plan *plan, int K, int rows, int cus, int per_cu, int *out);
 /* The same for the cut the launcher of the fp64 (kernel = 0) or bf16 (1) register-resident kernel itself chooses for a launch
  * of K = 2 or 4 applications over planes [begin, end) (and [begin2, end2), empty if end2 <= begin2) of h, on tiles_x x tiles_y
  * tiles and `slots` resident workgroups under plan options fused_z_chunk and spans3: cover[(ty * tiles_x + tx) * h + z] counts

@@ -254,6 +254,7 @@ SIGNATURES = {
     "lora_plan_stepn_region2": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "lora_debug_span_cover": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "lora_debug_cut_cover": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.POINTER(ctypes.c_int)] * 4),
+    "lora_debug_wg_layout": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)]),
     "lora_plan_run": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp]),
     "lora_plan_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridStats), _vp]),
     "lora_plan_diff": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(GridDiff), _vp]),

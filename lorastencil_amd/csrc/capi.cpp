@@ -398,6 +398,14 @@ int lora_debug_span_cover(int tiles_x, int tiles_y, int depth, int S, int slots,
     return ok ? LORA_OK : LORA_EHIP;  // (a segment out of range: a bug)
 }
 
+// Test support (no device): the strips and row chunks the workgroup-row 2D kernel's launcher chooses for K applications over
+// `rows` rows of the plan's grid (its wg_rows / wg_edge_pct options included) on cus x per_cu resident workgroups.
+int lora_debug_wg_layout(lora_plan *plan, int K, int rows, int cus, int per_cu, int *out) {
+    if (!plan || !out) return LORA_EINVAL;
+    if (plan->p.ndim != 2) return LORA_EUNSUPPORTED;
+    return lora::wg_layout_debug(plan->p, K, rows, cus, per_cu, out) ? LORA_OK : LORA_EINVAL;
+}
+
 // The cut the fp64 (kernel = 0) or bf16 (1) register-resident kernel's launcher chooses for K applications over planes
 // [begin, end) and [begin2, end2) of h, walked the same way; *kind = the layout (enum lora_cut_kind).
 int lora_debug_cut_cover(int kernel, int K, int tiles_x, int tiles_y, int h, int begin, int end, int begin2, int end2, int slots,

@@ -176,6 +176,7 @@ hipError_t launch_2d_wg(const Plan &p, int K, const double *in, double *out, int
 const char *kernel_name_2d_wg(const Plan &p);
 void prepare_2d_wg(const Plan &p);  // one-time host work of the plan's instantiations (no launch)
 int wg_strip_width(int K);
+bool wg_layout_debug(const Plan &p, int K, int rows, int cus, int per_cu, int out[8]);  // host only: the chunks of a launch
 hipError_t launch_3d(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);
 // two applications per launch, level 1 in LDS (fp64, reference boundary: level-1 halo = 0)
 hipError_t launch_3d_fused2(const Plan &p, const double *in, double *out, int begin, int end, hipStream_t s);

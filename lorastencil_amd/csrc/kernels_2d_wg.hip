@@ -17,7 +17,8 @@
 // This kernel keeps the scatter evaluation of rows_2d.h and the ring of LDS-DMA'd input rows, and changes the ownership:
 //   * A ROW belongs to the WORKGROUP: 512 input columns = one 16-byte piece per lane of four waves.  Every level shifts
 //     the lane -> column map by 3 (aligned 8-wide LDS windows, as before), but now once per workgroup: a strip yields
-//     512 - 6 K output columns (476 of 512 = 93 % at K = 6; 104 of 128 = 81 % before).  A lane's window reaches 6 columns
+//     512 - 6 (K - 1) output columns (482 of 512 = 94 % at K = 6; 104 of 128 = 81 % before): the ring holds the six
+//     positions behind the row too, so level 1 is complete on all 512 positions and only levels 2 .. K lose six each.  A lane's window reaches 6 columns
 //     into its right neighbour's piece -- also the next wave's -- so every level row goes through a workgroup-shared LDS
 //     row buffer, two copies per level (written in step r, read in step r + 1), and ONE s_barrier per step orders it all.
 //   * The K levels are split over S stages of KL levels: waves 4 s .. 4 s + 3 run levels s KL + 1 .. (s + 1) KL of the same
@@ -33,14 +34,15 @@
 //     level below is fetched between the profile phase of a level (after which its own window is dead) and its fourteen
 //     scatter multiply-adds, and waited for ahead of the level's ds_write: no more registers than before (116).
 //   * The launch is ONE round: strips x chunks = the workgroups that are resident at once (2 per CU), every chunk as
-//     long as that allows (16384^2: 35 strips x 14 chunks of 1171 rows, 7 K - 1 = 41 recomputed steps each = 3.5 %).
+//     long as that allows (16384^2: 32 strips x 15 chunks of 1093 rows + 2 rim strips x 16 of 1030 = 512 workgroups, 7 K - 1 = 41
+//     recomputed steps each = 3.8 %).
 //   * Halo semantics (as kernels_2d_stream.hip): cells of an intermediate level outside the interior are 0 at
 //     odd levels and the source buffer's own halo value at even levels.  Only workgroups at the rim of the grid can see
-//     such cells: they run a second copy of the step (EDGE) that forces them.  The halo values come straight from the
+//     such cells, and of those only the waves that hold such a column: they run a second copy of the step (EDGE) that forces them.  The halo values come straight from the
 //     input array -- while fused launches run, every buffer carries buffer 0's halo (capi.cpp) -- but NOT through a load
 //     the consuming wave waits for: vmcnt completes in order, so that wait would also drain the rows in flight (stage 0) or
 //     the store just issued (last stage), every step (measured: rim workgroups 2.3 x slower).  Instead stage 0 fetches
-//     them one step ahead, global -> LDS like the rows, into a row of halo values per even level (range-checked offsets:
+//     them one step ahead (right behind the barrier of the step before), global -> LDS like the rows, into a row of halo values per even level (range-checked offsets:
 //     lanes that need nothing make no memory request), where every stage picks them up behind the step's barrier.
 //     Under the Dirichlet option every level keeps the source's values: a row of halo values per level (K = 4 and 2).
 // Per accumulator the taps arrive in the same order as in the other fused 2D kernels: results are bit-identical to them.
@@ -61,9 +63,9 @@ struct ArgsWG {
     int ld, m, n;
     int row_begin, row_end;
     int strips;  // column strips of outw output columns
-    int outw;    // output columns per strip: 512 - 6 K
-    // Row chunks.  The first and the last strip ("rim strips": their lanes see columns outside the interior in every step)
-    // run the slower EDGE loop throughout and get shorter chunks, so that every workgroup of the one round takes about
+    int outw;    // output columns per strip: 512 - 6 (K - 1)
+    // Row chunks.  The first and the last strip ("rim strips": some of their lanes see columns outside the interior in every
+    // step) run the slower EDGE loop in the waves of those lanes and get shorter chunks, so that every workgroup of the one round takes about
     // the same time: rim strips have chunks_e chunks of rows_e rows, the others chunks_i of rows_i.
     int rim;  // number of rim strips in this launch: 2, or all of them when there are fewer than three
     int rows_i, groups_i, chunks_i;
@@ -78,14 +80,15 @@ struct ArgsWG {
 namespace {
 
 constexpr int kRowW = 512;  // doubles of a workgroup row: 4 waves x 64 lanes x 2 columns
-constexpr int kBufW = 520;  // doubles of a level row buffer: the last lanes' windows run 6 doubles past the row
+constexpr int kBufW = 520;  // doubles of a ring slot and of a level row buffer: the last lanes' windows run 6 doubles past the row
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// ring of input rows | two copies of a row per intermediate level | two copies of a row of halo values per even level
+// ring of input rows | two copies of a row per intermediate level | two copies of a row of halo values per even level | 8
+// spare doubles (where the stage-0 waves that do not hold the row's end drop their tail piece)
 // (DIRI: the Dirichlet option -- every intermediate level keeps the source's halo values, not only the even ones)
 __host__ __device__ constexpr int wg_halo_levels(int K, bool DIRI) { return DIRI ? K - 1 : K / 2 - 1; }
-__host__ __device__ constexpr int wg_lds_doubles(int K, int D, bool DIRI) { return (D + 1) * kRowW + (K - 1) * 2 * kBufW + wg_halo_levels(K, DIRI) * 2 * kRowW + 8; }
+__host__ __device__ constexpr int wg_lds_doubles(int K, int D, bool DIRI) { return (D + 1) * kBufW + (K - 1) * 2 * kBufW + wg_halo_levels(K, DIRI) * 2 * kRowW + 8; }
 
 // Step r of a chunk whose first output row is i0: stage 0 consumes input row i0 - 3 K + r; level l completes its row
 // i0 - 3 K - 4 l + 1 + r (a level lags 3 rows -- its radius -- plus one step of hand-off behind the level below).
@@ -97,7 +100,8 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
     static_assert(K % 2 == 0, "fused launches move an even number of levels");
     __shared__ __attribute__((aligned(128))) double lds[wg_lds_doubles(K, D, DIRI)];
     double *const ring = lds;
-    double *const rb = lds + NS * kRowW;  // rb + ((l - 1) * 2 + copy) * kBufW: row of level l
+    constexpr int RB = NS * kBufW;  // doubles of the ring: slots of kBufW, as wide as a level row
+    double *const rb = lds + RB;    // rb + ((l - 1) * 2 + copy) * kBufW: row of level l
 
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -133,16 +137,46 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
     const int j0 = strip * a.outw;              // first output column of the strip
     const int row_hi = min(i0 + rows, a.row_end);
     groups = min(groups, (row_hi - i0 + 7 * K - 1 + 6) / 7);  // the last chunk of a strip may be shorter
-    // Can this workgroup's lanes see a column outside the interior at some level?  (rim strips; uniform)
-    const bool col_edge = j0 - 3 * K < 0 || j0 + kRowW > a.n;
+    // Does one of THIS WAVE's 128 positions lie on a column outside the interior at some intermediate level?  (Level l
+    // puts position p on column j0 - 3 K + 3 l + p.)  Only waves of rim strips, and of those only the ones that hold the
+    // rim -- at 16384 columns wave 0 of the first strip and wave 3 of the last; the same for both stages.
+    const bool col_edge = j0 - 3 * K + 3 + 128 * wq < 0 || j0 - 3 + 128 * wq + 127 >= a.n;
 
     // input: interior columns j0 - 3 K + 2 t, +1 = padded columns j0 - 3 K + 4 + 2 t, clamped into the padded array
     // (clamped pieces only feed cells outside the interior, which the EDGE steps force)
     const int gcol = min(max(j0 - 3 * K + 4 + 2 * t, 0), a.n + 6);
+    // Positions 512 .. 517 of the row -- what the windows of the last three lanes reach past the workgroup's 512 columns, so
+    // that level 1 is complete on all 512 positions and only levels 2 .. K lose six columns each: three 16-byte pieces,
+    // clamped like gcol, fetched by lanes 0 .. 2 of wave 3 into the slot's tail.  Every stage-0 wave issues the piece
+    // (one instruction stream, the same vmcnt arithmetic for all four); the other three drop theirs into the eight spare
+    // doubles at the end of the LDS block, which nobody reads.  The lanes are chosen by EXEC, not by a range check: a
+    // lane that is switched off writes nothing to LDS, where a lane whose address is out of range may write a zero -- into
+    // the next slot, here.  (One asm statement: M0 is the compiler's, and a branch in the step is what this kernel avoids.)
+    const unsigned xoff = 8u * (unsigned) min(max(j0 - 3 * K + 4 + kRowW + 2 * lane, 0), a.n + 6);
+    const unsigned lds_base = (unsigned) (size_t) (__attribute__((address_space(3))) void *) lds;  // the block's LDS address
     auto issue = [&](int r) {
         const int pr = min(max(i0 - 3 * K + 4 + r, 0), a.m + 7);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (a.in + (size_t) pr * a.ld + gcol),
-                                         (__attribute__((address_space(3))) void *) (ring + (r & (NS - 1)) * kRowW + wq * 128), 16, 0, 0);
+        const double *const grow = a.in + (size_t) pr * a.ld;
+        double *const slot = ring + (r & (NS - 1)) * kBufW;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const unsigned tail = lds_base + 8u * (unsigned) (wq == 3 ? (r & (NS - 1)) * kBufW + kRowW : wg_lds_doubles(K, D, DIRI) - 8);
+        unsigned long long keep_exec;
+        unsigned keep_m0;
+        asm volatile(
+            "s_mov_b64 %0, exec\n\t"
+            "s_mov_b32 %1, m0\n\t"
+            "s_mov_b64 exec, 7\n\t"
+            "s_mov_b32 m0, %4\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dwordx4 %2, %3\n\t"
+            "s_mov_b32 m0, %1\n\t"
+            "s_mov_b64 exec, %0"
+            : "=&s"(keep_exec), "=&s"(keep_m0)
+            : "v"(xoff), "s"(grow), "s"(tail)
+            : "memory");
+#endif
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (grow + gcol),
+                                         (__attribute__((address_space(3))) void *) (slot + wq * 128), 16, 0, 0);
     };
     // stores: lanes t < outw / 2 write interior columns j0 + 2 t, +1; the descriptor's range check drops the rest
     const unsigned store_off = t < a.outw / 2 ? 16u * t : 0x80000000u;
@@ -158,9 +192,10 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
     // One copy of the 7-step group per (stage, EDGE): inside it the level numbers, the LDS addresses and the roles (who
     // loads, who stores) are compile-time constants and the instruction stream has NO branches -- with branches in it the
     // compiler sinks the partial-sum updates of a row towards their use, 7 steps later, and keeps every window alive
-    // meanwhile (256 VGPRs and scratch instead of 128).  EDGE is chosen per group and wave: rim strips always, the other
-    // strips only in the few groups whose level rows lie outside the interior (first / last chunk); both copies have
-    // one barrier per step, so waves of one workgroup may run different copies.
+    // meanwhile (256 VGPRs and scratch instead of 128).  EDGE is chosen per group and wave: always in the waves that hold a
+    // column outside the interior (col_edge: one wave per stage of a rim strip on wide grids), in all others only in the
+    // few groups whose level rows lie outside the interior (first / last chunk); both copies have one barrier per step,
+    // so waves of one workgroup run different copies side by side.
     auto run_stage = [&](auto stage_tag) {
         constexpr int STAGE = decltype(stage_tag)::value;
         constexpr bool FIRST = STAGE == 0;
@@ -210,28 +245,52 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
                 }
             }
         };
-        double *const hb = lds + NS * kRowW + (K - 1) * 2 * kBufW;  // hb + (e * 2 + copy) * kRowW: halo values of level 2 e + 2
+        double *const hb = lds + RB + (K - 1) * 2 * kBufW;  // hb + (e * 2 + copy) * kRowW: halo values of level 2 e + 2
 
         auto step = [&](const int r, auto phase_tag, auto edge_tag) {
             constexpr int P = decltype(phase_tag)::value;  // r mod 7: logical row 0 (the one completed now) is acc[P]
             constexpr bool EDGE = decltype(edge_tag)::value;
             const int par = r & 1;
-            // "input row r has landed": the D - 1 younger row loads may be outstanding (S > 1: stage 0 has no stores in its
-            // vmcnt; S == 1: as in kernels_2d_stream.hip, the interleaved stores only make the wait stricter).  EDGE: this
-            // step's halo values were issued in the previous step, BEFORE its row load: one younger load.
-            if (FIRST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EDGE && NH > 0 ? 1 : D - 1) : "memory");
+            // "input row r has landed": the D - 1 younger rows, two loads each (the row piece and the tail piece), may be
+            // outstanding (S > 1: stage 0 has no stores in its vmcnt; S == 1: as in kernels_2d_stream.hip, the interleaved
+            // stores only make the wait stricter).  EDGE: this step's halo values were issued in the previous step, BEFORE
+            // its row: one younger row.
+            if (FIRST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EDGE && NH > 0 ? 2 : 2 * (D - 1)) : "memory");
             // one barrier per step: behind it every wave's piece of input row r (and of this step's halo values) and every
             // level row of step r - 1 is visible, and nobody still reads what this step overwrites (ring slot of row r - 1,
             // row copies of step r - 2, halo values of step r - 1)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
+            if (FIRST && EDGE) {
+                // Halo values of step r + 1, every level that keeps any: this wave's 128 columns of them, into the copy that
+                // step r does not read (step r - 1 did, and every wave is past it).  Issued right behind the barrier they
+                // have the whole step to arrive; in vmcnt they stand in front of this step's row.
+#pragma unroll
+                for (int e = 0; e < NH; ++e) {
+                    const int row1 = i0 - 3 * K - 4 * (DIRI ? e + 1 : 2 * e + 2) + 1 + (r + 1);
+                    const int pr = min(max(row1 + 4, 0), a.m + 7);
+                    const __amdgpu_buffer_rsrc_t hsrc = __builtin_amdgcn_make_buffer_rsrc(
+                        const_cast<double *>(a.in) + (size_t) pr * a.ld, 0, (unsigned) a.ld * 8u, 0x00020000);
+#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass does not know this builtin and then drops the kernel's stub without a word)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                        hsrc, (__attribute__((address_space(3))) void *) (hb + (e * 2 + (par ^ 1)) * kRowW + wq * 128), 16,
+                        (unsigned) row1 < (unsigned) a.m ? hcol[e] : hall[e], 0, 0, 0);
+#else
+                    (void) hsrc;
+                    (void) hb;
+#endif
+                }
+                // (the compiler does not know that these overwrite LDS: nothing of the step may rise above them)
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+            }
             const int cur = par * kBufW, prev = kBufW - cur;  // this step's / the previous step's copy of a level row
             // the window of this wave's level number jj (global level LB + jj + 1): the pair the lane holds + three pieces, or
             // four pieces of another wave's row / of the ring
             auto window = [&](const int jj, double (&w)[8]) {
                 const int lw = LB + jj + 1;
-                const double *const src = lw == 1 ? winp + (r & (NS - 1)) * kRowW : winp + NS * kRowW + (lw - 2) * 2 * kBufW + prev;
+                const double *const src = lw == 1 ? winp + (r & (NS - 1)) * kBufW : winp + RB + (lw - 2) * 2 * kBufW + prev;
                 const bool own_pair = jj >= 1;  // the level below is this wave's: its pair is in `own`
                 if (own_pair) {
                     w[0] = own[jj >= 1 ? jj - 1 : 0].x;
@@ -258,7 +317,7 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
                 // EDGE: what this lane's cells are forced to when they lie outside the interior
                 d2 h = {0.0, 0.0};
                 if (EDGE && !to_global && ((l & 1) == 0 || DIRI))
-                    h = *reinterpret_cast<const d2 *>(winp + NS * kRowW + (K - 1) * 2 * kBufW + ((DIRI ? l - 1 : l / 2 - 1) * 2 + par) * kRowW);
+                    h = *reinterpret_cast<const d2 *>(winp + RB + (K - 1) * 2 * kBufW + ((DIRI ? l - 1 : l / 2 - 1) * 2 + par) * kRowW);
                 // the newest logical row (6) starts from zero: stated here, so that the zero is an inline constant of its
                 // first multiply-add and not a register carried around the loop
                 pa[j][(P + 6) % 7] = 0.0;
@@ -304,7 +363,7 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
                         o.w = (vb.w & m1) | (hb4.w & ~m1);
                         v = __builtin_bit_cast(d2, o);
                     }
-                    *reinterpret_cast<d2 *>(const_cast<double *>(winp) + NS * kRowW + (l - 1) * 2 * kBufW + cur) = v;
+                    *reinterpret_cast<d2 *>(const_cast<double *>(winp) + RB + (l - 1) * 2 * kBufW + cur) = v;
                     // what level l + 1 of this wave reads in the next step (it ran before this level in this step, on the
                     // pair of the step before)
                     if (j < KL - 1) own[j < KL - 1 ? j : 0] = v;
@@ -312,28 +371,9 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
                 __builtin_amdgcn_sched_barrier(0);
             }
             // The compiler does not know that the LDS-DMAs below overwrite LDS; nothing of this step may sink below them
+            // (row r + D goes where row r - 1 was: every wave finished with that one before this step's barrier)
             asm volatile("" ::: "memory");
-            if (FIRST) {
-                if (EDGE) {
-                    // halo values of step r + 1, every even level: this wave's 128 columns of them
-#pragma unroll
-                    for (int e = 0; e < NH; ++e) {
-                        const int row1 = i0 - 3 * K - 4 * (DIRI ? e + 1 : 2 * e + 2) + 1 + (r + 1);
-                        const int pr = min(max(row1 + 4, 0), a.m + 7);
-                        const __amdgpu_buffer_rsrc_t hsrc = __builtin_amdgcn_make_buffer_rsrc(
-                            const_cast<double *>(a.in) + (size_t) pr * a.ld, 0, (unsigned) a.ld * 8u, 0x00020000);
-#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass does not know this builtin and then drops the kernel's stub without a word)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                            hsrc, (__attribute__((address_space(3))) void *) (hb + (e * 2 + (par ^ 1)) * kRowW + wq * 128), 16,
-                            (unsigned) row1 < (unsigned) a.m ? hcol[e] : hall[e], 0, 0, 0);
-#else
-                        (void) hsrc;
-                        (void) hb;
-#endif
-                    }
-                }
-                issue(r + D);
-            }
+            if (FIRST) issue(r + D);
             __builtin_amdgcn_sched_barrier(0);
         };
         auto group = [&](const int r0, auto edge_tag) {
@@ -347,9 +387,10 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
         };
 
         // Rows the workgroup's intermediate levels complete in group g: [lo0 + 7 g, hi0 + 7 g].  Groups [0, g1) and
-        // [g2, groups) have rows outside the interior (first / last chunk only); rim strips run EDGE throughout.  The second
+        // [g2, groups) have rows outside the interior (first / last chunk only); waves with col_edge run EDGE throughout.  The second
         // EDGE range starts one group early: its first step finds no halo values fetched for it, and needs none there.
-        // The ranges are the same for every wave of the workgroup (stage 0 fetches for all).  Three plain loops: a branch
+        // The ranges are the same for the waves of both stages that share a quarter of the row (wq): the stage-0 wave
+        // fetches the halo values of its own 128 columns, for itself and for its partner above.  Three plain loops: a branch
         // inside one loop brings the register blow-up described above back.
         const int lo0 = i0 - 3 * K - 4 * (K - 1) + 1, hi0 = i0 - 3 * K - 4 + 1 + 6;
         int g1 = lo0 >= 0 ? 0 : (-lo0 + 6) / 7, g2 = hi0 >= a.m ? 0 : (a.m - hi0 + 6) / 7 - 1;
@@ -420,6 +461,76 @@ __global__ __launch_bounds__(256 * S, WPS) void stencil2d_wg_kernel(const ArgsWG
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// How much later a rim-strip workgroup finishes than any other with the same number of steps, in per cent (plan option
+// wg_edge_pct; -1 = this).  One wave per stage of such a workgroup runs the EDGE copy of the step, the others the interior
+// copy.  Six applications: a step's median cost is 1.14 - 1.19 x, the slowest workgroups of both classes are 1.05 - 1.16 x apart
+// (tools/wg_rim_ratio.py, profiles/r06_wg_rim_ratio.jsonl); up to 13 the 16384-column grid gets the layout that fills all 512
+// slots, which is the faster one there (bench.py, builds alternating: profiles/r06_wg_strips_ab.jsonl).  Four and two: those
+// launches wait for HBM, an interior step is shorter and the rim's extra work weighs more -- 16384^2, four applications, us
+// per launch at 12 / 60: 920 / 867 (profiles/r06_wg_tails.jsonl).
+constexpr int wg_edge_pct_default(int K) { return K >= 6 ? 12 : 60; }
+
+// The row chunks of one launch of K applications over rows_total rows and `strips` column strips, on `slots` resident
+// workgroups.  Rim strips (the first and the last; all of them below three) have chunks_e chunks of rows_e rows, the others
+// chunks_i of rows_i.
+struct WgLayout {
+    int rim, rows_i, chunks_i, rows_e, chunks_e;
+    long workgroups;
+};
+
+inline WgLayout wg_layout(int K, int strips, int rows_total, long slots, int edge_pct, int wg_rows) {
+    const int lag = 7 * K - 1;  // steps of a chunk beyond its output rows
+    auto fit = [&](long rows) {
+        long g = (rows + lag + 6) / 7;
+        if (g < K + 1) g = K + 1;
+        return (int) (7 * g - lag);
+    };
+    auto chunks = [&](int rows) { return (rows_total + rows - 1) / rows; };
+    WgLayout L{};
+    L.rim = strips >= 3 ? 2 : strips;
+    const int ni = strips - L.rim;
+    const long ratio = 100 + (edge_pct >= 0 ? edge_pct : wg_edge_pct_default(K));
+    // the most rows whose rim chunk finishes with an interior chunk of ri rows
+    auto rim_target = [&](int ri) { return std::max(1L, (long) (ri + lag) * 100 / ratio - lag); };
+    if (wg_rows > 0) {
+        L.rows_i = fit(wg_rows);
+        L.rows_e = ni > 0 ? fit(rim_target(L.rows_i)) : L.rows_i;
+    } else {
+        // ONE round: every workgroup of the launch resident at once.  Candidates: c interior chunks, and for the rim
+        // strips the fewest chunks that finish with those -- or as many as the slots the interior chunks leave allow --
+        // split evenly.  Score: the predicted finish, max(interior steps, ratio x rim steps); the first minimum wins.
+        // Small grids: filling the round matters more than the rows a chunk recomputes -- down to chunks of about 1.5 x
+        // the 7 K - 1 warm-up rows (star2d1r, six sweeps, GStencils/s at chunks of 64 / 100 / 128 / 164 / 256 rows: 4096^2
+        // 636 / 837 / 762 / 675 / 595, 2048^2 375 / 289 / 245 / 208 / 149, 1024 x 16384 685 / 875 / 775 / 816 / 595 --
+        // tools/wg_small.py; the first rule, four times the warm-up, left half the CUs idle on such grids)
+        const long min_rows = 3 * lag / 2;
+        long best = -1;
+        for (long c = 1; c <= rows_total; ++c) {
+            const int ri = fit((rows_total + c - 1) / c);
+            if (ri < min_rows && c > 1) break;
+            int re = ri;
+            if (ni > 0) {
+                const long ce_max = (slots - (long) ni * chunks(ri)) / L.rim;
+                if (ce_max < 1 && c > 1) break;
+                const long want = (rows_total + rim_target(ri) - 1) / rim_target(ri);
+                const long ce = std::max(1L, std::min(want, ce_max));
+                re = fit((rows_total + ce - 1) / ce);
+            }
+            if ((long) ni * chunks(ri) + (long) L.rim * chunks(re) > slots && c > 1) break;
+            const long score = std::max(100L * (ri + lag), ratio * (re + lag));
+            if (best < 0 || score < best) {
+                best = score;
+                L.rows_i = ri;
+                L.rows_e = re;
+            }
+        }
+    }
+    L.chunks_i = chunks(L.rows_i);
+    L.chunks_e = chunks(L.rows_e);
+    L.workgroups = (long) ni * L.chunks_i + (long) L.rim * L.chunks_e;
+    return L;
+}
+
 // Workgroups of this instantiation that are resident per CU (cached per device).  The first query of an instantiation
 // also makes the runtime load and resolve the kernel -- half a millisecond of host time that lora_plan_create /
 // lora_plan_set_* pay through prepare_2d_wg(), not the first launch of a run.
@@ -451,45 +562,15 @@ hipError_t launch_wg_t(const Plan &p, ArgsWG a, int rows_total, hipStream_t s) {
     // one round: as many workgroups as are resident at once
     const int per_cu_dev = wg_per_cu<EVAL, KL, S, D, WPS, DIRI>(dev);
     if (rows_total <= 0) return hipSuccess;  // prepare_2d_wg(): the query above is all that was wanted
-    const int lag = 7 * K - 1;  // steps of a chunk beyond its output rows
-    auto fit = [&](long rows) {
-        long g = (rows + lag + 6) / 7;
-        if (g < K + 1) g = K + 1;
-        return (int) (7 * g - lag);
-    };
-    a.rim = a.strips >= 3 ? 2 : a.strips;
+    const WgLayout lay = wg_layout(K, a.strips, rows_total, (long) per_cu_dev * cus, p.wg_edge_pct, p.wg_rows);
+    a.rim = lay.rim;
     const int ni = a.strips - a.rim;
-    // A rim-strip workgroup runs the EDGE steps throughout (selects, halo-value fetches, one row less in flight) and takes
-    // about half as long again per step: its chunks are that much shorter (16384^2, us per launch at 12 / 25 / 35 / 45 /
-    // 55 / 70 per cent: 1393 / 1391 / 1237 / 1189 / 1172 / 1164; gpurun_out/wg_sweep.log)
-    const int pct = p.wg_edge_pct >= 0 ? p.wg_edge_pct : 60;
-    auto rim_rows = [&](int rows_i) { return fit(std::max(1L, (long) (rows_i + lag) * 100 / (100 + pct) - lag)); };
-    if (p.wg_rows > 0) {
-        a.rows_i = fit(p.wg_rows);
-    } else {
-        // ONE round: the most interior chunks for which every workgroup of the launch is resident at once
-        const long slots = (long) per_cu_dev * cus;
-        // Small grids: filling the round matters more than the rows a chunk recomputes -- down to chunks of about 1.5 x
-        // the 7 K - 1 warm-up rows (star2d1r, six sweeps, GStencils/s at chunks of 64 / 100 / 128 / 164 / 256 rows: 4096^2
-        // 636 / 837 / 762 / 675 / 595, 2048^2 375 / 289 / 245 / 208 / 149, 1024 x 16384 685 / 875 / 775 / 816 / 595 --
-        // tools/wg_small.py; the first rule, four times the warm-up, left half the CUs idle on such grids)
-        const long min_rows = 3 * lag / 2;
-        int best = fit(rows_total);
-        for (long c = 1; c <= rows_total; ++c) {
-            const int ri = fit((rows_total + c - 1) / c);
-            if (ri < min_rows && c > 1) break;
-            const int re = ni > 0 ? rim_rows(ri) : ri;
-            const long wgs = (long) ni * ((rows_total + ri - 1) / ri) + (long) a.rim * ((rows_total + re - 1) / re);
-            if (wgs > slots && c > 1) break;
-            best = ri;
-        }
-        a.rows_i = best;
-    }
-    a.rows_e = ni > 0 ? rim_rows(a.rows_i) : a.rows_i;
-    a.groups_i = (a.rows_i + lag + 6) / 7;
-    a.groups_e = (a.rows_e + lag + 6) / 7;
-    a.chunks_i = (rows_total + a.rows_i - 1) / a.rows_i;
-    a.chunks_e = (rows_total + a.rows_e - 1) / a.rows_e;
+    a.rows_i = lay.rows_i;
+    a.rows_e = lay.rows_e;
+    a.groups_i = (a.rows_i + 7 * K - 1 + 6) / 7;
+    a.groups_e = (a.rows_e + 7 * K - 1 + 6) / 7;
+    a.chunks_i = lay.chunks_i;
+    a.chunks_e = lay.chunks_e;
     a.prio_split = (p.wg_prio != 0 && per_cu_dev == 2) ? cus : 0;
     a.prio_shift = p.wg_prio > 0 ? p.wg_prio : 12;
     Taps49 w;
@@ -580,7 +661,20 @@ void prepare_2d_wg(const Plan &p) {
 #endif
 }
 
-int wg_strip_width(int K) { return kRowW - 6 * K; }
+// Level 1 is complete on all 512 positions of a row (the ring holds the six positions behind them); levels 2 .. K lose six each
+int wg_strip_width(int K) { return kRowW - 6 * (K - 1); }
+
+// The layout of a launch of K applications over `rows` rows of the plan's grid on cus x per_cu resident workgroups, for
+// lora_debug_wg_layout (no device): out = strips, outw, rows_i, chunks_i, rows_e, chunks_e, workgroups, rim strips
+bool wg_layout_debug(const Plan &p, int K, int rows, int cus, int per_cu, int out[8]) {
+    if ((K != 6 && K != 4 && K != 2) || rows < 1 || cus < 1 || per_cu < 1 || p.ndim != 2) return false;
+    const int outw = wg_strip_width(K), strips = (p.dims[1] + outw - 1) / outw;
+    const WgLayout L = wg_layout(K, strips, rows, (long) cus * per_cu, p.wg_edge_pct, p.wg_rows);
+    if (L.workgroups > 0x7fffffffL) return false;
+    const int v[8] = {strips, outw, L.rows_i, strips > L.rim ? L.chunks_i : 0, L.rows_e, L.chunks_e, (int) L.workgroups, L.rim};
+    std::copy(v, v + 8, out);
+    return true;
+}
 
 #ifdef LORA_DIAGNOSTICS
 long long *g_wg_stamps = nullptr;  // set by the probe: 4 x int64 per workgroup

@@ -26,7 +26,7 @@ static lora::ArgsWG args(const lora::Plan &p, int K, const double *in, double *o
     a.ld = a.n + 8;
     a.row_begin = 0;
     a.row_end = a.m;
-    a.outw = 512 - 6 * K;
+    a.outw = 512 - 6 * (K - 1);  // (wg_strip_width: level 1 is complete on all 512 positions)
     a.strips = (a.n + a.outw - 1) / a.outw;
     return a;
 }

@@ -62,6 +62,13 @@ int main(int argc, char **argv) {
     for (int b = 0; b < maxwg; ++b)
         if (s[4 * b] && (t0 < 0 || s[4 * b] < t0)) t0 = s[4 * b];
     printf("# launch %.1f us; columns: block,start_us,end_us,se,cu,xcc,strip,chunk\n", ms * 1e3);
+    {  // the chunks of that launch (two workgroups per CU): tools/wg_rim_ratio.py divides a workgroup's time by its steps
+        int cus = 256, lay[8] = {0};
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0);
+        if (lora::wg_layout_debug(p, 6, m, cus, 2, lay))
+            printf("# layout strips %d outw %d rows_i %d chunks_i %d rows_e %d chunks_e %d workgroups %d rim %d\n", lay[0], lay[1], lay[2],
+                   lay[3], lay[4], lay[5], lay[6], lay[7]);
+    }
     for (int b = 0; b < maxwg; ++b) {
         if (!s[4 * b]) continue;
         const unsigned hw = (unsigned) s[4 * b + 2], xcc = (unsigned) (s[4 * b + 2] >> 32) & 15;
