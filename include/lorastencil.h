@@ -296,6 +296,9 @@ int lora_set_default_normalize(int on);
 /* Option "leap3" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_leapfrog and
  * lora_run_host_chebyshev (what lorastencil_3d's --leap3 flag sets).  Returns the previous value. */
 int lora_set_default_leap3(int on);
+/* Option "wave3" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_wave (what
+ * lorastencil_3d's --wave3 flag sets).  Returns the previous value. */
+int lora_set_default_wave3(int on);
 /* Option "coarse1" (below) of the plans created afterwards on this thread, i.e. also of lora_run_host_mg, lora_run_host_pcg and
  * lora_run_host_theta_mg (what the CLIs' --coarse1 flag sets); never of the internal plans of a multigrid hierarchy.  Returns
  * the previous value. */
@@ -322,6 +325,12 @@ int lora_set_default_mgfuse(int on);
  *                     effect on other plans, and none on the kernel name, signature or depth of the plain sweeps.  Same
  *                     bits either way.  Measured: a launch takes 0.72 - 0.89 of the time
  *                     of two single steps, a run of 120 steps 0.79 - 0.95; off until the default is decided on those figures
+ *   wave3             0 (default) / 1 : 3D fp64 plans with an even innermost extent and no source get the two-step wave launch
+ *                     (kernels_3d_step2.hip; lora_plan_wave_depth reads 2, the lora_plan_step2_wave* entries work, wave runs
+ *                     take pairs of launches).  Any non-zero value reads back as 1; independent of "leap3"; no effect on other
+ *                     plans, and none on the kernel name, signature, leapfrog depth or depth of the plain sweeps.  Same bits
+ *                     either way.  Measured: a launch takes 0.78 - 0.83 of the time of two single steps, a run of 120 steps
+ *                     0.76 - 0.86; off until the default is decided on those figures
  *   coarse1           0 (default) / 1 : the multigrid cycles this plan drives (lora_plan_run_mg_until, lora_plan_mg_precondition,
  *                     lora_plan_run_pcg_until, lora_plan_run_theta_mg) run their coarsest level as ONE launch,
  *                     lora_plan_cg_small, when that level's plan reads "cg_small" = 1; otherwise nothing changes.  The level's
@@ -598,9 +607,9 @@ int lora_chebyshev_coeffs(double rho, int first_step, int count, double *a, doub
  * two-step entry on a plan of wave depth below 2; LORA_ENODEVICE when the launch fails for want of a device.  All entries are
  * asynchronous on `stream`. */
 /* 0: the plan has no wave kernel (LORA_BF16 plans, 2D plans of LORA_VARIANT_MFMA, plans that currently carry a source);
- * 2: also the two-step launch (2D plans of the direct variant with an even innermost extent); 1: single steps (every other
- * plan; a 3D plan reads 1 with or without option "leap3": there is no two-step wave launch in 3D).  A function of the plan
- * alone; needs no device. */
+ * 2: also the two-step launch (2D plans of the direct variant with an even innermost extent; 3D plans with an even innermost
+ * extent on which option "wave3" is 1); 1: single steps (every other plan; without "wave3" a 3D plan reads 1 with or without
+ * option "leap3", which moves the leapfrog depth alone).  A function of the plan alone; needs no device. */
 int lora_plan_wave_depth(const lora_plan *plan);
 /* One step, in place: on every interior cell of the swept range
  *     d_prev = fl( fl( fl(k * acc) + fl(b * u) ) + fl(c * d_prev) )
@@ -618,7 +627,10 @@ int lora_plan_step_wave_region(lora_plan *plan, const void *d_cur, void *d_prev,
  * levels; the five buffers are pairwise distinct.  Level-1 cells outside the interior take the value d_prev holds there; direct
  * taps in row-major order at both levels whatever option "lowrank_valu" says: a launch equals two single steps bit for bit on
  * any data.  Halo cells of d_out1 / d_out2 are never written, d_prev, d_cur and d_k never at all; d_k is read on interior
- * cells alone, at both levels. */
+ * cells alone, at both levels.
+ *   3D (option "wave3"): the same contract with [begin, end) counting planes, the geometry and the boundary rule of the 3D
+ * lora_plan_step2_leapfrog (level 1 is computed, not stored, on planes begin - 1 and end), the tap chain of the plan's single
+ * step.  A padded plane of 2^28 cells or more is refused by the launch (LORA_EHIP), as there. */
 int lora_plan_step2_wave(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_k, void *d_out1, void *d_out2, double b,
                          double c, void *stream);
 int lora_plan_step2_wave_region(lora_plan *plan, const void *d_prev, const void *d_cur, const void *d_k, void *d_out1, void *d_out2,
@@ -627,8 +639,8 @@ int lora_plan_step2_wave_region(lora_plan *plan, const void *d_prev, const void 
  * lora_plan_run_leapfrog's with the wave depth in place of the leapfrog depth: on plans of wave depth 2, times / 4 pairs of
  * two-step launches through the plan's two scratch grids (the same two; lora_plan_prepare_wave allocates them; d_k must differ
  * from them as from d_prev and d_cur, else the run takes single steps), times % 4 single steps at the end; single steps only
- * under LORA_BC_PERIODIC (d_k is never wrapped: its halo is never read), with option "scratch" = 0, and on every 3D plan
- * whatever option "leap3" says.  Direct launches.  Whatever the schedule, the result is bit for bit that of `times` single
+ * under LORA_BC_PERIODIC (d_k is never wrapped: its halo is never read), with option "scratch" = 0, and on every plan of wave
+ * depth 1: a 3D plan without option "wave3", whatever option "leap3" says.  Direct launches.  Whatever the schedule, the result is bit for bit that of `times` single
  * steps. */
 int lora_plan_run_wave(lora_plan *plan, void *d_prev, void *d_cur, const void *d_k, double b, double c, int times, void *stream);
 /* Allocates now what lora_plan_run_wave(plan, ..., times, ...) would allocate on first need.  Optional and idempotent. */

@@ -56,6 +56,7 @@ from .ops import (  # noqa: F401
     set_default_coarse1,
     set_default_mgfuse,
     set_default_leap3,
+    set_default_wave3,
     set_default_source,
     stats_merge,
     svd_7x7,

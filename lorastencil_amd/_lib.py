@@ -197,6 +197,7 @@ SIGNATURES = {
     "lora_set_default_boundary": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_normalize": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_leap3": (ctypes.c_int, [ctypes.c_int]),
+    "lora_set_default_wave3": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_coarse1": (ctypes.c_int, [ctypes.c_int]),
     "lora_set_default_mgfuse": (ctypes.c_int, [ctypes.c_int]),
     "lora_plan_set_source": (ctypes.c_int, [_vp, _vp]),

@@ -26,6 +26,8 @@
 //   --wave=K0[,K1]     time_size steps of the wave equation in a heterogeneous medium, u(t+1) = 2 u(t) - u(t-1) + kappa(x) L u(t)
 //                      from u(-1) = u(0), L the zero-sum form of the taps (lora_run_host_wave with b = 2, c = -1, laplacian = 1);
 //                      kappa = K0 on the first half of the outermost dimension and K1 (default K0) on the rest; one GPU, fp64
+//   --wave3            (lorastencil_3d only, with --wave) the run takes two wave steps per launch (lora_set_default_wave3; plan
+//                      option wave3); same results, same output
 //   --chebyshev=RHO    solve u = S(u) + f by the Chebyshev semi-iteration for a spectrum of S inside [-RHO, RHO], 0 <= RHO < 1
 //                      (lora_run_host_chebyshev): time_size steps, or with --until=TOL until the true residual
 //                      max |S(u) + f - u| <= TOL (time_size is the cap); f from --source= when given; one GPU, fp64
@@ -175,7 +177,7 @@ int main(int argc, char *argv[]) {
     double wave_k[2] = {0.0, 0.0};
     bool chebyshev = false;
     double chebyshev_rho = 0.0;
-    bool leap3 = false, coarse1 = false, mgfuse = false;
+    bool leap3 = false, wave3 = false, coarse1 = false, mgfuse = false;
     bool cg = false;
     bool mg = false, check_every_given = false, pcg = false, precond = false;
     int pcg_smooth = 2, precond_smooth = 2;
@@ -256,6 +258,8 @@ int main(int argc, char *argv[]) {
         }
         else if (a == "--leap3" && kDim == 3)
             leap3 = true;
+        else if (a == "--wave3" && kDim == 3)
+            wave3 = true;
         else if (a == "--coarse1" && kDim >= 2)
             coarse1 = true;
         else if (a == "--mgfuse" && kDim >= 2)
@@ -461,6 +465,11 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     if (leap3) lora_set_default_leap3(1);
+    if (wave3 && !wave) {
+        std::cerr << "--wave3 chooses the launches of a wave run: only with --wave\n";
+        return 1;
+    }
+    if (wave3) lora_set_default_wave3(1);
     if (coarse1 && !mg && !pcg && !precond) {
         std::cerr << "--coarse1 chooses the launches of a multigrid cycle's coarsest level: only with --mg, --pcg or --precond=mg\n";
         return 1;

@@ -111,6 +111,7 @@ struct Plan : Resolved {
     int lanes3 = -1;          // 3D fused launches through the register-resident kernels (kernels_3d_lanes.hip, fp64; kernels_3d_bf16_lanes.hip, bf16: four applications per launch): -1 by grid size, 0 never, 1 always (star / separable box taps, reference boundary)
     int fused_z_chunk = 0;    // 3D fused: output planes per workgroup (0 = auto: 32, shorter on small grids)
     int leap3 = 0;            // 3D fp64: leapfrog runs take the two-step launch (kernels_3d_step2.hip); no effect outside 3D
+    int wave3 = 0;            // 3D fp64: wave runs take the two-step launch (kernels_3d_step2.hip, EPI_WAVE); no effect outside 3D
     int coarse1 = 0;          // multigrid cycles of this plan run a coarsest level that fits as ONE launch (lora_plan_cg_small; mg.cpp)
     int mgfuse = 0;           // multigrid cycles of this plan restrict a level's defect in the launch that computes it (lora_plan_mg_defect_restrict; mg.cpp)
     int spans3 = -1;          // 3D register-resident kernels: cut the (tile, plane) line into equal pieces per CU (1), equal chunks per tile (0), by region depth (-1)
@@ -425,16 +426,25 @@ inline hipError_t launch_leapfrog2_src(const Plan &p, const double *prev, const 
 }
 
 // ---- variable-coefficient wave steps, prev <- k S(cur) + b cur + c prev with k a padded grid (kernels_step.hip: one step;
-// kernels_2d_wave2.hip: two per launch in 2D; 3D has single steps only, whatever option leap3 says).  k is a call argument.
-// Picked by the *_wave entries of leapfrog.cpp and by nothing else.
+// kernels_2d_wave2.hip: two per launch in 2D; kernels_3d_step2.hip: two per launch in 3D behind option wave3 -- option leap3
+// alone leaves 3D wave runs at single steps).  k is a call argument.  Picked by the *_wave entries of leapfrog.cpp and by
+// nothing else.
 hipError_t launch_wave(const Plan &p, const double *cur, double *prev, const double *k, double b, double c, int begin, int end,
                        hipStream_t s);
 hipError_t launch_wave2_2d(const Plan &p, const double *prev, const double *cur, const double *k, double *out1, double *out2, double b,
                            double c, int begin, int end, hipStream_t s);
-// 0: no wave kernel (the plans of leapfrog depth 0); 2: also the two-step launch (2D: direct variant, even innermost extent);
-// 1: single steps (every other plan, every 3D plan among them).
+hipError_t launch_wave2_3d(const Plan &p, const double *prev, const double *cur, const double *k, double *out1, double *out2, double b,
+                           double c, int begin, int end, hipStream_t s);
+inline hipError_t launch_wave2(const Plan &p, const double *prev, const double *cur, const double *k, double *out1, double *out2, double b,
+                               double c, int begin, int end, hipStream_t s) {
+    return p.ndim == 3 ? launch_wave2_3d(p, prev, cur, k, out1, out2, b, c, begin, end, s)
+                       : launch_wave2_2d(p, prev, cur, k, out1, out2, b, c, begin, end, s);
+}
+// 0: no wave kernel (the plans of leapfrog depth 0); 2: also the two-step launch (2D: direct variant, even innermost extent;
+// 3D: even innermost extent and option wave3 on); 1: single steps (every other plan).
 inline int wave_depth(const Plan &p) {
     if (leapfrog_depth(p) == 0) return 0;
+    if (p.ndim == 3) return p.wave3 && !p.generic ? 2 : 1;
     return p.ndim == 2 && !p.generic ? 2 : 1;
 }
 

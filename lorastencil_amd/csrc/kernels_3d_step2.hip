@@ -1,8 +1,10 @@
-// kernels_3d_step2.hip -- TWO leapfrog steps per launch, 3D fp64 (plan option leap3): ONE kernel body,
-// stencil3d_step2_kernel<TAPSET, EPI>, whose rule EPI (step_epilogue.h) is a template parameter:
+// kernels_3d_step2.hip -- TWO leapfrog or wave steps per launch, 3D fp64 (plan options leap3, wave3): ONE
+// kernel body, stencil3d_step2_kernel<TAPSET, EPI>, whose rule EPI (step_epilogue.h) is a template parameter:
 //     EPI_LEAP          out1 = S(cur) + c prev,            out2 = S(out1) + c cur            launch_leapfrog2
 //     EPI_LEAP_SCALED   out1 = a1 S(cur) + c1 prev,        out2 = a2 S(out1) + c2 cur        launch_leapfrog2_src, f == nullptr
 //     EPI_LEAP_SRC      out1 = a1 (S(cur) + f) + c1 prev,  out2 = a2 (S(out1) + f) + c2 cur  launch_leapfrog2_src
+//     EPI_WAVE          out1 = k S(cur) + b cur + c prev,  out2 = k S(out1) + b out1 + c cur  launch_wave2_3d
+//                       (k travels where f travels, b in a1 / a2, c in c1 / c2; the centre cells u: at `u1`, `u2` below)
 // The 3D counterpart of kernels_2d_step2.hip.  EPI_SOURCE is not built: a 3D plan with a source runs single sweeps.
 //
 // Geometry: that of stencil3d_fused2_kernel (kernels_3d_fused.hip) at four rows per lane -- 256 threads, a wave = 2 row
@@ -115,13 +117,18 @@ __device__ __forceinline__ void load_window(double (&win)[6], const double *row)
     win[5] = 0.0;
 }
 
-// Three workgroups per CU (168 registers) in every instantiation, as stencil3d_fused2_kernel has; no scratch.  What keeps the
-// rule that reads both prev and f inside them: a finished accumulator slot is not cleared but reopened by its first tap
+// Workgroups per CU the kernel is bounded to, a function of the rule: the wave rule carries its centre cells of both levels
+// across an iteration (below), sixteen register pairs the 168 registers of three workgroups do not hold.
+constexpr int step23_wgs(int epi) { return epi_reads_u(epi) ? 2 : 3; }
+
+// Three workgroups per CU (168 registers) in every leapfrog instantiation, as stencil3d_fused2_kernel has; no scratch.  What
+// keeps the rule that reads both prev and f inside them: a finished accumulator slot is not cleared but reopened by its first tap
 // (scatter_row's FRESH), the window reads skip the two elements no tap uses, and the lane offsets stay 32-bit (below).
 template <int TAPSET, int EPI>
-__global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep23 a, const Taps27 W) {
+__global__ __launch_bounds__(256, step23_wgs(EPI)) void stencil3d_step2_kernel(const ArgsStep23 a, const Taps27 W) {
     static_assert(EPI != EPI_SOURCE, "a 3D plan with a source runs single sweeps");
     constexpr bool RF = epi_reads_f(EPI);
+    constexpr bool RU = epi_reads_u(EPI);
     constexpr int RY = kRY;
     constexpr int NIT = (kInH + kStageRows - 1) / kStageRows;
     __shared__ __attribute__((aligned(16))) double A[kInH * kInW];
@@ -190,6 +197,14 @@ __global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep2
     // the level-1 cells this lane owns in the output tile: it stores them to out1 as it publishes them
     const bool own1_col = cl >= 1 && cl <= kLanesX - 2 && col1 < a.n;
     const double c2 = EPI == EPI_LEAP ? a.c1 : a.c2;
+    // EPI_WAVE: the centre cells u of the plane each level completes next -- the lane's own pair (win[2], win[3]) of window
+    // rows 1 .. RY, taken from the scatter one iteration before the epilogue that reads them, when the tile still held that
+    // plane.  Level 1: cells of cur; level 2: the level-1 cells themselves.  (Other rules: never touched, no register.)
+    d2 u1[RY], u2[RY];
+    if constexpr (RU) {
+#pragma unroll
+        for (int r = 0; r < RY; ++r) u1[r].x = u1[r].y = u2[r].x = u2[r].y = 0.0;
+    }
 
     load_plane(0);
     write_plane();
@@ -225,6 +240,7 @@ __global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep2
         }
 
         // ---- level 1: plane p of cur (interior k0-2+p) -> level-1 planes p+1, p, p-1 ----
+        d2 n1[RY], n2[RY];  // (EPI_WAVE) the centre cells this iteration's scatters pass: next iteration's u1, u2
         {
             const double *strip = &A[strip_off];
 #pragma unroll
@@ -232,6 +248,12 @@ __global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep2
                 double win[6];
                 load_window(win, strip + j * kInW);
                 scatter_row<TAPSET, RY, PH, true>(a0, a1, win, j, W);
+                if constexpr (RU) {
+                    if (j >= 1 && j <= RY) {
+                        n1[j - 1].x = win[2];
+                        n1[j - 1].y = win[3];
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -248,9 +270,15 @@ __global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep2
                 const bool in = z_in && col1_in && row1 + r >= 0 && row1 + r < a.m;
                 d2 v = pv[r];
                 if (in) {
-                    v.x = step_epilogue<EPI>(a0[s][r], fv[r].x, a.a1, a.c1, pv[r].x);
-                    v.y = step_epilogue<EPI>(a1[s][r], fv[r].y, a.a1, a.c1, pv[r].y);
+                    if constexpr (RU) {
+                        v.x = step_epilogue<EPI>(a0[s][r], fv[r].x, a.a1, a.c1, pv[r].x, u1[r].x);
+                        v.y = step_epilogue<EPI>(a1[s][r], fv[r].y, a.a1, a.c1, pv[r].y, u1[r].y);
+                    } else {
+                        v.x = step_epilogue<EPI>(a0[s][r], fv[r].x, a.a1, a.c1, pv[r].x);
+                        v.y = step_epilogue<EPI>(a1[s][r], fv[r].y, a.a1, a.c1, pv[r].y);
+                    }
                 }
+                if constexpr (RU) u1[r] = n1[r];
                 *reinterpret_cast<d2 *>(&B[strip_off + r * kInW]) = v;
                 if (own_z && own1_col && sid * RY + r >= 1 && sid * RY + r <= kOutH && row1 + r < a.m) st16(a.out1 + pl1, cell1 + r * ldb, v);
             }
@@ -280,6 +308,12 @@ __global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep2
                 double win[6];
                 load_window(win, strip + j * kInW);
                 scatter_row<TAPSET, RY, PH2, true>(b0, b1, win, j, W);
+                if constexpr (RU) {
+                    if (j >= 1 && j <= RY) {
+                        n2[j - 1].x = win[2];
+                        n2[j - 1].y = win[3];
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -295,11 +329,20 @@ __global__ __launch_bounds__(256, 3) void stencil3d_step2_kernel(const ArgsStep2
                 for (int r = 0; r < RY; ++r) {
                     if (sid * RY + r < kOutH && rowo + r < a.m) {
                         d2 v;
-                        v.x = step_epilogue<EPI>(b0[s][r], gv[r].x, a.a2, c2, cv[r].x);
-                        v.y = step_epilogue<EPI>(b1[s][r], gv[r].y, a.a2, c2, cv[r].y);
+                        if constexpr (RU) {
+                            v.x = step_epilogue<EPI>(b0[s][r], gv[r].x, a.a2, c2, cv[r].x, u2[r].x);
+                            v.y = step_epilogue<EPI>(b1[s][r], gv[r].y, a.a2, c2, cv[r].y, u2[r].y);
+                        } else {
+                            v.x = step_epilogue<EPI>(b0[s][r], gv[r].x, a.a2, c2, cv[r].x);
+                            v.y = step_epilogue<EPI>(b1[s][r], gv[r].y, a.a2, c2, cv[r].y);
+                        }
                         st16(a.out2 + plo, cello + r * ldb, v);
                     }
                 }
+            }
+            if constexpr (RU) {
+#pragma unroll
+                for (int r = 0; r < RY; ++r) u2[r] = n2[r];
             }
         }
         if (more) write_plane();
@@ -382,6 +425,21 @@ hipError_t launch_leapfrog2_src_3d(const Plan &p, const double *prev, const doub
     a.a2 = a2;
     a.c2 = c2;
     return f ? launch_step23_e<EPI_LEAP_SRC>(p, a, begin, end, s) : launch_step23_e<EPI_LEAP_SCALED>(p, a, begin, end, s);
+}
+
+// Two wave steps over the interior planes [begin, end) (plans of wave_depth 2 in 3D): k in f's place, b as both scales.
+hipError_t launch_wave2_3d(const Plan &p, const double *prev, const double *cur, const double *k, double *out1, double *out2, double b,
+                           double c, int begin, int end, hipStream_t s) {
+    if (end <= begin) return hipSuccess;
+    ArgsStep23 a = {};
+    a.prev = prev;
+    a.cur = cur;
+    a.f = k;
+    a.out1 = out1;
+    a.out2 = out2;
+    a.a1 = a.a2 = b;
+    a.c1 = a.c2 = c;
+    return launch_step23_e<EPI_WAVE>(p, a, begin, end, s);
 }
 
 }  // namespace lora

@@ -1,7 +1,8 @@
 // leapfrog.cpp -- the leapfrog entries of the C ABI (include/lorastencil.h): u(t+1) = S(u(t)) + c u(t-1), the new level stored
 // over the oldest one, their forms with a source and a scale, a (S(u) + f) + c u-, and the variable-coefficient
-// wave steps k(x) S(u) + b u + c u- (two per launch in 2D only: kernels_2d_wave2.hip).  One step in place
-// (kernels_step.hip), two steps per launch in 2D (kernels_2d_step2.hip) and, behind option leap3, in 3D (kernels_3d_step2.hip),
+// wave steps k(x) S(u) + b u + c u- (two per launch in 2D: kernels_2d_wave2.hip, and, behind option wave3, in 3D:
+// kernels_3d_step2.hip).  One step in place (kernels_step.hip), two leapfrog steps per launch in 2D
+// (kernels_2d_step2.hip) and, behind option leap3, in 3D (kernels_3d_step2.hip),
 // the one run driver both rules go through (run_steps) and the host-buffer operator (its skeleton: hostrun.cpp).  The
 // coefficients and the buffers are call arguments: nothing here changes what a plan resolves to, and no run is cached in a graph.
 #include <hip/hip_runtime.h>
@@ -66,16 +67,16 @@ int step1_wave(const Plan &p, const void *d_cur, void *d_prev, const void *d_k, 
 
 int step2_wave(const Plan &p, const void *d_prev, const void *d_cur, const void *d_k, void *d_out1, void *d_out2, double b, double c,
                int begin, int end, hipStream_t s) {
-    const hipError_t e = launch_wave2_2d(p, static_cast<const double *>(d_prev), static_cast<const double *>(d_cur),
-                                         static_cast<const double *>(d_k), static_cast<double *>(d_out1), static_cast<double *>(d_out2),
-                                         b, c, begin, end, s);
+    const hipError_t e = launch_wave2(p, static_cast<const double *>(d_prev), static_cast<const double *>(d_cur),
+                                      static_cast<const double *>(d_k), static_cast<double *>(d_out1), static_cast<double *>(d_out2),
+                                      b, c, begin, end, s);
     return e == hipSuccess ? LORA_OK : failed("two-step wave kernel launch", e);
 }
 
 // LORA_EUNSUPPORTED for the plans that have no wave kernel: those plan_refused refuses (`two`: plans of wave depth below 2)
 int wave_refused(const Plan &p, bool two) {
     if (int rc = plan_refused(p, false)) return rc;
-    if (two && wave_depth(p) < 2) return unsupported("two wave steps per launch: 2D plans of the direct variant with an even innermost extent");
+    if (two && wave_depth(p) < 2) return unsupported("two wave steps per launch: 2D plans of the direct variant, 3D plans with option wave3 = 1, each with an even innermost extent");
     return LORA_OK;
 }
 

@@ -19,6 +19,7 @@ namespace lora {
 static thread_local int g_default_boundary = LORA_BC_REFERENCE;
 static thread_local int g_default_normalize = 0;
 static thread_local int g_default_leap3 = 0;
+static thread_local int g_default_wave3 = 0;
 static thread_local int g_default_coarse1 = 0;
 static thread_local int g_default_mgfuse = 0;
 
@@ -497,6 +498,8 @@ const Option kOptions[] = {
     range("fused_z_chunk", &Plan::fused_z_chunk, 0, 4096),
     // 3D fp64 leapfrog: two steps per launch (lora_plan_leapfrog_depth reads 2); chooses no kernel of the plain sweeps
     flag("leap3", &Plan::leap3),
+    // 3D fp64 wave steps: two per launch (lora_plan_wave_depth reads 2); chooses no kernel of the plain sweeps or the leapfrog rules
+    flag("wave3", &Plan::wave3),
     // multigrid cycles of this plan run a coarsest level that fits as one launch (lora_plan_cg_small); chooses no kernel of a sweep
     flag("coarse1", &Plan::coarse1),
     // multigrid cycles of this plan restrict a level's defect in the launch that computes it (lora_plan_mg_defect_restrict); chooses
@@ -601,6 +604,7 @@ int lora_plan_create(lora_plan **out, int shape, int dtype, const int *dims, con
     p.generic = odd_inner;
     p.boundary = lora::g_default_boundary;
     p.leap3 = lora::g_default_leap3;
+    p.wave3 = lora::g_default_wave3;
     p.coarse1 = lora::g_default_coarse1;
     p.mgfuse = lora::g_default_mgfuse;
     if (nd == 3) {
@@ -652,6 +656,12 @@ int lora_set_default_normalize(int on) {
 int lora_set_default_leap3(int on) {
     const int old = lora::g_default_leap3;
     lora::g_default_leap3 = on ? 1 : 0;
+    return old;
+}
+
+int lora_set_default_wave3(int on) {
+    const int old = lora::g_default_wave3;
+    lora::g_default_wave3 = on ? 1 : 0;
     return old;
 }
 

@@ -354,6 +354,12 @@ def set_default_leap3(on) -> int:
     return _lib.lib().lora_set_default_leap3(1 if on else 0)
 
 
+def set_default_wave3(on) -> int:
+    """Plan option "wave3" (3D fp64: two wave steps per launch) of the plans created afterwards on this thread, the ones of
+    run_host_wave included (lora_set_default_wave3).  Returns the previous value."""
+    return _lib.lib().lora_set_default_wave3(1 if on else 0)
+
+
 def set_default_coarse1(on) -> int:
     """Plan option "coarse1" (multigrid cycles run a coarsest level that fits as one launch) of the plans created afterwards on
     this thread, the ones of run_host_mg, run_host_pcg and run_host_theta_mg included (lora_set_default_coarse1).  Returns the
@@ -917,7 +923,8 @@ class Plan:
     # -- variable-coefficient wave steps: u+ = k S(u) + b u + c u-; d_k is a padded device grid, read on interior cells alone
     @property
     def wave_depth(self) -> int:
-        """0: no wave kernel; 1: single steps; 2: also the two-step launch, 2D only (lora_plan_wave_depth)."""
+        """0: no wave kernel; 1: single steps; 2: also the two-step launch: 2D, and 3D plans with option "wave3"
+        (lora_plan_wave_depth)."""
         return _lib.lib().lora_plan_wave_depth(self._h)
 
     def step_wave(self, d_cur, d_prev, d_k, b: float = 2.0, c: float = -1.0, stream=None):
